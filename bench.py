@@ -10,9 +10,18 @@ main loop, src/main.cu:415-431 - rendered by multi-frame launches (rt_render_dev
 frames per launch): every sample of every frame is traced, each pixel's frames are blended in order,
 and the image is bit-identical to K launches (--check verifies it; tests/test_gpu_parity.py).  What
 the single launch buys: a frame ends with a few expensive tiles running alone for half its duration,
-and the next frame, which has its own random stream, fills the idle GPU meanwhile.  The line also
-carries "frame_by_frame" (the same K steps with one launch per step, N = 1 only), and
+and the next frame, which has its own random stream, fills the idle GPU meanwhile.  With --full the line
+also carries "frame_by_frame" (the same K steps with one launch per step, N = 1 only), and
 --frame-by-frame makes that the measured mode.
+
+A plain run (no --full) does only what the headline needs: set up, W warm-up steps, the K timed steps,
+the outputs if --dump-outputs is given, and the JSON line (with the roofline, which takes no run of its
+own).  --full adds every side measurement and check described below: the frame_by_frame and pipelined
+legs, the CPU baseline and the VALU figure (N = 1), and for N > 1 the self-test, the weak-scaling and
+configs[4] extras and capi_multi.
+--dump-outputs DIR writes what the timed path computed in its last step, the frame a caller of
+rt_render_device_batch receives (H x W x 3 float32 progressive means), as DIR/frame.npy; an image above
+60 MiB is written as a fixed sample of its pixels (seed 0, rows of RGB in ascending pixel order).
 
 Workloads (--config, BASELINE.json configs[i]; --scene/--width/--height/--spp/--limit override):
     1  three-sphere Lambertian + sky, 1920x1080, 1024 spp, 8 bounces
@@ -34,7 +43,7 @@ belongs to rank b % N.)  The headline for every N is STRONG scaling of the confi
 the metric): K frames cut over N GPUs, each rank rendering its share of all K frames in one launch.  A
 single 1080p frame cannot scale (a pixel's 1024 samples are one sequential random stream and the most
 expensive tile alone takes ~95 % of a one-GPU frame), a sequence of frames can: each GPU
-overlaps its K x tiles/N tile-frames.  For N > 1 the line also carries, as extras, the weak-scaling
+overlaps its K x tiles/N tile-frames.  For N > 1 and --full the line also carries, as extras, the weak-scaling
 measurement (image area grows with N at fixed aspect and field of view), BASELINE configs[4]
 (3840x2160, 4096 spp) and "capi_multi": the same K frames through rt_render_multi_device - the C ABI's
 one-host-thread path a C++ maintainer of the reference would call - over all visible GPUs while the ranks wait,
@@ -45,7 +54,7 @@ When WORLD_SIZE is not set and N > 1 this script starts its own N ranks (torch.d
 touching the GPU and relays rank 0's line.  If RCCL cannot initialise the run FAILS (exit code 3) unless
 --allow-gloo-fallback is given.
 
-Besides the contract's keys the JSON line carries
+Besides the contract's keys the JSON line carries (valu and cpu_baseline with --full only)
   backend, world_size   the process group that moved the tiles ("none" for N = 1)
   roofline      the render kernel against the HBM roof (algorithmic bytes: 24 B per pixel per frame + the
                 scene once), with the rocprofv3-measured HBM bytes of the same launch
@@ -71,6 +80,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 FP32_VECTOR_PEAK_TFLOPS = 157.3
 MAX_BATCH = 32                 # RT_MAX_BATCH_FRAMES (rt_max_batch_frames lowers it for images whose planes would not fit)
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: a larger frame is written as a seeded sample of its pixels
 
 CONFIGS = {1: ("three_sphere", 1920, 1080, 1024, 8), 2: ("cube", 1920, 1080, 1024, 8),
            3: ("monkey", 1920, 1080, 1024, 8), 4: ("monkey", 3840, 2160, 4096, 8),
@@ -102,7 +112,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="N > 1: skip the weak-scaling, configs[4] and capi_multi side measurements")
     ap.add_argument("--capi-multi", default=None, metavar="DEVICES",
                     help="also time rt_render_multi_device from ONE process over these devices (e.g. 0,0 rehearses two ranks on one GPU); "
-                         "N > 1 does it over all visible GPUs unless --no-extras")
+                         "N > 1 with --full does it over all visible GPUs unless --no-extras")
     ap.add_argument("--capi-multi-child", action="store_true", help=argparse.SUPPRESS)     # internal: this process IS the capi_multi measurement
     ap.add_argument("--capi-self-test", action="store_true", help=argparse.SUPPRESS)        # internal: the child stops after its 4-spp first contact and prints that frame's hash
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -114,10 +124,15 @@ def parse_args(argv=None):
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses cuda:0 (rehearsal on a one-GPU box)")
     ap.add_argument("--check", action="store_true", help="rank 0 also renders the frames alone and checks the gathered frame equals it bit for bit")
     ap.add_argument("--self-test", action="store_true",
-                    help="N > 1 (on by default there unless --no-extras): before anything is timed, 2 frames at 4 spp through BOTH multi-GPU drivers "
+                    help="N > 1 (on with --full unless --no-extras): before anything is timed, 2 frames at 4 spp through BOTH multi-GPU drivers "
                          "(process group + gather, and rt_render_multi_device in a child) must equal rank 0 rendering alone, bit for bit")
     ap.add_argument("--no-self-test", action="store_true")
     ap.add_argument("--no-host-group", action="store_true", help=argparse.SUPPRESS)      # rehearsal: behave as if the gloo side group could not be created
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement and check: frame_by_frame and pipelined legs, CPU baseline and VALU figure (N = 1); "
+                         "self-test, weak-scaling and configs[4] extras and capi_multi (N > 1).  A plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last timed step produced to DIR/frame.npy (float32)")
     args = ap.parse_args(argv)
     scene, W, H, spp, limit = CONFIGS[args.config]
     args.scene = args.scene or scene
@@ -125,10 +140,12 @@ def parse_args(argv=None):
     args.height = args.height or H
     args.spp = args.spp or spp
     args.limit = limit if args.limit is None else args.limit
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     return args
 
 
-def spawn_ranks(n):
+def spawn_ranks(n, dump_outputs=None):
     """N > 1 without a launcher: start the N ranks as children of this process - which has not touched the GPU -
     and relay rank 0's line.  (Never re-exec a process that has initialised HIP.)"""
     with socket.socket() as s:
@@ -139,6 +156,8 @@ def spawn_ranks(n):
     env.setdefault("MASTER_ADDR", "127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if dump_outputs:
+        cmd += ["--dump-outputs", dump_outputs]        # absolute: the ranks run in ROOT (argparse keeps the last one)
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if lines:
@@ -265,7 +284,7 @@ def main():
         capi_multi_child(args)
         return
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        spawn_ranks(args.gpus)
+        spawn_ranks(args.gpus, args.dump_outputs)
 
     import importlib
     import numpy as np
@@ -411,22 +430,24 @@ def main():
 
     W, H, spp, limit = args.width, args.height, args.spp, args.limit
     self_test = None
-    if world > 1 and not args.no_self_test and (args.self_test or not args.no_extras):
+    if world > 1 and not args.no_self_test and (args.self_test or (args.full and not args.no_extras)):
         self_test = run_self_test(args, rt, dm, ctx, scene, sky, dev, rank, world, stream, measure, host_group, host_group_kind)
     if world > 1 and args.scaling == "weak":
         W, H = weak_image(args.width, args.height, world)
     batched = not args.frame_by_frame
     m = measure(W, H, spp, limit, args.warmup, args.steps, batched)
     elapsed, frame, kernel_ms, frames_per_launch, cam, rd = m["elapsed"], m["frame"], m["kernel_ms"], m["frames_per_launch"], m["cam"], m["rd"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame)
     per_frame = None
-    if batched and rank == 0 and world == 1 and not args.no_frame_by_frame_leg:
+    if args.full and batched and rank == 0 and world == 1 and not args.no_frame_by_frame_leg:
         # for the record: the same number of steps with one launch per frame (a single 1920x1080x1024spp render is
         # this figure); not the headline value
         f_elapsed = measure(W, H, spp, limit, 0, args.steps, False)["elapsed"]
         per_frame = {"value": W * H * spp * args.steps / f_elapsed / 1e6, "unit": "Msamples/s", "ms_per_step": f_elapsed / args.steps * 1e3,
                      "frames_per_s": args.steps / f_elapsed, "note": "one launch per step (the reference's main-loop cadence, src/main.cu:415-431)"}
     pipelined = None
-    if batched and rank == 0 and world == 1 and not args.no_frame_by_frame_leg and hasattr(rt, "frame_submit"):
+    if args.full and batched and rank == 0 and world == 1 and not args.no_frame_by_frame_leg and hasattr(rt, "frame_submit"):
         # one launch per frame through rt_frame_submit / rt_frame_collect: seeds handed over one call at a time (the reference's loop
         # draws them from the wall clock), the next frames submitted before the oldest is waited for, each on 1 / depth of the CUs
         def run_pipelined(depth, n_frames):
@@ -459,7 +480,7 @@ def main():
         pipelined["note"] = ("one launch per step through rt_frame_submit / rt_frame_collect: each seed handed over at call time, frames_in_flight submitted "
                              "before the oldest is waited for, each on 1 / frames_in_flight of the CUs; the time includes filling and draining the pipeline")
     extras = {}
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         if args.scaling != "weak":
             # side figure: weak scaling (image area grows with N at the same aspect ratio and field of view)
             w_W, w_H = weak_image(args.width, args.height, world)
@@ -477,7 +498,7 @@ def main():
     capi_devices = None
     if args.capi_multi:
         capi_devices = [int(x) for x in args.capi_multi.split(",")]
-    elif world > 1 and not args.no_extras and batched:
+    elif world > 1 and args.full and not args.no_extras and batched:
         capi_devices = [0] * world if args.share_gpu else list(range(min(world, torch.cuda.device_count())))
     capi_after_group = capi_runs_after_group(bool(capi_devices), world, backend, host_group is not None)
     if capi_devices and not capi_after_group:
@@ -555,7 +576,7 @@ def main():
         out["pipelined"] = pipelined
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb, st = cpu_baseline(rt, objs, sky, W, H, limit, spp)
             out["cpu_baseline"] = cb
             fps = flops_per_sample(st)
@@ -582,6 +603,20 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1 and not capi_after_group:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the timed path's result of its last step, the [H, W, 3] float32 frame, as out_dir/frame.npy.
+    Above DUMP_MAX_BYTES it is a fixed sample instead: the RGB rows of pixels drawn without replacement with seed 0,
+    in ascending pixel order (the same pixels for the same image size in every run)."""
+    import numpy as np
+    img = np.ascontiguousarray(frame.detach().cpu().numpy(), dtype=np.float32)
+    if img.nbytes > DUMP_MAX_BYTES:
+        px = img.reshape(-1, img.shape[-1])
+        pick = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_MAX_BYTES // px[0].nbytes, replace=False))
+        img = px[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), img)
 
 
 def capi_runs_after_group(have_devices, world, backend, have_host_group):

@@ -105,3 +105,32 @@ def test_capi_multi_never_runs_under_an_rccl_barrier():
     assert f(True, 1, "none", False) is False         # one GPU: --capi-multi runs inline
     a = bench.parse_args(["--gpus", "2", "--no-host-group", "--self-test"])
     assert a.no_host_group and a.self_test and not a.no_self_test
+
+
+def test_full_and_dump_outputs_options():
+    """a plain run times the headline only (--full adds the side legs); --dump-outputs is made absolute, so ranks started
+    in the repository root write where the caller asked"""
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    a = b.parse_args(["--full", "--dump-outputs", "outs"])
+    assert a.full is True and a.dump_outputs == os.path.abspath("outs")
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    b = _bench()
+    frame = torch.arange(6 * 10 * 3, dtype=torch.float32).reshape(6, 10, 3) / 7.0
+    b.dump_outputs(str(tmp_path / "small"), frame)
+    got = np.load(tmp_path / "small" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.numpy())
+    # above the size limit: the same seeded pixels, in ascending order, on every call
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 12 * 20)
+    b.dump_outputs(str(tmp_path / "a"), frame)
+    b.dump_outputs(str(tmp_path / "b"), frame)
+    sa, sb = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "b" / "frame.npy")
+    assert sa.shape == (20, 3) and sa.dtype == np.float32 and np.array_equal(sa, sb)
+    px = frame.numpy().reshape(-1, 3)
+    idx = [int(np.flatnonzero((px == row).all(axis=1))[0]) for row in sa]
+    assert idx == sorted(set(idx))

@@ -298,7 +298,7 @@ def test_bench_two_ranks_on_one_gpu():
     (no launcher: the script spawns its own ranks before touching the GPU).  Two ranks share cuda:0 over gloo -
     RCCL refuses duplicate devices, so this is the closest a one-GPU box gets to the multi-GPU run.  The
     headline is strong scaling of the metric's 1920x1080 image; the gathered frame must equal the single-launch
-    frame bit for bit; weak scaling and configs[4] ride along as extras."""
+    frame bit for bit; weak scaling and configs[4] ride along as extras (--full)."""
     import json
     import os
     import subprocess
@@ -306,7 +306,7 @@ def test_bench_two_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--spp", "4", "--backend", "gloo", "--share-gpu", "--check", "--no-cpu-baseline"]
+           "--spp", "4", "--backend", "gloo", "--share-gpu", "--check", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -322,12 +322,41 @@ def test_bench_two_ranks_on_one_gpu():
     # under a launcher, weak scaling as the measured mode: the image area grows with N at the same aspect ratio
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29600 + os.getpid() % 300), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--spp", "8", "--backend", "gloo", "--share-gpu", "--check", "--no-cpu-baseline", "--scaling", "weak"]
+           "--spp", "8", "--backend", "gloo", "--share-gpu", "--check", "--no-cpu-baseline", "--scaling", "weak", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["scaling"] == "weak" and j["config"]["image"] == "2720x1530" and j["gathered_equals_single_launch"] is True
     assert "2720x1530" in j["metric"]
+
+
+def test_bench_plain_run_dumps_the_timed_frame(rt, ctx, tmp_path):
+    """a plain `bench.py --gpus 1` run: the contract's keys, none of the --full legs, and --dump-outputs writes the frame of
+    the timed steps, which is the frame rt_render_device_batch renders for those seeds"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "4",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "Msamples/s"
+    assert j["higher_is_better"] is True and j["dtype"] == "f32" and "1920x1080" in j["metric"]
+    assert not {"cpu_baseline", "valu", "frame_by_frame", "pipelined", "extras"} & set(j)
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 3)
+    objs, sky = rt.scenes.monkey()
+    scene = ctx.commit(rt.SceneObjects(objs))
+    want = torch.zeros((1080, 1920, 3), dtype=torch.float32, device="cuda:0")
+    rt.render_device_batch(ctx, scene, rt.Camera(1920, 1080), rt.RenderData(4, 8, True, sky), [12345, 12346, 12347], 0, want.data_ptr(),
+                           stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert eq(got, want.cpu().numpy())
 
 
 def test_textured_and_refractive_primitives(rt, orc, ctx, models_dir):
