@@ -4,6 +4,7 @@
  * (src/dispatch.cu:104-163): where the reference allocates and frees four device buffers per
  * frame and copies the frame element-wise out of managed memory, the context here keeps
  * persistent HBM frame buffers and the device-buffer entry point takes caller-owned HBM.
+ * What the launches' tile orders are is worked out in rt_schedule.h.
  *
  * There is no CPU fallback: rt_ctx_create fails when HIP has no device.
  */
@@ -14,15 +15,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <new>
-#include <set>
 #include <queue>
+#include <set>
 #include <string>
 #include <vector>
 
 #include "rt_host.h"
+#include "rt_schedule.h"
 
 extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, int has_mesh, int scene_in_lds, int threads, int blocks, size_t lds_bytes, hipStream_t stream);
 extern "C" int rt_kernel_blocks_per_cu(int has_mesh, int scene_in_lds, int threads, size_t lds_bytes);
@@ -38,6 +41,26 @@ extern "C" hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *o
 
 namespace {
 
+/* A device buffer of at least `cap` elements, freed with its owner.  grow() keeps a large enough buffer and otherwise
+ * replaces it (the content is not kept; an empty request still gets 16 bytes); a failure leaves {nullptr, 0}. */
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t grow(size_t need)
+    {
+        if (cap >= need && p) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&p, (need ? need : 16 / sizeof(T)) * sizeof(T));
+        if (e == hipSuccess) cap = need; else p = nullptr;
+        return e;
+    }
+};
+
 /* a tile list on the device, found again by content (lists are a few KB to ~130 KB and change only with the view).
  * `host` is a pinned copy: what a hash hit is compared with (a 64-bit hash alone would render the wrong
  * tiles on a collision) and what the asynchronous upload reads.  An entry is recycled least-recently-used first; the
@@ -45,21 +68,23 @@ namespace {
 struct DevList {
     uint64_t hash = 0;
     int n = 0;
-    uint32_t *d = nullptr;
-    uint32_t *host = nullptr;            /* pinned, `cap` entries */
-    size_t cap = 0;
+    DevBuf<uint32_t> d;
+    uint32_t *host = nullptr;            /* pinned, d.cap entries */
     uint64_t seq = 0;                    /* rt_ctx::list_seq when last handed out (LRU order; > pin_floor: not recyclable) */
     hipStream_t stream = nullptr;        /* the stream of the launches it was last handed out for */
     hipEvent_t ev = nullptr;             /* scratch: "everything queued on `stream` so far" (orders a reuse on another stream) */
     hipEvent_t ev_up = nullptr;          /* "the upload from `host` is done": the pinned copy may be rewritten */
+    ~DevList() { clear(); if (ev) (void)hipEventDestroy(ev); if (ev_up) (void)hipEventDestroy(ev_up); }
+    /* no content and no buffers: what every failure leaves behind */
+    void clear() { d.release(); if (host) (void)hipHostFree(host); host = nullptr; n = 0; hash = 0; }
 };
 
 /* the root's landing area for one source context's compact image (rt_gather, rt_render_multi_device) */
 struct Stage {
-    float *d = nullptr;
-    size_t cap = 0;                      /* floats */
+    DevBuf<float> d;
     hipEvent_t ev_free = nullptr;        /* recorded on the root's stream after the last de-interleave that read the area */
     bool used = false;
+    ~Stage() { if (ev_free) (void)hipEventDestroy(ev_free); }
 };
 
 /* rt_render_multi[_device] with cost-balanced tile lists: what the root remembers between calls */
@@ -69,6 +94,27 @@ struct MultiState {
     std::vector<std::vector<uint32_t>> lists, costs, peaks;   /* per rank: its tiles (image indices), their measured costs and peak pixel costs */
 };
 
+/* where the measured tile costs of the current view are */
+enum class Costs { none, on_device, on_host };
+
+/* the current view: (scene, camera, image, tile spec).  Its tiles, their order and what they cost */
+struct View {
+    std::vector<uint32_t> key;           /* what the state below was built for */
+    std::vector<uint32_t> tiles;         /* local tile t of the launch -> the tile's index in the image */
+    bool use_order = false;              /* the scene has a mesh: tickets go through `order` (else the kernel scatters raster order) */
+    std::vector<uint32_t> order;         /* ticket -> local tile (host copy of d_order) */
+    DevBuf<uint32_t> d_order;
+    DevBuf<uint32_t> d_cost, d_peak;     /* per tile: the weighted work of its pixels and of its most expensive one, collected by a launch */
+    Costs costs = Costs::none;           /* on_device: a launch of this view collected them; on_host: cost / peak hold them and the order is refined */
+    int cost_spp = 0;                    /* rays_per_pixel of the launch the figures come from (a pilot: 1) */
+    std::vector<uint32_t> cost, peak;    /* the measured (or caller-supplied) costs and peak pixel costs, per local tile */
+    int num_heavy = 0;                   /* refined order: how many leading tiles go first for ALL frames of a multi-frame launch */
+    /* multi-frame launches, once the tile costs of the view are known: the whole schedule (ticket -> tile, frame),
+     * longest job first over all frames (rt_sched::build_job_order) */
+    DevBuf<uint32_t> d_jobs;
+    int job_frames = 0;                  /* what the uploaded schedule was built for */
+};
+
 }  // namespace
 
 /* One frame in flight of the pipelined per-frame entry points (rt_frame_submit / rt_frame_collect): everything a launch
@@ -76,8 +122,7 @@ struct MultiState {
 struct FrameSlot {
     hipStream_t stream = nullptr;
     uint32_t *counter = nullptr;        /* 1 KB like rt_ctx::tile_counter */
-    float *plane = nullptr;
-    size_t plane_cap = 0;               /* floats */
+    DevBuf<float> plane;
     hipEvent_t ev_done = nullptr;       /* the frame's render kernel has finished (recorded on `stream`) */
     hipEvent_t ev_free = nullptr;       /* the blend that read the plane has finished (recorded on `stream` too: the blend runs there) */
     hipEvent_t ev_call = nullptr;       /* where the collector's stream stood when it asked for the frame */
@@ -93,8 +138,7 @@ struct Pipeline {
     int pending = 0;
     int depth = RT_PIPELINE_DEFAULT_DEPTH;   /* rt_frame_depth: how many frames the caller keeps in flight */
     int last_fold = -1;                 /* the slot whose frame was folded last (folds into one frame happen in collection order) */
-    uint32_t *d_list = nullptr;         /* the view's tile list (listed tile specs), shared by the frames in flight */
-    size_t list_cap = 0;
+    DevBuf<uint32_t> d_list;            /* the view's tile list (listed tile specs), shared by the frames in flight */
     std::vector<uint32_t> list_host;
 };
 
@@ -113,61 +157,30 @@ struct rt_ctx {
     bool launched = false;
     /* multi-GPU entry points (rt_render_multi*): this rank's compact buffer, its stream and "my image is in the root's
      * staging area" event; on the root also the staging areas, one per source context */
-    float *d_bands = nullptr;
-    size_t bands_cap = 0;                /* floats */
+    DevBuf<float> d_bands;
     std::map<rt_ctx *, Stage> stages;
     hipStream_t multi_stream = nullptr;
     hipEvent_t ev_multi = nullptr;
     MultiState multi;
     std::map<int, int> peer_ok;          /* device -> 1 direct access both ways, 0 refused */
     /* persistent frame buffers for the host-buffer entry point */
-    float *d_prev = nullptr, *d_out = nullptr;
-    size_t frame_bytes = 0;
-    /* ---- the current view: (scene, camera, image, tile spec).  Its tiles, their order and what they cost ---- */
-    std::vector<uint32_t> order_key;     /* what the view state below was built for */
-    std::vector<uint32_t> tiles_host;    /* local tile t of the launch -> the tile's index in the image */
-    std::vector<uint32_t> order_host;    /* ticket -> local tile (host copy of d_tile_order), when the view uses an order */
-    bool use_order = false;
-    uint32_t *d_tile_order = nullptr;
-    size_t tile_order_cap = 0;
-    uint32_t *d_tile_cost = nullptr;     /* per tile: the weighted work of its pixels, collected by the first launch of a view */
-    size_t tile_cost_cap = 0;
-    uint32_t *d_tile_peak = nullptr;     /* ... and of its most expensive pixel */
-    size_t tile_peak_cap = 0;
-    int cost_spp = 0;                    /* rays_per_pixel of the launch the figures come from (a pilot: 1) */
-    int cost_state = 0;                  /* 0 nothing, 1 a launch of this view collected costs, 2 cost_host holds them (and the order is refined) */
-    std::vector<uint32_t> cost_host;     /* the measured (or caller-supplied) costs, per local tile */
-    std::vector<uint32_t> peak_host;     /* ... and peak pixel costs: what the schedule sorts by */
-    int order_num_heavy = 0;             /* refined order: how many leading tiles go first for ALL frames of a multi-frame launch */
-    float *d_partial = nullptr;          /* multi-frame launches: one plane of per-pixel frame means per frame */
-    size_t partial_cap = 0;              /* floats */
-    /* multi-frame launches, once the tile costs of the view are known: the whole schedule (ticket -> tile, frame),
-     * longest job first over all frames (see build_job_order) */
-    uint32_t *d_job_order = nullptr;
-    size_t job_cap = 0;
-    int job_frames = 0;                  /* what the uploaded schedule was built for (with order_key) */
-    std::vector<DevList> dev_lists;
+    DevBuf<float> d_prev, d_out;
+    View view;
+    DevBuf<float> d_partial;             /* multi-frame launches: one plane of per-pixel frame means per frame; the pilot's scratch plane */
+    std::deque<DevList> dev_lists;       /* (a deque: an entry stays where it is while others are added) */
     size_t dev_list_cap = 64;            /* cached tile lists; beyond that the least recently used entry is recycled (raised when one call pins more) */
     uint64_t list_seq = 0, pin_floor = ~0ull;   /* entries handed out after pin_floor are held by the running call (rt_render_multi_device) */
     /* knobs (RT_AMD_*), none changes an image */
-    int heavy_top = 1024;                /* RT_AMD_HEAVY_TOP: the refined order moves that many tiles at most to the front (0 = never refine) */
-    int lpt = 1;                         /* RT_AMD_LPT=0: the round-1 ticket order (heavy tiles of frame 0, 1, ... first) */
-    int lpt_top = 1 << 30;               /* RT_AMD_LPT_TOP: at most this many tiles (most expensive first) are scheduled by cost */
-    int pilot = 1, pilot_min_spp = 32;   /* RT_AMD_PILOT=0: no pilot launch for a new view; RT_AMD_PILOT_MIN_SPP: only for at least this many samples per pixel */
-    int lpt_by_peak = 1, top_by_peak = 0; /* RT_AMD_LPT_BY_PEAK: the multi-frame schedule sorts by the tile's peak pixel cost (0: by its summed cost); RT_AMD_TOP_BY_PEAK: so does the
-                                          * one-frame order (default 0: by the sum - same-box A/B, one 1080p frame: monkey 509 vs 526 ms, cube 171 vs 178, reference scene 0 3,104 vs 3,083) */
-    int heavy_first = 1;                 /* RT_AMD_HEAVY_FIRST=0 disables */
     int work_threshold = RT_DEF_WORK_THRESHOLD;      /* lanes; RT_AMD_WORK_THRESHOLD */
     int descend_keep = RT_DEF_DESCEND_KEEP;       /* RT_AMD_DESCEND_KEEP (0..64): 0 = run every descent to its end */
-    int tile_scatter = 1;        /* RT_AMD_TILE_SCATTER=0: hand tiles out in raster order */
     int ready_break = RT_DEF_READY_BREAK;        /* lanes; RT_AMD_READY_BREAK; 65 = never */
     int hit_break = RT_DEF_HIT_BREAK;          /* lanes; RT_AMD_HIT_BREAK */
     int hit_low = RT_DEF_HIT_LOW, mix_break = -1;                 /* RT_AMD_HIT_LOW, RT_AMD_MIX_BREAK (0 = that rule off; -1 = not set: the default of the scene's workgroup shape) */
     int shade_batch = RT_DEF_SHADE_BATCH;        /* lanes; RT_AMD_SHADE_BATCH (1..64) */
     Pipeline pipe;
-    int pipe_share = 2;                          /* RT_AMD_PIPE_SHARE: pipelined frames run on 1 / depth of the CUs - 0 never, 1 always, 2 when a workgroup fills a CU */
     int multi_careful = 0;                       /* RT_AMD_MULTI_CAREFUL=1: rt_render_multi_device waits on the host after every phase (diagnosis) */
 };
+
 
 struct rt_scene {
     rt_ctx *ctx = nullptr;
@@ -220,13 +233,37 @@ uint64_t fnv1a(const void *data, size_t bytes, uint64_t h = 1469598103934665603u
 void pin_tile_lists(rt_ctx *ctx) { ctx->pin_floor = ctx->list_seq; }
 void unpin_tile_lists(rt_ctx *ctx) { ctx->pin_floor = ~0ull; }
 
-void free_dev_list(DevList &dl)
+
+/* `list` into the entry `dl` and on its way to the device on `stream`.  A recycled entry's new upload must not overtake a
+ * queued launch that still reads the old content (same stream: stream order; another stream: an event), and the pinned
+ * copy is rewritten only once ITS last upload is done - which it has been since dev_list_cap lists ago, so that wait
+ * returns at once.  On an error *what says which step failed. */
+hipError_t fill_dev_list(DevList &dl, bool recycled, const uint32_t *list, int n, hipStream_t stream, const char **what)
 {
-    if (dl.d) (void)hipFree(dl.d);
-    if (dl.host) (void)hipHostFree(dl.host);
-    if (dl.ev) (void)hipEventDestroy(dl.ev);
-    if (dl.ev_up) (void)hipEventDestroy(dl.ev_up);
-    dl = DevList();
+    hipError_t e = hipSuccess;
+    if (recycled) {
+        *what = "ordering a tile list's reuse";
+        e = hipEventRecord(dl.ev, dl.stream);
+        if (e == hipSuccess && dl.stream != stream) e = hipStreamWaitEvent(stream, dl.ev, 0);
+        if (e != hipSuccess) return e;
+    }
+    if (dl.d.cap < (size_t)n) {
+        /* a larger buffer: the old one goes once the launches reading it are done (the event just recorded) */
+        if (dl.d.p) (void)hipEventSynchronize(dl.ev);    /* (rare: lists of one image size share a capacity) */
+        dl.clear();
+        const size_t cap = (size_t)n + (size_t)n / 4 + 64;
+        *what = "allocating a tile list";
+        if ((e = dl.d.grow(cap)) != hipSuccess) return e;
+        *what = "allocating a tile list's staging copy";
+        if ((e = hipHostMalloc((void **)&dl.host, cap * 4, hipHostMallocDefault)) != hipSuccess) { dl.host = nullptr; return e; }
+    } else if (dl.n > 0) {
+        (void)hipEventSynchronize(dl.ev_up);
+    }
+    std::memcpy(dl.host, list, (size_t)n * 4);
+    *what = "uploading a tile list";
+    e = hipMemcpyAsync(dl.d.p, dl.host, (size_t)n * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipEventRecord(dl.ev_up, stream);
+    return e;
 }
 
 /* `list` (host) on ctx's GPU, for launches the caller queues on `stream` after this call.  A list seen before costs a hash
@@ -234,7 +271,8 @@ void free_dev_list(DevList &dl)
  * pinned buffer and is uploaded asynchronously on `stream`, behind (hipStreamWaitEvent) whatever was queued on the stream
  * the entry last served - no host synchronisation on the steady-state path, and no device-wide one ever (round 3 emptied a
  * full cache after hipDeviceSynchronize and waited for every upload).  The pointer stays valid until the entry
- * is recycled: after dev_list_cap other lists, and never while pinned. */
+ * is recycled: after dev_list_cap other lists, and never while pinned.  An entry that fails is left empty (a new one is
+ * dropped). */
 rt_status device_tile_list(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t stream, const uint32_t **out)
 {
     *out = nullptr;
@@ -249,7 +287,7 @@ rt_status device_tile_list(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t
                 dl.stream = stream;
             }
             dl.seq = ++ctx->list_seq;
-            *out = dl.d;
+            *out = dl.d.p;
             return RT_OK;
         }
     DevList *slot = nullptr;
@@ -258,55 +296,19 @@ rt_status device_tile_list(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t
             if ((ctx->pin_floor == ~0ull || dl.seq <= ctx->pin_floor) && (!slot || dl.seq < slot->seq)) slot = &dl;
         if (!slot) ctx->dev_list_cap = ctx->dev_lists.size() + 1;      /* everything is pinned by the running call: grow */
     }
-    if (!slot) {
+    const bool recycled = slot != nullptr;
+    if (!recycled) {
         ctx->dev_lists.emplace_back();
         slot = &ctx->dev_lists.back();
-        RT_HIP(ctx, hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming), "creating a tile list's event");
-        RT_HIP(ctx, hipEventCreateWithFlags(&slot->ev_up, hipEventDisableTiming), "creating a tile list's event");
-    } else {
-        /* recycle: the new upload must not overtake a queued launch that still reads the old content (same stream: stream
-         * order; another stream: an event), and the pinned copy is rewritten only once ITS last upload is done - which it
-         * has been since dev_list_cap lists ago, so that wait returns at once */
-        RT_HIP(ctx, hipEventRecord(slot->ev, slot->stream), "recording a tile list's last use");
-        if (slot->stream != stream) RT_HIP(ctx, hipStreamWaitEvent(stream, slot->ev, 0), "ordering a tile list's reuse");
+        hipError_t e = hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&slot->ev_up, hipEventDisableTiming);
+        if (e != hipSuccess) { ctx->dev_lists.pop_back(); return hip_fail(ctx, e, "creating a tile list's event"); }
     }
-    if (slot->cap < (size_t)n) {
-        /* a larger buffer: the old one goes once the launches reading it are done (the event just recorded) */
-        if (slot->d) { (void)hipEventSynchronize(slot->ev); (void)hipFree(slot->d); (void)hipHostFree(slot->host); slot->d = nullptr; slot->host = nullptr; }   /* (rare: lists of one image size share a capacity) */
-        const size_t cap = (size_t)n + (size_t)n / 4 + 64;
-        RT_HIP(ctx, hipMalloc((void **)&slot->d, cap * 4), "allocating a tile list");
-        hipError_t e = hipHostMalloc((void **)&slot->host, cap * 4, hipHostMallocDefault);
-        if (e != hipSuccess) { (void)hipFree(slot->d); slot->d = nullptr; slot->cap = 0; slot->n = 0; slot->hash = 0; return hip_fail(ctx, e, "allocating a tile list's staging copy"); }
-        slot->cap = cap;
-    } else if (slot->n > 0) {
-        (void)hipEventSynchronize(slot->ev_up);
-    }
-    std::memcpy(slot->host, list, (size_t)n * 4);
+    const char *what = "";
+    const hipError_t e = fill_dev_list(*slot, recycled, list, n, stream, &what);
+    if (e != hipSuccess) { slot->clear(); return hip_fail(ctx, e, what); }
     slot->hash = h; slot->n = n; slot->stream = stream; slot->seq = ++ctx->list_seq;
-    hipError_t e = hipMemcpyAsync(slot->d, slot->host, (size_t)n * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipEventRecord(slot->ev_up, stream);
-    if (e != hipSuccess) { slot->n = 0; slot->hash = 0; return hip_fail(ctx, e, "uploading a tile list"); }
-    *out = slot->d;
-    return RT_OK;
-}
-
-rt_status grow(rt_ctx *ctx, float **buf, size_t *cap, size_t need, const char *what)
-{
-    if (*cap >= need && *buf) return RT_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    RT_HIP(ctx, hipMalloc((void **)buf, (need ? need : 4) * 4), what);
-    *cap = need;
-    return RT_OK;
-}
-
-rt_status grow_u32(rt_ctx *ctx, uint32_t **buf, size_t *cap, size_t need, const char *what)
-{
-    if (*cap >= need && *buf) return RT_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr; *cap = 0;
-    RT_HIP(ctx, hipMalloc((void **)buf, (need ? need : 1) * 4), what);
-    *cap = need;
+    *out = slot->d.p;
     return RT_OK;
 }
 
@@ -340,20 +342,10 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     ctx->total_mem = prop.totalGlobalMem;
     if (const char *e = getenv("RT_AMD_WORK_THRESHOLD")) { int v = atoi(e); if (v >= 1 && v <= 64) ctx->work_threshold = v; }
     if (const char *e = getenv("RT_AMD_DESCEND_KEEP")) { int v = atoi(e); if (v >= 0 && v <= 64) ctx->descend_keep = v; }
-    if (const char *e = getenv("RT_AMD_TILE_SCATTER")) ctx->tile_scatter = atoi(e) != 0;
-    if (const char *e = getenv("RT_AMD_HEAVY_FIRST")) ctx->heavy_first = atoi(e) != 0;
-    if (const char *e = getenv("RT_AMD_HEAVY_TOP")) { int v = atoi(e); if (v >= 0) ctx->heavy_top = v; }
-    if (const char *e = getenv("RT_AMD_LPT")) ctx->lpt = atoi(e) != 0;
-    if (const char *e = getenv("RT_AMD_LPT_TOP")) { int v = atoi(e); if (v >= 0) ctx->lpt_top = v; }
-    if (const char *e = getenv("RT_AMD_PILOT")) ctx->pilot = atoi(e) != 0;
-    if (const char *e = getenv("RT_AMD_PILOT_MIN_SPP")) { int v = atoi(e); if (v >= 1) ctx->pilot_min_spp = v; }
-    if (const char *e = getenv("RT_AMD_LPT_BY_PEAK")) ctx->lpt_by_peak = atoi(e) != 0;
-    if (const char *e = getenv("RT_AMD_TOP_BY_PEAK")) ctx->top_by_peak = atoi(e) != 0;
     if (const char *e = getenv("RT_AMD_HIT_BREAK")) { int v = atoi(e); if (v >= 1 && v <= 65) ctx->hit_break = v; }
     if (const char *e = getenv("RT_AMD_HIT_LOW")) { int v = atoi(e); if (v >= 0 && v <= 65) ctx->hit_low = v; }
     if (const char *e = getenv("RT_AMD_MIX_BREAK")) { int v = atoi(e); if (v >= 0 && v <= 130) ctx->mix_break = v; }
     if (const char *e = getenv("RT_AMD_SHADE_BATCH")) { int v = atoi(e); if (v >= 1 && v <= 64) ctx->shade_batch = v; }
-    if (const char *e = getenv("RT_AMD_PIPE_SHARE")) { int v = atoi(e); if (v >= 0 && v <= 2) ctx->pipe_share = v; }
     if (const char *e = getenv("RT_AMD_MULTI_CAREFUL")) ctx->multi_careful = atoi(e) != 0;
     if (const char *e = getenv("RT_AMD_READY_BREAK")) { int v = atoi(e); if (v >= 1 && v <= 65) ctx->ready_break = v; }
     if (hipMalloc((void **)&ctx->tile_counter, 1024) != hipSuccess ||
@@ -380,40 +372,24 @@ extern "C" void rt_ctx_destroy(rt_ctx *ctx)
             auto it = r->stages.find(ctx);
             if (it == r->stages.end()) continue;
             (void)hipSetDevice(r->device);
-            if (it->second.ev_free) { (void)hipEventSynchronize(it->second.ev_free); (void)hipEventDestroy(it->second.ev_free); }
-            if (it->second.d) (void)hipFree(it->second.d);
+            if (it->second.ev_free) (void)hipEventSynchronize(it->second.ev_free);
             r->stages.erase(it);
         }
     }
     (void)hipSetDevice(ctx->device);
     if (ctx->tile_counter) (void)hipFree(ctx->tile_counter);
-    if (ctx->d_prev) (void)hipFree(ctx->d_prev);
-    if (ctx->d_out) (void)hipFree(ctx->d_out);
-    if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
-    if (ctx->d_tile_cost) (void)hipFree(ctx->d_tile_cost);
-    if (ctx->d_tile_peak) (void)hipFree(ctx->d_tile_peak);
-    if (ctx->d_job_order) (void)hipFree(ctx->d_job_order);
-    if (ctx->d_partial) (void)hipFree(ctx->d_partial);
-    if (ctx->d_bands) (void)hipFree(ctx->d_bands);
     for (FrameSlot &fs : ctx->pipe.slots) {
         if (fs.stream) { (void)hipStreamSynchronize(fs.stream); (void)hipStreamDestroy(fs.stream); }
         if (fs.counter) (void)hipFree(fs.counter);
-        if (fs.plane) (void)hipFree(fs.plane);
         if (fs.ev_done) (void)hipEventDestroy(fs.ev_done);
         if (fs.ev_free) (void)hipEventDestroy(fs.ev_free);
         if (fs.ev_call) (void)hipEventDestroy(fs.ev_call);
-    }
-    if (ctx->pipe.d_list) (void)hipFree(ctx->pipe.d_list);
-    for (DevList &dl : ctx->dev_lists) free_dev_list(dl);
-    for (auto &kv : ctx->stages) {
-        if (kv.second.d) (void)hipFree(kv.second.d);
-        if (kv.second.ev_free) (void)hipEventDestroy(kv.second.ev_free);
     }
     if (ctx->multi_stream) (void)hipStreamDestroy(ctx->multi_stream);
     if (ctx->ev_multi) (void)hipEventDestroy(ctx->ev_multi);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-    delete ctx;
+    delete ctx;                          /* (the device buffers, tile lists and staging areas go with it) */
 }
 
 extern "C" const char *rt_last_error(const rt_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -563,12 +539,6 @@ extern "C" int32_t rt_tile_owned_rows(const rt_tile_spec *t, int32_t height)
     return owned * t->band_rows;
 }
 
-extern "C" int32_t rt_max_batch_frames(rt_ctx *ctx, int32_t width, int32_t height)
-{
-    if (!ctx || width <= 0 || height <= 0) return 1;
-    return batch_cap(ctx, (size_t)width * (size_t)height * 3);
-}
-
 /* Longest-processing-time-first ownership (see include/rt_amd.h) */
 extern "C" rt_status rt_partition_tiles(const uint32_t *cost, int32_t tiles_x, int32_t tiles_y, int32_t n_ranks, int32_t *owner)
 {
@@ -596,6 +566,12 @@ extern "C" rt_status rt_partition_tiles(const uint32_t *cost, int32_t tiles_x, i
     return RT_OK;
 }
 
+extern "C" int32_t rt_max_batch_frames(rt_ctx *ctx, int32_t width, int32_t height)
+{
+    if (!ctx || width <= 0 || height <= 0) return 1;
+    return batch_cap(ctx, (size_t)width * (size_t)height * 3);
+}
+
 /* persistent waves: enough workgroups to fill the chip, each wave pulls 8x8 tiles */
 static int launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles)
 {
@@ -605,47 +581,8 @@ static int launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles
     return blocks > needed ? needed : blocks;
 }
 
-/* the schedule of a multi-frame launch (see its use in render_frames): `order` is the launch's tile order
- * (any permutation of 0..n-1; ties in cost keep it), cost[t] the measured cost of tile t - bit 0 set if a ray of the
- * tile entered a mesh: those are the long jobs; the others (sky, ground) follow frame by frame */
-static void build_job_order(const std::vector<uint32_t> &order, const std::vector<uint32_t> &cost, const std::vector<uint32_t> &peak, uint32_t top_max,
-                            uint32_t frames, std::vector<uint32_t> &jobs)
-{
-    const uint32_t n = (uint32_t)order.size();
-    std::vector<uint32_t> idx;
-    idx.reserve(n);
-    for (uint32_t t : order) if (cost[t] & 1u) idx.push_back(t);
-    /* a job lasts as long as its longest pixel: by decreasing peak pixel cost (measured at N = 8, 1024 spp: ordering by
-     * the tile's SUM left a rank in four with a long pixel started late - ranks 611-718 ms; by peak 612-631) */
-    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return peak[x] > peak[y]; });
-    const uint32_t top = top_max < (uint32_t)idx.size() ? top_max : (uint32_t)idx.size();
-    jobs.clear();
-    jobs.reserve((size_t)n * frames);
-    /* by decreasing cost, the frames of a tile together */
-    for (uint32_t r = 0; r < top; r++)
-        for (uint32_t f = 0; f < frames; f++) jobs.push_back(idx[r] | (f << RT_JOB_FRAME_SHIFT));
-    /* everything else frame by frame, in the launch's tile order */
-    std::vector<char> taken(n, 0);
-    for (uint32_t r = 0; r < top; r++) taken[idx[r]] = 1;
-    for (uint32_t f = 0; f < frames; f++)
-        for (uint32_t t : order) if (!taken[t]) jobs.push_back(t | (f << RT_JOB_FRAME_SHIFT));
-}
-
 namespace {
 
-uint32_t gcd_u32(uint32_t x, uint32_t y) { while (y) { uint32_t t = x % y; x = y; y = t; } return x; }
-
-/* a stride near n / golden ratio, made coprime to n */
-uint32_t coprime_stride(uint32_t n)
-{
-    if (n <= 2u) return 1u;
-    uint32_t st = (uint32_t)(n * 0.6180339887) | 1u;
-    while (gcd_u32(st, n) != 1u) st += 2u;
-    return st % n ? st % n : 1u;
-}
-
-/* The view's measured costs are on the device (cost_state 1): bring them to the host on `stream` (one
- * synchronisation), and, when the view uses a tile order, move the `heavy_top` most expensive tiles to its front. */
 /* the render kernels of every pipelined frame have finished (host wait); with_folds: so have the blends that read their planes
  * and the view's tile list */
 rt_status drain_pipeline(rt_ctx *ctx, bool with_folds)
@@ -657,49 +594,48 @@ rt_status drain_pipeline(rt_ctx *ctx, bool with_folds)
     return RT_OK;
 }
 
+/* `v` into `buf` (grown to fit) on `stream`; the host waits for the copy, as `v` is often a local */
+rt_status upload(rt_ctx *ctx, DevBuf<uint32_t> &buf, const std::vector<uint32_t> &v, hipStream_t stream, const char *what)
+{
+    RT_HIP(ctx, buf.grow(v.size()), what);
+    RT_HIP(ctx, hipMemcpyAsync(buf.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, stream), what);
+    RT_HIP(ctx, hipStreamSynchronize(stream), what);
+    return RT_OK;
+}
+
+/* The view's measured costs are on the device: bring them to the host on `stream` (one synchronisation).  Then, when the
+ * view uses a tile order, move the most expensive tiles to its front (rt_sched::refined_order). */
 rt_status read_costs_and_refine(rt_ctx *ctx, hipStream_t stream)
 {
-    const uint32_t n = (uint32_t)ctx->tiles_host.size();
-    if (ctx->cost_state == 1) {
+    View &v = ctx->view;
+    const uint32_t n = (uint32_t)v.tiles.size();
+    if (v.costs == Costs::on_device) {
         /* on the launch stream: the launch that collected the costs ran on it (or this stream has been ordered
          * behind it), and a blocking copy on the null stream would not wait for a non-blocking stream's kernel */
         std::vector<uint32_t> cost(n), peak(n);
-        RT_HIP(ctx, hipMemcpyAsync(cost.data(), ctx->d_tile_cost, (size_t)n * 4, hipMemcpyDeviceToHost, stream), "reading tile costs");
-        RT_HIP(ctx, hipMemcpyAsync(peak.data(), ctx->d_tile_peak, (size_t)n * 4, hipMemcpyDeviceToHost, stream), "reading tile costs");
+        RT_HIP(ctx, hipMemcpyAsync(cost.data(), v.d_cost.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream), "reading tile costs");
+        RT_HIP(ctx, hipMemcpyAsync(peak.data(), v.d_peak.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream), "reading tile costs");
         RT_HIP(ctx, hipStreamSynchronize(stream), "reading tile costs");
-        ctx->cost_host.swap(cost);
-        ctx->peak_host.swap(peak);
+        v.cost.swap(cost);
+        v.peak.swap(peak);
     }
-    if (ctx->use_order && ctx->heavy_top > 0) {
-        const std::vector<uint32_t> &cost = ctx->cost_host, &peak = ctx->peak_host;
-        std::vector<uint32_t> idx;
-        idx.reserve(n);
-        for (uint32_t t : ctx->order_host) if (cost[t] & 1u) idx.push_back(t);          /* tiles with a ray in a mesh */
-        const std::vector<uint32_t> &key = ctx->top_by_peak ? peak : cost;
-        std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return key[x] > key[y]; });
-        const uint32_t top = (uint32_t)ctx->heavy_top < (uint32_t)idx.size() ? (uint32_t)ctx->heavy_top : (uint32_t)idx.size();
-        std::vector<char> taken(n, 0);
-        std::vector<uint32_t> merged;
-        merged.reserve(n);
-        const uint32_t st = ctx->tile_scatter ? coprime_stride(top) : 1u;
-        for (uint32_t i = 0; i < top; i++) { const uint32_t t = idx[(size_t)(((uint64_t)i * st) % top)]; merged.push_back(t); taken[t] = 1; }
-        for (uint32_t t : ctx->order_host) if (!taken[t]) merged.push_back(t);
+    if (v.use_order) {
         /* nothing may still be indexing the old order: the stream was synchronised above, or (caller-supplied costs)
          * the order has not been used by a launch yet */
-        RT_HIP(ctx, hipMemcpyAsync(ctx->d_tile_order, merged.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream), "uploading tile order");
-        RT_HIP(ctx, hipStreamSynchronize(stream), "uploading tile order");     /* `merged` is a local */
-        ctx->order_host.swap(merged);
-        ctx->order_num_heavy = (int)top;
+        std::vector<uint32_t> order;
+        const uint32_t top = rt_sched::refined_order(v.order, v.cost, order);
+        rt_status st = upload(ctx, v.d_order, order, stream, "uploading tile order");
+        if (st != RT_OK) return st;
+        v.order.swap(order);
+        v.num_heavy = (int)top;
     }
-    ctx->cost_state = 2;
-    ctx->job_frames = 0;                    /* any uploaded schedule is for another view */
+    v.costs = Costs::on_host;
+    v.job_frames = 0;                    /* any uploaded schedule is for another view */
     return RT_OK;
 }
 
 }  // namespace
 
-/* one launch rendering n_frames consecutive progressive frames (n_frames == 1: a plain frame with an
- * optional separate previous frame; > 1: d_out is updated in place) */
 /* (c + prev * n) / (n + 1) over the pixels a launch owns, frame by frame (src/raytracer.cu:109-112): `planes` holds n_frames planes of
  * per-pixel means in the launch's output layout.  Compact layouts, and a full frame rendered whole: one pass over the buffer; a
  * full-layout frame of which the launch owns some bands / tiles: only those are folded */
@@ -723,40 +659,24 @@ static rt_status fold_planes(rt_ctx *ctx, const float *planes, size_t plane_floa
     return RT_OK;
 }
 
-/* slot != NULL: a pipelined frame (rt_frame_submit) - the launch runs on the slot's stream with the slot's ticket counter, its
- * pixels' means go to the slot's plane and nothing is folded here; d_prev, d_out and hip_stream are not used. */
-static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
-                               const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
-                               const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot = nullptr)
+/* ---- one launch, step by step (render_frames below) ----------------------------------------------------------------------- */
+
+static rt_status check_launch(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const rt_tile_spec *t, bool have_out)
 {
-    if (!ctx || !scene || !cam || !rs || (!d_out && !slot)) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    if (!ctx || !scene || !cam || !rs || !have_out) return set_err(ctx, RT_ERR_INVALID, "null argument");
     if (scene->ctx != ctx) return set_err(ctx, RT_ERR_INVALID, "scene belongs to another context");
     if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768 || (int64_t)cam->width * cam->height > (1 << 28))
         return set_err(ctx, RT_ERR_INVALID, "bad image size (at most 32768 pixels on a side and 2^28 in all)");
     if (rs->rays_per_pixel < 0 || rs->reflection_limit < 0) return set_err(ctx, RT_ERR_INVALID, "bad render settings");
-    rt_tile_spec full;
-    std::memset(&full, 0, sizeof full);
-    full.band_rows = 8; full.band_stride = 1;
-    const rt_tile_spec *t = tiles ? tiles : &full;
-    const bool listed = t->tile_list != nullptr;
-    const int tiles_x = (cam->width + 7) / 8, tiles_y = (cam->height + 7) / 8;
-    if (listed) {
-        if (t->num_tiles < 0 || t->num_tiles > tiles_x * tiles_y) return set_err(ctx, RT_ERR_INVALID, "bad tile spec (num_tiles)");
-    } else {
-        if (t->tile_cost || t->tile_peak) return set_err(ctx, RT_ERR_INVALID, "bad tile spec (tile_cost / tile_peak need a tile_list)");
-        if (t->band_rows <= 0 || (t->band_rows & 7) || t->band_stride <= 0 || t->band_first < 0 || t->band_first >= t->band_stride)
-            return set_err(ctx, RT_ERR_INVALID, "bad tile spec (band_rows must be a positive multiple of 8, 0 <= band_first < band_stride)");
-    }
-    hipStream_t stream = slot ? slot->stream : (hipStream_t)hip_stream;
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    /* one launch in flight per context: the scratch is shared (see rt_ctx) ... */
-    if (ctx->launched && (slot || ctx->last_stream != stream)) RT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_stop, 0), "ordering the launch behind the previous one");
-    /* ... except pipelined frames, which bring their own (FrameSlot) and only read the view's: they overlap each other, and an
-     * ordinary launch is queued behind all of them */
-    if (!slot)
-        for (FrameSlot &fs : ctx->pipe.slots)
-            if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
+    if (!t->tile_list && (t->tile_cost || t->tile_peak)) return set_err(ctx, RT_ERR_INVALID, "bad tile spec (tile_cost / tile_peak need a tile_list)");
+    if (const char *bad = rt_sched::tile_spec_error(*t, (cam->width + 7) / 8, (cam->height + 7) / 8)) return set_err(ctx, RT_ERR_INVALID, bad);
+    return RT_OK;
+}
 
+static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
+                                  int32_t n_frames, int32_t frame_num, const rt_tile_spec *t, const float *d_prev, float *d_out, uint32_t *tile_counter)
+{
+    const bool listed = t->tile_list != nullptr;
     rt_kernel_args a;
     std::memset(&a, 0, sizeof a);
     std::memcpy(a.cam + 0, cam->cam_pos, 12);
@@ -776,11 +696,9 @@ static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_came
     a.band_first = listed ? 0 : t->band_first;
     a.band_stride = listed ? 1 : t->band_stride;
     a.compact = t->compact ? 1 : 0;
-    a.tiles_x = tiles_x;
-    const int owned_rows = listed ? 0 : rt_tile_owned_rows(t, cam->height);
-    a.num_tiles = listed ? t->num_tiles : (owned_rows / 8) * a.tiles_x;
-    const uint32_t n = a.num_tiles > 0 ? (uint32_t)a.num_tiles : 0u;
-    a.tile_stride = ctx->tile_scatter ? coprime_stride(n ? n : 1u) : 1u;
+    a.tiles_x = (cam->width + 7) / 8;
+    a.num_tiles = listed ? t->num_tiles : (rt_tile_owned_rows(t, cam->height) / 8) * a.tiles_x;
+    a.tile_stride = rt_sched::coprime_stride((uint32_t)a.num_tiles);
 
     a.objects = scene->d_objects;
     a.num_objects = (int32_t)scene->flat.objects.size();
@@ -805,266 +723,283 @@ static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_came
     a.tex_data = scene->d_tex;
     a.prev = d_prev;
     a.out = d_out;
-    a.tile_counter = slot ? slot->counter : ctx->tile_counter;
+    a.tile_counter = tile_counter;
     a.stats = (unsigned long long *)(a.tile_counter + 16);   /* 48 x u64 after the counter; used by -DRT_STATS builds only */
+    return a;
+}
 
+static void push_camera(std::vector<uint32_t> &key, const rt_camera *cam)
+{
+    for (const float *v : {cam->cam_pos, cam->tl_pixel_pos, cam->delta_u, cam->delta_v})
+        for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &v[i], 4); key.push_back(u); }
+}
 
-    /* one plane of the launch's output layout (floats) */
-    const size_t plane_floats = a.compact ? (listed ? (size_t)n * 192 : (size_t)owned_rows * (size_t)cam->width * 3)
-                                          : (size_t)cam->height * (size_t)cam->width * 3;
-
-    /* ---- the view: which tiles, in which order, at what cost ---------------------------------------- */
-    bool collecting = false;
-    if (n > 0) {
-        std::vector<uint32_t> key;
-        key.push_back(scene->uid); key.push_back((uint32_t)ctx->tile_scatter);
-        for (int i = 0; i < 12; i++) { uint32_t u; std::memcpy(&u, &a.cam[i], 4); key.push_back(u); }
-        key.push_back((uint32_t)a.width); key.push_back((uint32_t)a.height);
-        key.push_back((uint32_t)a.reflection_limit);      /* (a launch at bounce limit 0 or 1 says nothing about one at 8) */
-        if (listed) {
-            uint64_t h = fnv1a(t->tile_list, (size_t)n * 4);
-            if (t->tile_cost) h = fnv1a(t->tile_cost, (size_t)n * 4, h);
-            if (t->tile_cost && t->tile_peak) h = fnv1a(t->tile_peak, (size_t)n * 4, h);
-            key.push_back(0xffffffffu); key.push_back(n); key.push_back((uint32_t)h); key.push_back((uint32_t)(h >> 32)); key.push_back(t->tile_cost ? 1u : 0u);
-        } else {
-            key.push_back((uint32_t)a.band_rows); key.push_back((uint32_t)a.band_first); key.push_back((uint32_t)a.band_stride);
-        }
-        /* a pixel's cost counter is 26 bits wide (rt_device_scene.h RT_COST_*): launches that could overflow it (65,536 or
-         * more bounces per pixel) do not collect costs and run on the schedule the view already has */
-        const bool cost_fits = (long long)rs->rays_per_pixel * (long long)(rs->reflection_limit > 0 ? rs->reflection_limit : 1) < 65536ll;
-        /* figures from a launch with far fewer samples (a 1-spp preview, a profiler's warm-up launch) are provisional
-         * like a pilot's: this launch runs on them and measures again */
-        const bool new_view = key != ctx->order_key;
-        const bool provisional = !new_view && ctx->cost_state == 2 && ctx->cost_spp > 0 && (long long)ctx->cost_spp * 8 <= (long long)rs->rays_per_pixel &&
-                                 !(listed && t->tile_cost) && cost_fits;
-        if (slot) {
-            /* Pipelined frames overlap as long as they only READ the view (tile order, tile list).  A launch that writes it - a
-             * new view, a pilot, a launch that measures tile costs, the one that sorts by them - first waits (on the host)
-             * for the frames in flight: once or twice per view. */
-            const bool will_pilot = ctx->pilot && ctx->use_order && rs->rays_per_pixel >= ctx->pilot_min_spp && rs->reflection_limit > 0;
-            const bool list_changed = listed && (ctx->pipe.list_host.size() != (size_t)n || std::memcmp(ctx->pipe.list_host.data(), t->tile_list, (size_t)n * 4) != 0);
-            if (list_changed)
-                for (int j = 0; j < ctx->pipe.pending; j++)
-                    if (ctx->pipe.slots[ctx->pipe.order[j]].listed)
-                        return set_err(ctx, RT_ERR_BUSY, "frames of another tile list are waiting to be collected (rt_frame_collect; d_frame == NULL discards one)");
-            if (new_view || list_changed || (ctx->cost_state == 0 && (cost_fits || will_pilot)) || (ctx->cost_state == 1 && ctx->use_order) || provisional) {
-                rt_status st = drain_pipeline(ctx, new_view || list_changed);
-                if (st != RT_OK) return st;
-            }
-            if (listed && (list_changed || !ctx->pipe.d_list)) {
-                rt_status st = grow_u32(ctx, &ctx->pipe.d_list, &ctx->pipe.list_cap, n, "allocating the pipeline's tile list");
-                if (st != RT_OK) return st;
-                ctx->pipe.list_host.clear();
-                RT_HIP(ctx, hipMemcpy(ctx->pipe.d_list, t->tile_list, (size_t)n * 4, hipMemcpyHostToDevice), "uploading the pipeline's tile list");
-                ctx->pipe.list_host.assign(t->tile_list, t->tile_list + n);
-            }
-        }
-        if (new_view) {
-            /* a new view.  local tile -> tile of the image */
-            std::vector<uint32_t> th(n);
-            if (listed) {
-                std::vector<char> seen((size_t)tiles_x * tiles_y, 0);
-                for (uint32_t i = 0; i < n; i++) {
-                    const uint32_t g = t->tile_list[i];
-                    if (g >= (uint32_t)(tiles_x * tiles_y) || seen[g]) return set_err(ctx, RT_ERR_INVALID, "bad tile spec (a tile index outside the image, or listed twice)");
-                    seen[g] = 1;
-                    th[i] = g;
-                }
-            } else {
-                const int tiles_per_band = a.tiles_x * (a.band_rows >> 3);
-                for (uint32_t i = 0; i < n; i++) {
-                    const int band_local = (int)i / tiles_per_band, in_band = (int)i % tiles_per_band;
-                    const int band = a.band_first + band_local * a.band_stride;
-                    th[i] = (uint32_t)((band * (a.band_rows >> 3) + in_band / a.tiles_x) * a.tiles_x + in_band % a.tiles_x);
-                }
-            }
-            ctx->order_key.clear();              /* (until everything below has succeeded) */
-            ctx->tiles_host.swap(th);
-            ctx->cost_state = 0;
-            ctx->cost_host.clear();
-            ctx->peak_host.clear();
-            ctx->order_num_heavy = 0;
-            ctx->job_frames = 0;
-            rt_status st;
-            if ((st = grow_u32(ctx, &ctx->d_tile_cost, &ctx->tile_cost_cap, n, "allocating tile costs")) != RT_OK) return st;
-            if ((st = grow_u32(ctx, &ctx->d_tile_peak, &ctx->tile_peak_cap, n, "allocating tile costs")) != RT_OK) return st;
-            ctx->use_order = ctx->heavy_first && scene->flat.num_meshes > 0 && n > 1;
-            if (ctx->use_order) {
-                /* longest-job-first, first guess: tiles whose centre ray enters a mesh root box are handed out
-                 * first.  Host float math, a heuristic only: any order renders the same image. */
-                std::vector<uint32_t> heavy, light;
-                for (uint32_t i = 0; i < n; i++) {
-                    const int ty = (int)(ctx->tiles_host[i] / (uint32_t)a.tiles_x), tx = (int)(ctx->tiles_host[i] % (uint32_t)a.tiles_x);
-                    const float px = tx * 8 + 4.0f, py = ty * 8 + 4.0f;
-                    float d[3], o[3];
-                    for (int k = 0; k < 3; k++) { o[k] = a.cam[k]; d[k] = a.cam[3 + k] + a.cam[6 + k] * px + a.cam[9 + k] * py - o[k]; }
-                    bool hit = false;
-                    for (size_t m = 0; m < scene->flat.objects.size() && !hit; m++) {
-                        const rt_object &ob = scene->flat.objects[m];
-                        if (ob.type != RT_OBJ_MESH) continue;
-                        float tmin = 0.0f, tmax = 3.0e38f;
-                        for (int k = 0; k < 3; k++) {
-                            /* grow the box by a margin: the tile is 8 pixels wide and paths leave it */
-                            const float ext = 0.15f * (ob.v[3 + k] - ob.v[k]) + 1e-3f;
-                            const float inv = 1.0f / d[k];
-                            float t1 = (ob.v[k] - ext - o[k]) * inv, t2 = (ob.v[3 + k] + ext - o[k]) * inv;
-                            if (t1 > t2) { float s = t1; t1 = t2; t2 = s; }
-                            if (t1 > tmin) tmin = t1;
-                            if (t2 < tmax) tmax = t2;
-                        }
-                        hit = tmin <= tmax;
-                    }
-                    (hit ? heavy : light).push_back(i);
-                }
-                std::vector<uint32_t> order;
-                order.reserve(n);
-                for (const std::vector<uint32_t> *cls : {&heavy, &light}) {
-                    const uint32_t m = (uint32_t)cls->size();
-                    const uint32_t st2 = ctx->tile_scatter ? coprime_stride(m) : 1u;
-                    for (uint32_t i = 0; i < m; i++) order.push_back((*cls)[(size_t)(((uint64_t)i * st2) % m)]);
-                }
-                if ((st = grow_u32(ctx, &ctx->d_tile_order, &ctx->tile_order_cap, n, "allocating tile order")) != RT_OK) return st;
-                RT_HIP(ctx, hipMemcpyAsync(ctx->d_tile_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream), "uploading tile order");
-                RT_HIP(ctx, hipStreamSynchronize(stream), "uploading tile order");     /* `order` is a local */
-                ctx->order_host.swap(order);
-            }
-            if (listed && t->tile_cost) {
-                /* the caller knows what the tiles cost (an earlier launch of the view, possibly on other GPUs) */
-                ctx->cost_host.assign(t->tile_cost, t->tile_cost + n);
-                if (t->tile_peak) ctx->peak_host.assign(t->tile_peak, t->tile_peak + n);
-                else ctx->peak_host = ctx->cost_host;
-                if ((st = read_costs_and_refine(ctx, stream)) != RT_OK) return st;
-            }
-            ctx->order_key = key;
-        }
-        if (listed && slot) {
-            a.tile_list = ctx->pipe.d_list;
-        } else if (listed) {
-            rt_status st = device_tile_list(ctx, t->tile_list, (int)n, stream, &a.tile_list);
-            if (st != RT_OK) return st;
-        }
-        /* The first launch of a view adds up, per tile, the work of its pixels; the second reads the sums back (one
-         * synchronisation) and moves the `heavy_top` most expensive tiles to the front of the order, most expensive
-         * first within rounds of one ticket per wave.  In a multi-frame launch those tiles go first for ALL frames
-         * (see px_fetch): with the true costs that is worth 10 % at three frames per launch (with the guess, nothing). */
-        if (ctx->cost_state == 0) {
-            /* Pilot: a view's first launch would run on the guessed order (measured: 315 instead of 228 ms per frame for
-             * the monkey's first five frames).  One sample per pixel of the launch's first frame, rendered into a scratch
-             * plane, measures the tiles well enough to schedule by (~1/spp of a frame + one synchronisation); the launch
-             * itself then measures them properly for the launches after it.  Nothing of the pilot reaches the image. */
-            if (ctx->pilot && ctx->use_order && rs->rays_per_pixel >= ctx->pilot_min_spp && rs->reflection_limit > 0) {
-                rt_status st = grow(ctx, &ctx->d_partial, &ctx->partial_cap, plane_floats * (size_t)(in_place ? n_frames : 1), "allocating the pilot's scratch plane");
-                if (st != RT_OK) return st;
-                rt_kernel_args ap = a;
-                ap.rays_per_pixel = 1;
-                ap.num_frames = 1;
-                ap.partial = ctx->d_partial;
-                ap.partial_plane = (int64_t)(plane_floats / 3);
-                ap.prev = nullptr;
-                ap.tile_order = ctx->d_tile_order;
-                ap.tile_cost = ctx->d_tile_cost;
-                ap.tile_peak = ctx->d_tile_peak;
-                RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_cost, 0, (size_t)n * 4, stream), "clearing tile costs");
-                RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_peak, 0, (size_t)n * 4, stream), "clearing tile costs");
-                RT_HIP(ctx, hipMemsetAsync(ap.tile_counter, 0, 512, stream), "clearing tile counter");
-                RT_HIP(ctx, rt_launch_render(&ap, scene->flat.has_mesh ? 1 : 0, scene->scene_in_lds, scene->threads, launch_blocks(ctx, scene, (int)n), scene->lds_bytes, stream),
-                       "launching the pilot");
-                ctx->cost_state = 1; ctx->cost_spp = 1;
-                if ((st = read_costs_and_refine(ctx, stream)) != RT_OK) return st;      /* -> 2: a provisional schedule */
-            }
-            if (cost_fits) {
-                RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_cost, 0, (size_t)n * 4, stream), "clearing tile costs");
-                RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_peak, 0, (size_t)n * 4, stream), "clearing tile costs");
-                a.tile_cost = ctx->d_tile_cost;
-                a.tile_peak = ctx->d_tile_peak;
-                collecting = true;
-            }
-        } else {
-            if (ctx->cost_state == 1 && ctx->use_order) {
-                rt_status st = read_costs_and_refine(ctx, stream);
-                if (st != RT_OK) return st;
-            }
-            if (provisional && ctx->cost_state == 2) {
-                RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_cost, 0, (size_t)n * 4, stream), "clearing tile costs");
-                RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_peak, 0, (size_t)n * 4, stream), "clearing tile costs");
-                a.tile_cost = ctx->d_tile_cost;
-                a.tile_peak = ctx->d_tile_peak;
-                collecting = true;
-            }
-        }
-        if (ctx->use_order) {
-            a.num_heavy_tiles = (ctx->cost_state == 2 && n_frames > 1) ? ctx->order_num_heavy : 0;
-            a.tile_order = ctx->d_tile_order;
-            /* Multi-frame launch of a view whose tile costs are known: the host lays out the whole schedule.
-             * A job is one tile of one frame; a pixel's samples are one sequential random stream, so a job
-             * cannot be split and the launch is at least as long as its longest job - which therefore has to
-             * start at once, for EVERY frame (frames only meet in the blend behind the kernel).  Longest
-             * processing time first: jobs in order of decreasing measured tile cost, all frames of a tile
-             * together; tiles that cost nothing follow frame by frame.  Consecutive tickets are also similar
-             * in cost, so the lanes a wave refills as its cheap pixels finish collect pixels of one kind.  Any
-             * schedule renders the same image.  (Measured, 20 frames of the monkey configuration: +6 % on one
-             * GPU and +25 % on the share one of 8 GPUs renders, against "the 1,024 most expensive tiles of frame
-             * 0, of frame 1, ... first".) */
-            if (ctx->lpt && ctx->cost_state == 2 && n_frames > 1 && n <= (RT_JOB_TILE_MASK + 1u) && ctx->cost_host.size() == n && ctx->peak_host.size() == n) {
-                if (ctx->job_frames != n_frames) {
-                    std::vector<uint32_t> jobs;
-                    build_job_order(ctx->order_host, ctx->cost_host, ctx->lpt_by_peak ? ctx->peak_host : ctx->cost_host, (uint32_t)ctx->lpt_top, (uint32_t)n_frames, jobs);
-                    rt_status st = grow_u32(ctx, &ctx->d_job_order, &ctx->job_cap, jobs.size(), "allocating the launch schedule");
-                    if (st != RT_OK) return st;
-                    RT_HIP(ctx, hipMemcpyAsync(ctx->d_job_order, jobs.data(), jobs.size() * 4, hipMemcpyHostToDevice, stream), "uploading the launch schedule");
-                    RT_HIP(ctx, hipStreamSynchronize(stream), "uploading the launch schedule");     /* `jobs` is a local */
-                    ctx->job_frames = n_frames;
-                }
-                a.job_order = ctx->d_job_order;
-            }
-        }
+static std::vector<uint32_t> view_key(const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const rt_tile_spec *t, uint32_t n)
+{
+    std::vector<uint32_t> key;
+    key.push_back(scene->uid);
+    push_camera(key, cam);
+    key.push_back((uint32_t)cam->width); key.push_back((uint32_t)cam->height);
+    key.push_back((uint32_t)rs->reflection_limit);      /* (a launch at bounce limit 0 or 1 says nothing about one at 8) */
+    if (t->tile_list) {
+        uint64_t h = fnv1a(t->tile_list, (size_t)n * 4);
+        if (t->tile_cost) h = fnv1a(t->tile_cost, (size_t)n * 4, h);
+        if (t->tile_cost && t->tile_peak) h = fnv1a(t->tile_peak, (size_t)n * 4, h);
+        key.push_back(0xffffffffu); key.push_back(n); key.push_back((uint32_t)h); key.push_back((uint32_t)(h >> 32)); key.push_back(t->tile_cost ? 1u : 0u);
+    } else {
+        key.push_back((uint32_t)t->band_rows); key.push_back((uint32_t)t->band_first); key.push_back((uint32_t)t->band_stride);
     }
-    if (slot) {
-        if (slot->plane_cap < plane_floats && slot->folded) RT_HIP(ctx, hipEventSynchronize(slot->ev_free), "waiting for a frame's blend");   /* (the plane is about to be replaced) */
-        rt_status st = grow(ctx, &slot->plane, &slot->plane_cap, plane_floats, "allocating a pipelined frame's plane");
+    return key;
+}
+
+/* Pilot: a view's first launch would run on the guessed order (measured: 315 instead of 228 ms per frame for the monkey's first
+ * five frames).  One sample per pixel of the launch's first frame, rendered into a scratch plane, measures the tiles well
+ * enough to schedule by (~1/spp of a frame + one synchronisation); the launch itself then measures them properly for the
+ * launches after it.  Nothing of the pilot reaches the image. */
+static bool wants_pilot(const View &v, const rt_render_settings *rs)
+{
+    return v.use_order && rs->rays_per_pixel >= rt_sched::PILOT_MIN_SPP && rs->reflection_limit > 0;
+}
+
+/* the launch `a` adds up what its tiles cost */
+static rt_status collect_costs(rt_ctx *ctx, rt_kernel_args &a, hipStream_t stream)
+{
+    View &v = ctx->view;
+    RT_HIP(ctx, hipMemsetAsync(v.d_cost.p, 0, (size_t)a.num_tiles * 4, stream), "clearing tile costs");
+    RT_HIP(ctx, hipMemsetAsync(v.d_peak.p, 0, (size_t)a.num_tiles * 4, stream), "clearing tile costs");
+    a.tile_cost = v.d_cost.p;
+    a.tile_peak = v.d_peak.p;
+    return RT_OK;
+}
+
+/* Pipelined frames overlap as long as they only READ the view (tile order, tile list).  A launch that writes it - a new view, a
+ * pilot, a launch that measures tile costs, the one that sorts by them - first waits (on the host) for the frames in flight:
+ * once or twice per view.  A listed view's tile list is the pipeline's own copy. */
+static rt_status pipeline_view(rt_ctx *ctx, const rt_render_settings *rs, const rt_tile_spec *t, uint32_t n, bool new_view, bool cost_fits, bool provisional)
+{
+    Pipeline &pl = ctx->pipe;
+    const View &v = ctx->view;
+    const bool listed = t->tile_list != nullptr;
+    const bool list_changed = listed && (pl.list_host.size() != (size_t)n || std::memcmp(pl.list_host.data(), t->tile_list, (size_t)n * 4) != 0);
+    if (list_changed)
+        for (int j = 0; j < pl.pending; j++)
+            if (pl.slots[pl.order[j]].listed)
+                return set_err(ctx, RT_ERR_BUSY, "frames of another tile list are waiting to be collected (rt_frame_collect; d_frame == NULL discards one)");
+    if (new_view || list_changed || (v.costs == Costs::none && (cost_fits || wants_pilot(v, rs))) || (v.costs == Costs::on_device && v.use_order) || provisional) {
+        rt_status st = drain_pipeline(ctx, new_view || list_changed);
         if (st != RT_OK) return st;
-        a.partial = slot->plane;
-        a.partial_plane = (int64_t)(plane_floats / 3);
+    }
+    if (listed && (list_changed || !pl.d_list.p)) {
+        RT_HIP(ctx, pl.d_list.grow(n), "allocating the pipeline's tile list");
+        pl.list_host.clear();
+        RT_HIP(ctx, hipMemcpy(pl.d_list.p, t->tile_list, (size_t)n * 4, hipMemcpyHostToDevice), "uploading the pipeline's tile list");
+        pl.list_host.assign(t->tile_list, t->tile_list + n);
+    }
+    return RT_OK;
+}
+
+/* a new view: its tiles, the first guess of their order, and the costs the caller may know (an earlier launch of the view,
+ * possibly on other GPUs) */
+static rt_status new_view(rt_ctx *ctx, const rt_scene *scene, const rt_tile_spec *t, const rt_kernel_args &a, const std::vector<uint32_t> &key, hipStream_t stream)
+{
+    View &v = ctx->view;
+    std::vector<uint32_t> tiles;
+    if (!rt_sched::view_tiles(*t, a.width, a.height, tiles)) return set_err(ctx, RT_ERR_INVALID, "bad tile spec (a tile index outside the image, or listed twice)");
+    const uint32_t n = (uint32_t)tiles.size();
+    v.key.clear();                       /* (until everything below has succeeded) */
+    v.tiles.swap(tiles);
+    v.costs = Costs::none;
+    v.cost.clear();
+    v.peak.clear();
+    v.num_heavy = 0;
+    v.job_frames = 0;
+    RT_HIP(ctx, v.d_cost.grow(n), "allocating tile costs");
+    RT_HIP(ctx, v.d_peak.grow(n), "allocating tile costs");
+    v.use_order = scene->flat.num_meshes > 0 && n > 1;
+    rt_status st;
+    if (v.use_order) {
+        std::vector<uint32_t> order = rt_sched::guessed_order(v.tiles, a.tiles_x, a.cam, scene->flat.objects);
+        if ((st = upload(ctx, v.d_order, order, stream, "uploading tile order")) != RT_OK) return st;
+        v.order.swap(order);
+    }
+    if (t->tile_list && t->tile_cost) {
+        v.cost.assign(t->tile_cost, t->tile_cost + n);
+        if (t->tile_peak) v.peak.assign(t->tile_peak, t->tile_peak + n);
+        else v.peak = v.cost;
+        if ((st = read_costs_and_refine(ctx, stream)) != RT_OK) return st;
+    }
+    v.key = key;
+    return RT_OK;
+}
+
+static rt_status run_pilot(rt_ctx *ctx, const rt_scene *scene, const rt_kernel_args &a, size_t plane_floats, size_t n_planes, hipStream_t stream)
+{
+    View &v = ctx->view;
+    RT_HIP(ctx, ctx->d_partial.grow(plane_floats * n_planes), "allocating the pilot's scratch plane");
+    rt_kernel_args ap = a;
+    ap.rays_per_pixel = 1;
+    ap.num_frames = 1;
+    ap.partial = ctx->d_partial.p;
+    ap.partial_plane = (int64_t)(plane_floats / 3);
+    ap.prev = nullptr;
+    ap.tile_order = v.d_order.p;
+    rt_status st = collect_costs(ctx, ap, stream);
+    if (st != RT_OK) return st;
+    RT_HIP(ctx, hipMemsetAsync(ap.tile_counter, 0, 512, stream), "clearing tile counter");
+    RT_HIP(ctx, rt_launch_render(&ap, scene->flat.has_mesh ? 1 : 0, scene->scene_in_lds, scene->threads, launch_blocks(ctx, scene, ap.num_tiles), scene->lds_bytes, stream),
+           "launching the pilot");
+    v.costs = Costs::on_device;
+    v.cost_spp = 1;
+    return read_costs_and_refine(ctx, stream);      /* -> on_host: a provisional schedule */
+}
+
+/* Multi-frame launch of a view whose tile costs are known: the host lays out the whole schedule.  A job is one tile of one
+ * frame; a pixel's samples are one sequential random stream, so a job cannot be split and the launch is at least as long as
+ * its longest job - which therefore has to start at once, for EVERY frame (frames only meet in the blend behind the kernel).
+ * Longest processing time first (rt_sched::build_job_order).  Consecutive tickets are also similar in cost, so the lanes a
+ * wave refills as its cheap pixels finish collect pixels of one kind.  (Measured, 20 frames of the monkey configuration: +6 %
+ * on one GPU and +25 % on the share one of 8 GPUs renders, against "the 1,024 most expensive tiles of frame 0, of frame 1,
+ * ... first".) */
+static rt_status tile_schedule(rt_ctx *ctx, rt_kernel_args &a, hipStream_t stream)
+{
+    View &v = ctx->view;
+    const uint32_t n = (uint32_t)a.num_tiles;
+    const bool known = v.costs == Costs::on_host && a.num_frames > 1;
+    a.num_heavy_tiles = known ? v.num_heavy : 0;
+    a.tile_order = v.d_order.p;
+    if (!known || n > RT_JOB_TILE_MASK + 1u || v.cost.size() != n || v.peak.size() != n) return RT_OK;
+    if (v.job_frames != a.num_frames) {
+        std::vector<uint32_t> jobs;
+        rt_sched::build_job_order(v.order, v.cost, v.peak, (uint32_t)a.num_frames, jobs);
+        rt_status st = upload(ctx, v.d_jobs, jobs, stream, "uploading the launch schedule");
+        if (st != RT_OK) return st;
+        v.job_frames = a.num_frames;
+    }
+    a.job_order = v.d_jobs.p;
+    return RT_OK;
+}
+
+/* The view of a launch with tiles: which ones, in which order, at what cost.  The first launch of a view adds up, per tile,
+ * the work of its pixels (*collecting); the next reads the sums back (one synchronisation) and moves the most expensive
+ * tiles to the front of the order.  In a multi-frame launch those tiles go first for ALL frames (see px_fetch): with the
+ * true costs that is worth 10 % at three frames per launch (with the guess, nothing). */
+static rt_status prepare_view(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const rt_tile_spec *t,
+                              rt_kernel_args &a, size_t plane_floats, bool in_place, FrameSlot *slot, hipStream_t stream, bool *collecting)
+{
+    View &v = ctx->view;
+    const uint32_t n = (uint32_t)a.num_tiles;
+    const std::vector<uint32_t> key = view_key(scene, cam, rs, t, n);
+    /* a pixel's cost counter is 26 bits wide (rt_device_scene.h RT_COST_*): launches that could overflow it (65,536 or
+     * more bounces per pixel) do not collect costs and run on the schedule the view already has */
+    const bool cost_fits = (long long)rs->rays_per_pixel * (long long)(rs->reflection_limit > 0 ? rs->reflection_limit : 1) < 65536ll;
+    /* figures from a launch with far fewer samples (a 1-spp preview, a profiler's warm-up launch) are provisional
+     * like a pilot's: this launch runs on them and measures again */
+    const bool is_new = key != v.key;
+    const bool provisional = !is_new && v.costs == Costs::on_host && v.cost_spp > 0 && (long long)v.cost_spp * 8 <= (long long)rs->rays_per_pixel &&
+                             !(t->tile_list && t->tile_cost) && cost_fits;
+    rt_status st;
+    if (slot && (st = pipeline_view(ctx, rs, t, n, is_new, cost_fits, provisional)) != RT_OK) return st;
+    if (is_new && (st = new_view(ctx, scene, t, a, key, stream)) != RT_OK) return st;
+    if (t->tile_list) {
+        if (slot) a.tile_list = ctx->pipe.d_list.p;
+        else if ((st = device_tile_list(ctx, t->tile_list, (int)n, stream, &a.tile_list)) != RT_OK) return st;
+    }
+    if (v.costs == Costs::none) {
+        if (wants_pilot(v, rs) && (st = run_pilot(ctx, scene, a, plane_floats, in_place ? (size_t)a.num_frames : 1, stream)) != RT_OK) return st;
+        *collecting = cost_fits;
+    } else {
+        if (v.costs == Costs::on_device && v.use_order && (st = read_costs_and_refine(ctx, stream)) != RT_OK) return st;
+        *collecting = provisional;
+    }
+    if (*collecting && (st = collect_costs(ctx, a, stream)) != RT_OK) return st;
+    return v.use_order ? tile_schedule(ctx, a, stream) : RT_OK;
+}
+
+/* where the launch's per-frame means go: a pipelined frame's plane, the planes of a multi-frame launch, or nowhere (a plain
+ * one-frame launch writes d_out itself) */
+static rt_status bind_output(rt_ctx *ctx, rt_kernel_args &a, size_t plane_floats, bool listed, bool in_place, FrameSlot *slot)
+{
+    if (slot) {
+        if (slot->plane.cap < plane_floats && slot->folded) RT_HIP(ctx, hipEventSynchronize(slot->ev_free), "waiting for a frame's blend");   /* (the plane is about to be replaced) */
+        RT_HIP(ctx, slot->plane.grow(plane_floats), "allocating a pipelined frame's plane");
+        a.partial = slot->plane.p;
         slot->plane_floats = plane_floats; slot->compact = a.compact; slot->listed = listed ? 1 : 0;
         slot->band_rows = a.band_rows; slot->band_first = a.band_first; slot->band_stride = a.band_stride;
-        slot->width = cam->width; slot->height = cam->height; slot->tiles_x = tiles_x; slot->n_tiles = a.num_tiles;
+        slot->width = a.width; slot->height = a.height; slot->tiles_x = a.tiles_x; slot->n_tiles = a.num_tiles;
     } else if (in_place) {
-        const size_t need = plane_floats * (size_t)n_frames;
-        rt_status st = grow(ctx, &ctx->d_partial, &ctx->partial_cap, need, "allocating the per-frame planes of a multi-frame launch");
-        if (st != RT_OK) return st;
-        a.partial = ctx->d_partial;
-        a.partial_plane = (int64_t)(plane_floats / 3);
+        RT_HIP(ctx, ctx->d_partial.grow(plane_floats * (size_t)a.num_frames), "allocating the per-frame planes of a multi-frame launch");
+        a.partial = ctx->d_partial.p;
+    } else {
+        return RT_OK;
     }
+    a.partial_plane = (int64_t)(plane_floats / 3);
+    return RT_OK;
+}
+
+static rt_status launch(rt_ctx *ctx, const rt_scene *scene, const rt_kernel_args &a, bool pipelined, hipStream_t stream)
+{
+    int blocks = launch_blocks(ctx, scene, a.num_tiles);
+    /* A pipelined frame gets its share of the CUs, not all of them: a frame alone on the GPU is as long as its longest
+     * pixel and leaves most CUs idle (or held by a workgroup with one busy wave) for half of that time; on 1 / depth of
+     * the CUs the same frame is bound by its work instead, and `depth` of them fill the GPU (measured, monkey 1080p
+     * 1024 spp, 4 in flight: 286 ms per frame with full-size launches, 242 with quarter-size ones).
+     * Only where a workgroup has its CU to itself (a mesh that fills the LDS): smaller workgroups of several launches share
+     * CUs anyway, and full-size launches are then the faster ones (three-sphere 61.7 against 65.1 ms, cube 112.8 against 118.0). */
+    if (pipelined && scene->blocks_per_cu == 1) blocks = (blocks + ctx->pipe.depth - 1) / ctx->pipe.depth;
+    RT_HIP(ctx, hipMemsetAsync(a.tile_counter, 0, 512, stream), "clearing tile counter");
+    RT_HIP(ctx, rt_launch_render(&a, scene->flat.has_mesh ? 1 : 0, scene->scene_in_lds, scene->threads, blocks, scene->lds_bytes, stream), "launching render kernel");
+    return RT_OK;
+}
+
+/* One launch rendering n_frames consecutive progressive frames (n_frames == 1: a plain frame with an optional separate previous
+ * frame; > 1, or in_place: d_out is updated in place through one plane of per-pixel means per frame).
+ * slot != NULL: a pipelined frame (rt_frame_submit) - the launch runs on the slot's stream with the slot's ticket counter, its
+ * pixels' means go to the slot's plane and nothing is folded here; d_prev, d_out and hip_stream are not used. */
+static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
+                               const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
+                               const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot = nullptr)
+{
+    rt_tile_spec full;
+    std::memset(&full, 0, sizeof full);
+    full.band_rows = 8; full.band_stride = 1;
+    const rt_tile_spec *t = tiles ? tiles : &full;
+    const bool listed = t->tile_list != nullptr;
+    rt_status st = check_launch(ctx, scene, cam, rs, t, d_out || slot);
+    if (st != RT_OK) return st;
+    hipStream_t stream = slot ? slot->stream : (hipStream_t)hip_stream;
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    /* one launch in flight per context: the scratch is shared (see rt_ctx) ... */
+    if (ctx->launched && (slot || ctx->last_stream != stream)) RT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_stop, 0), "ordering the launch behind the previous one");
+    /* ... except pipelined frames, which bring their own (FrameSlot) and only read the view's: they overlap each other, and an
+     * ordinary launch is queued behind all of them */
+    if (!slot)
+        for (FrameSlot &fs : ctx->pipe.slots)
+            if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
+
+    rt_kernel_args a = kernel_args(ctx, scene, cam, rs, times_ms, n_frames, frame_num, t, d_prev, d_out, slot ? slot->counter : ctx->tile_counter);
+    /* one plane of the launch's output layout (floats) */
+    const size_t plane_floats = !a.compact ? (size_t)a.height * (size_t)a.width * 3
+                                           : listed ? (size_t)a.num_tiles * 192 : (size_t)(a.num_tiles / a.tiles_x) * 8 * (size_t)a.width * 3;
+    bool collecting = false;
+    if (a.num_tiles > 0 && (st = prepare_view(ctx, scene, cam, rs, t, a, plane_floats, in_place, slot, stream, &collecting)) != RT_OK) return st;
+    if ((st = bind_output(ctx, a, plane_floats, listed, in_place, slot)) != RT_OK) return st;
     if (!slot) {
         RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");
         ctx->have_timing = false;
     }
     if (a.num_tiles > 0) {
-        int blocks = launch_blocks(ctx, scene, a.num_tiles);
-        if (slot) {
-            /* A pipelined frame gets its share of the CUs, not all of them: a frame alone on the GPU is as long as its longest
-             * pixel and leaves most CUs idle (or held by a workgroup with one busy wave) for half of that time; on 1 / depth of
-             * the CUs the same frame is bound by its work instead, and `depth` of them fill the GPU (measured, monkey 1080p
-             * 1024 spp, 4 in flight: 286 ms per frame with full-size launches, 242 with quarter-size ones).
-             * Only where a workgroup has its CU to itself (a mesh that fills the LDS): smaller workgroups of several launches share
-             * CUs anyway, and full-size launches are then the faster ones (three-sphere 61.7 against 65.1 ms, cube 112.8 against 118.0). */
-            const int d = ctx->pipe.depth;
-            if (ctx->pipe_share == 1 || (ctx->pipe_share == 2 && scene->blocks_per_cu == 1)) blocks = (blocks + d - 1) / d;
-        }
-        RT_HIP(ctx, hipMemsetAsync(a.tile_counter, 0, 512, stream), "clearing tile counter");
-        RT_HIP(ctx, rt_launch_render(&a, scene->flat.has_mesh ? 1 : 0, scene->scene_in_lds, scene->threads, blocks, scene->lds_bytes, stream), "launching render kernel");
-        if (collecting) { ctx->cost_state = 1; ctx->cost_spp = rs->rays_per_pixel; }   /* only now: a failed launch leaves no costs to sort on */
+        if ((st = launch(ctx, scene, a, slot != nullptr, stream)) != RT_OK) return st;
+        if (collecting) { ctx->view.costs = Costs::on_device; ctx->view.cost_spp = rs->rays_per_pixel; }   /* only now: a failed launch leaves no costs to sort on */
     }
     if (slot) {
         RT_HIP(ctx, hipEventRecord(slot->ev_done, stream), "recording a pipelined frame's end");
         slot->used = true;
         return RT_OK;
     }
-    if (in_place && a.num_tiles > 0) {
-        rt_status st = fold_planes(ctx, ctx->d_partial, plane_floats, n_frames, frame_num, d_out, a.compact, listed, a.tile_list, (int)n, tiles_x,
-                                   a.band_rows, a.band_first, a.band_stride, cam->width, cam->height, stream);
-        if (st != RT_OK) return st;
-    }
+    if (in_place && a.num_tiles > 0 &&
+        (st = fold_planes(ctx, ctx->d_partial.p, plane_floats, n_frames, frame_num, d_out, a.compact, listed, a.tile_list, a.num_tiles, a.tiles_x,
+                          a.band_rows, a.band_first, a.band_stride, a.width, a.height, stream)) != RT_OK)
+        return st;
     RT_HIP(ctx, hipEventRecord(ctx->ev_stop, stream), "recording stop event");
     ctx->have_timing = true;
     ctx->launched = true;
@@ -1159,7 +1094,7 @@ extern "C" rt_status rt_frame_collect(rt_ctx *ctx, int32_t frame_num, float *d_f
         RT_HIP(ctx, hipStreamWaitEvent(fs.stream, fs.ev_call, 0), "ordering the blend behind the collector's stream");
         if (pl.last_fold >= 0 && pl.last_fold != pl.order[0])
             RT_HIP(ctx, hipStreamWaitEvent(fs.stream, pl.slots[pl.last_fold].ev_free, 0), "ordering the blend behind the previous frame's");
-        rt_status st = fold_planes(ctx, fs.plane, fs.plane_floats, 1, frame_num, d_frame, fs.compact, fs.listed != 0, pl.d_list, fs.n_tiles, fs.tiles_x,
+        rt_status st = fold_planes(ctx, fs.plane.p, fs.plane_floats, 1, frame_num, d_frame, fs.compact, fs.listed != 0, pl.d_list.p, fs.n_tiles, fs.tiles_x,
                                    fs.band_rows, fs.band_first, fs.band_stride, fs.width, fs.height, fs.stream);
         if (st != RT_OK) return st;
         RT_HIP(ctx, hipEventRecord(fs.ev_free, fs.stream), "recording a pipelined frame's blend");
@@ -1201,10 +1136,10 @@ extern "C" rt_status rt_frame_collect_host(rt_ctx *ctx, int32_t *frame_num, floa
     if (st != RT_OK) return st;
     /* everything on the frame's own stream, behind its render kernel; the host waits for that stream only - the younger frames
      * keep running (a hipDeviceSynchronize, as in rt_render, would wait for them too) */
-    if (*frame_num > 0) RT_HIP(ctx, hipMemcpyAsync(ctx->d_out, previous_render, bytes, hipMemcpyHostToDevice, fs.stream), "copying previous frame");
-    st = rt_frame_collect(ctx, *frame_num, ctx->d_out, fs.stream);
+    if (*frame_num > 0) RT_HIP(ctx, hipMemcpyAsync(ctx->d_out.p, previous_render, bytes, hipMemcpyHostToDevice, fs.stream), "copying previous frame");
+    st = rt_frame_collect(ctx, *frame_num, ctx->d_out.p, fs.stream);
     if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpyAsync(previous_render, ctx->d_out, bytes, hipMemcpyDeviceToHost, fs.stream), "copying frame to host");
+    RT_HIP(ctx, hipMemcpyAsync(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost, fs.stream), "copying frame to host");
     RT_HIP(ctx, hipStreamSynchronize(fs.stream), "render kernel");
     *frame_num += 1;                                   /* src/dispatch.cu:159 */
     return RT_OK;
@@ -1225,17 +1160,18 @@ extern "C" rt_status rt_tile_costs(rt_ctx *ctx, uint32_t *tile_ids, uint32_t *co
     if (!ctx || !count || capacity < 0 || (capacity > 0 && (!tile_ids || !costs))) return set_err(ctx, RT_ERR_INVALID, "null argument");
     *count = 0;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    if (ctx->order_key.empty() || ctx->cost_state == 0) return set_err(ctx, RT_ERR_INVALID, "no launch of the current view has collected tile costs");
-    if (ctx->cost_state == 1) {
+    const View &v = ctx->view;
+    if (v.key.empty() || v.costs == Costs::none) return set_err(ctx, RT_ERR_INVALID, "no launch of the current view has collected tile costs");
+    if (v.costs == Costs::on_device) {
         rt_status st = drain_pipeline(ctx, false);       /* (a pipelined frame may be the launch that measures, or be reading the order) */
         if (st != RT_OK) return st;
         st = read_costs_and_refine(ctx, ctx->last_stream);
         if (st != RT_OK) return st;
     }
-    const size_t n = ctx->tiles_host.size();
-    if (ctx->cost_host.size() != n || ctx->peak_host.size() != n) return set_err(ctx, RT_ERR_INVALID, "no launch of the current view has collected tile costs");
+    const size_t n = v.tiles.size();
+    if (v.cost.size() != n || v.peak.size() != n) return set_err(ctx, RT_ERR_INVALID, "no launch of the current view has collected tile costs");
     const size_t m = n < (size_t)capacity ? n : (size_t)capacity;
-    for (size_t i = 0; i < m; i++) { tile_ids[i] = ctx->tiles_host[i]; costs[i] = ctx->cost_host[i]; if (peaks) peaks[i] = ctx->peak_host[i]; }
+    for (size_t i = 0; i < m; i++) { tile_ids[i] = v.tiles[i]; costs[i] = v.cost[i]; if (peaks) peaks[i] = v.peak[i]; }
     *count = (int32_t)n;
     return RT_OK;
 }
@@ -1245,8 +1181,7 @@ extern "C" rt_status rt_tiles_copy_device(rt_ctx *ctx, float *d_compact, float *
 {
     if (!ctx || !d_compact || !d_frame || width <= 0 || height <= 0 || num_tiles < 0 || (num_tiles > 0 && !tile_list)) return set_err(ctx, RT_ERR_INVALID, "bad argument");
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
-    for (int32_t i = 0; i < num_tiles; i++)
-        if (tile_list[i] >= (uint32_t)(tiles_x * tiles_y)) return set_err(ctx, RT_ERR_INVALID, "a tile index outside the image");
+    if (!rt_sched::tiles_in_image(tile_list, num_tiles, tiles_x, tiles_y)) return set_err(ctx, RT_ERR_INVALID, "a tile index outside the image");
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     const uint32_t *d_list = nullptr;
     rt_status st = device_tile_list(ctx, tile_list, num_tiles, (hipStream_t)hip_stream, &d_list);
@@ -1313,16 +1248,15 @@ extern "C" rt_status rt_last_kernel_ms(rt_ctx *ctx, float *ms)
 
 namespace {
 
+/* d_prev and d_out of exactly `bytes` */
 rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes)
 {
-    if (bytes == ctx->frame_bytes) return RT_OK;
-    if (ctx->d_prev) (void)hipFree(ctx->d_prev);
-    if (ctx->d_out) (void)hipFree(ctx->d_out);
-    ctx->d_prev = ctx->d_out = nullptr;
-    ctx->frame_bytes = 0;
-    RT_HIP(ctx, hipMalloc((void **)&ctx->d_prev, bytes), "allocating previous-frame buffer");
-    RT_HIP(ctx, hipMalloc((void **)&ctx->d_out, bytes), "allocating frame buffer");
-    ctx->frame_bytes = bytes;
+    const size_t floats = bytes / 4;
+    if (ctx->d_prev.cap == floats && ctx->d_out.cap == floats) return RT_OK;
+    ctx->d_prev.release();
+    ctx->d_out.release();
+    RT_HIP(ctx, ctx->d_prev.grow(floats), "allocating previous-frame buffer");
+    RT_HIP(ctx, ctx->d_out.grow(floats), "allocating frame buffer");
     return RT_OK;
 }
 
@@ -1337,11 +1271,11 @@ extern "C" rt_status rt_render(rt_ctx *ctx, const rt_scene *scene, const rt_came
     const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
     rt_status st = ensure_frame_buffers(ctx, bytes);
     if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpy(ctx->d_prev, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
-    st = rt_render_device(ctx, scene, cam, rs, time_ms, *frame_num, nullptr, ctx->d_prev, ctx->d_out, nullptr);
+    RT_HIP(ctx, hipMemcpy(ctx->d_prev.p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
+    st = rt_render_device(ctx, scene, cam, rs, time_ms, *frame_num, nullptr, ctx->d_prev.p, ctx->d_out.p, nullptr);
     if (st != RT_OK) return st;
     RT_HIP(ctx, hipDeviceSynchronize(), "render kernel");
-    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out, bytes, hipMemcpyDeviceToHost), "copying frame to host");
+    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
     *frame_num += 1;                                   /* src/dispatch.cu:159 */
     RT_HIP(ctx, hipPeekAtLastError(), "final check after render");   /* src/dispatch.cu:161-162 */
     return RT_OK;
@@ -1358,16 +1292,16 @@ extern "C" rt_status rt_render_frames(rt_ctx *ctx, const rt_scene *scene, const 
     const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
     rt_status st = ensure_frame_buffers(ctx, bytes);
     if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpy(ctx->d_out, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
+    RT_HIP(ctx, hipMemcpy(ctx->d_out.p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
     const int32_t cap = batch_cap(ctx, bytes / 4);
     for (int32_t done = 0; done < n_frames;) {
         const int32_t k = n_frames - done < cap ? n_frames - done : cap;
-        st = rt_render_device_batch(ctx, scene, cam, rs, times_ms + done, k, *frame_num + done, nullptr, ctx->d_out, nullptr);
+        st = rt_render_device_batch(ctx, scene, cam, rs, times_ms + done, k, *frame_num + done, nullptr, ctx->d_out.p, nullptr);
         if (st != RT_OK) return st;
         done += k;
     }
     RT_HIP(ctx, hipDeviceSynchronize(), "render kernel");
-    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out, bytes, hipMemcpyDeviceToHost), "copying frame to host");
+    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
     *frame_num += n_frames;
     RT_HIP(ctx, hipPeekAtLastError(), "final check after render");
     return RT_OK;
@@ -1458,12 +1392,11 @@ rt_status stage_for(rt_ctx *root, rt_ctx *src, size_t need, hipStream_t s0, Stag
     { std::lock_guard<std::mutex> lock(g_ctx_mutex); sgp = &root->stages[src]; }
     Stage &sg = *sgp;
     if (!sg.ev_free) RT_HIP(root, hipEventCreateWithFlags(&sg.ev_free, hipEventDisableTiming), "creating the staging event");
-    if (sg.cap < need || !sg.d) {
+    if (sg.d.cap < need || !sg.d.p) {
         /* nothing may still be reading or writing the old area */
         if (sg.used) RT_HIP(root, hipEventSynchronize(sg.ev_free), "waiting for the staging area");
         if (src->multi_stream) { (void)hipSetDevice(src->device); (void)hipStreamSynchronize(src->multi_stream); (void)hipSetDevice(root->device); }
-        rt_status st = grow(root, &sg.d, &sg.cap, need, "allocating the gather staging area");
-        if (st != RT_OK) return st;
+        RT_HIP(root, sg.d.grow(need), "allocating the gather staging area");
         sg.used = false;
     }
     if (sg.used) RT_HIP(root, hipStreamWaitEvent(s0, sg.ev_free, 0), "ordering behind the previous de-interleave");
@@ -1512,15 +1445,11 @@ extern "C" rt_status rt_gather(rt_ctx *root, float *d_frame, int32_t width, int3
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     BandLayout L;
     size_t floats;
+    if (const char *bad = rt_sched::tile_spec_error(*src_tiles, tiles_x, tiles_y)) return set_err(root, RT_ERR_INVALID, bad);
     if (listed) {
-        if (src_tiles->num_tiles < 0 || src_tiles->num_tiles > tiles_x * tiles_y) return set_err(root, RT_ERR_INVALID, "bad tile spec");
-        for (int32_t i = 0; i < src_tiles->num_tiles; i++)
-            if (src_tiles->tile_list[i] >= (uint32_t)(tiles_x * tiles_y)) return set_err(root, RT_ERR_INVALID, "a tile index outside the image");
+        if (!rt_sched::tiles_in_image(src_tiles->tile_list, src_tiles->num_tiles, tiles_x, tiles_y)) return set_err(root, RT_ERR_INVALID, "a tile index outside the image");
         floats = (size_t)src_tiles->num_tiles * 192;
     } else {
-        if (src_tiles->band_rows <= 0 || (src_tiles->band_rows & 7) || src_tiles->band_stride <= 0 ||
-            src_tiles->band_first < 0 || src_tiles->band_first >= src_tiles->band_stride)
-            return set_err(root, RT_ERR_INVALID, "bad tile spec");
         L.W = width; L.H = height; L.band_rows = src_tiles->band_rows; L.n = src_tiles->band_stride;
         floats = L.floats_of(src_tiles->band_first);
     }
@@ -1539,11 +1468,11 @@ extern "C" rt_status rt_gather(rt_ctx *root, float *d_frame, int32_t width, int3
         RT_HIP(src, hipSetDevice(src->device), "selecting device");
         if (sg->used) RT_HIP(src, hipStreamWaitEvent(src->multi_stream, sg->ev_free, 0), "ordering the copy behind the previous de-interleave");
         if (src->launched) RT_HIP(src, hipStreamWaitEvent(src->multi_stream, src->ev_stop, 0), "ordering the gather behind the render");
-        RT_HIP(src, copy_between(sg->d, root->device, d_bands, src->device, floats * 4, src->multi_stream), "copying the rank's image to the root GPU");
+        RT_HIP(src, copy_between(sg->d.p, root->device, d_bands, src->device, floats * 4, src->multi_stream), "copying the rank's image to the root GPU");
         RT_HIP(src, hipEventRecord(src->ev_multi, src->multi_stream), "recording the gather event");
         RT_HIP(root, hipSetDevice(root->device), "selecting device");
         RT_HIP(root, hipStreamWaitEvent(s0, src->ev_multi, 0), "ordering the de-interleave behind the copy");
-        from = sg->d;
+        from = sg->d.p;
     } else {
         RT_HIP(root, hipSetDevice(root->device), "selecting device");
         if (src->launched) RT_HIP(root, hipStreamWaitEvent(s0, src->ev_stop, 0), "ordering the gather behind the render");
@@ -1612,10 +1541,7 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
     bool collect_after = false;
     if (listed) {
         std::vector<uint32_t> key;
-        for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &cam->cam_pos[i], 4); key.push_back(u); }
-        for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &cam->tl_pixel_pos[i], 4); key.push_back(u); }
-        for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &cam->delta_u[i], 4); key.push_back(u); }
-        for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &cam->delta_v[i], 4); key.push_back(u); }
+        push_camera(key, cam);
         key.push_back((uint32_t)W); key.push_back((uint32_t)H); key.push_back((uint32_t)n_ranks);
         /* the bounce limit, and whether this is a preview-quality launch (< 8 samples) or a real one: ownership measured on
          * the one says little about the other */
@@ -1625,10 +1551,7 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
         if (key != ms.key || ms.lists.size() != (size_t)n_ranks) {
             /* a new view: interleaved ownership; this call's first launches measure what the tiles cost */
             if ((st = rt_partition_tiles(nullptr, tiles_x, tiles_y, n_ranks, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
-            ms.lists.assign((size_t)n_ranks, std::vector<uint32_t>());
-            ms.costs.assign((size_t)n_ranks, std::vector<uint32_t>());
-            ms.peaks.assign((size_t)n_ranks, std::vector<uint32_t>());
-            for (size_t g = 0; g < owner.size(); g++) ms.lists[(size_t)owner[g]].push_back((uint32_t)g);
+            rt_sched::deal_tiles(owner, n_ranks, nullptr, nullptr, ms.lists, ms.costs, ms.peaks);
             ms.key = key;
             ms.stage = 0;
         } else if (ms.stage == 1) {
@@ -1651,12 +1574,7 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
             RT_HIP(root, hipSetDevice(root->device), "selecting device");
             if (have_all) {
                 if ((st = rt_partition_tiles(cost.data(), tiles_x, tiles_y, n_ranks, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
-                ms.lists.assign((size_t)n_ranks, std::vector<uint32_t>());
-                ms.costs.assign((size_t)n_ranks, std::vector<uint32_t>());
-                ms.peaks.assign((size_t)n_ranks, std::vector<uint32_t>());
-                for (size_t g = 0; g < owner.size(); g++) {
-                    ms.lists[(size_t)owner[g]].push_back((uint32_t)g); ms.costs[(size_t)owner[g]].push_back(cost[g]); ms.peaks[(size_t)owner[g]].push_back(peak[g]);
-                }
+                rt_sched::deal_tiles(owner, n_ranks, cost.data(), peak.data(), ms.lists, ms.costs, ms.peaks);
                 ms.stage = 2;
             } else {
                 ms.stage = 0;            /* (a rank's view was replaced in between: measure again) */
@@ -1690,10 +1608,10 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
     std::vector<Stage *> stage((size_t)n_ranks, nullptr);
     for (int i = 0; i < n_ranks; i++) {
         rt_ctx *c = ranks[i].ctx;
-        if (c->bands_cap < plan[(size_t)i].floats || !c->d_bands) {
+        if (c->d_bands.cap < plan[(size_t)i].floats || !c->d_bands.p) {
             RT_HIP(c, hipSetDevice(c->device), "selecting device");
             RT_HIP(c, hipStreamSynchronize(c->multi_stream), "waiting for the rank's image buffer");
-            if ((st = grow(c, &c->d_bands, &c->bands_cap, plan[(size_t)i].floats, "allocating the rank's image buffer")) != RT_OK) return set_err(root, st, rt_last_error(c));
+            if (hipError_t e = c->d_bands.grow(plan[(size_t)i].floats)) return set_err(root, hip_fail(c, e, "allocating the rank's image buffer"), c->err);
         }
         if ((st = stage_for(root, c, plan[(size_t)i].floats, s0, &stage[(size_t)i])) != RT_OK) return st;
     }
@@ -1705,8 +1623,8 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
     if (frame_num > 0) {
         for (int i = 0; i < n_ranks; i++) {
             if (plan[(size_t)i].floats == 0) continue;
-            if (listed) RT_HIP(root, rt_launch_tiles_copy(stage[(size_t)i]->d, d_frame, plan[(size_t)i].root_list, plan[(size_t)i].spec.num_tiles, tiles_x, W, H, 0, s0), "interleaving tiles");
-            else RT_HIP(root, copy_bands(L, i, d_frame, stage[(size_t)i]->d, false, s0), "interleaving bands");
+            if (listed) RT_HIP(root, rt_launch_tiles_copy(stage[(size_t)i]->d.p, d_frame, plan[(size_t)i].root_list, plan[(size_t)i].spec.num_tiles, tiles_x, W, H, 0, s0), "interleaving tiles");
+            else RT_HIP(root, copy_bands(L, i, d_frame, stage[(size_t)i]->d.p, false, s0), "interleaving bands");
         }
     }
     /* RT_AMD_MULTI_CAREFUL=1 (diagnosis): the host waits for every stream involved after each phase, so that no ordering between
@@ -1735,7 +1653,7 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
         RT_HIP(c, hipSetDevice(c->device), "selecting device");
         RT_HIP(c, hipStreamWaitEvent(c->multi_stream, root->ev_multi, 0), "ordering the ranks behind the caller's stream");
         if (frame_num > 0)
-            RT_HIP(c, copy_between(c->d_bands, c->device, stage[(size_t)i]->d, root->device, plan[(size_t)i].floats * 4, c->multi_stream), "copying the image so far to its owner");
+            RT_HIP(c, copy_between(c->d_bands.p, c->device, stage[(size_t)i]->d.p, root->device, plan[(size_t)i].floats * 4, c->multi_stream), "copying the image so far to its owner");
     }
     if ((st = careful("careful mode: waiting for the image so far to reach its owners (scatter-out)")) != RT_OK) return st;
     /* ---- every rank renders its tiles (asynchronous launches from this one thread) and sends them back ---- */
@@ -1746,11 +1664,11 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
         const int32_t cap = batch_cap(c, plan[(size_t)i].floats);
         for (int32_t done = 0; done < n_frames;) {
             const int32_t k = std::min<int32_t>(n_frames - done, cap);
-            st = rt_render_device_batch(c, ranks[i].scene, cam, rs, times_ms + done, k, frame_num + done, &plan[(size_t)i].spec, c->d_bands, c->multi_stream);
+            st = rt_render_device_batch(c, ranks[i].scene, cam, rs, times_ms + done, k, frame_num + done, &plan[(size_t)i].spec, c->d_bands.p, c->multi_stream);
             if (st != RT_OK) return set_err(root, st, rt_last_error(c));
             done += k;
         }
-        RT_HIP(c, copy_between(stage[(size_t)i]->d, root->device, c->d_bands, c->device, plan[(size_t)i].floats * 4, c->multi_stream), "copying the rank's image to the root GPU");
+        RT_HIP(c, copy_between(stage[(size_t)i]->d.p, root->device, c->d_bands.p, c->device, plan[(size_t)i].floats * 4, c->multi_stream), "copying the rank's image to the root GPU");
         RT_HIP(c, hipEventRecord(c->ev_multi, c->multi_stream), "recording the gather event");
     }
     if ((st = careful("careful mode: waiting for the ranks' kernels and their copies to the root GPU")) != RT_OK) return st;
@@ -1758,8 +1676,8 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
     for (int i = 0; i < n_ranks; i++) {
         if (plan[(size_t)i].floats == 0) continue;
         RT_HIP(root, hipStreamWaitEvent(s0, ranks[i].ctx->ev_multi, 0), "ordering the de-interleave behind the copies");
-        if (listed) RT_HIP(root, rt_launch_tiles_copy(stage[(size_t)i]->d, d_frame, plan[(size_t)i].root_list, plan[(size_t)i].spec.num_tiles, tiles_x, W, H, 1, s0), "de-interleaving tiles");
-        else RT_HIP(root, copy_bands(L, i, d_frame, stage[(size_t)i]->d, true, s0), "de-interleaving bands");
+        if (listed) RT_HIP(root, rt_launch_tiles_copy(stage[(size_t)i]->d.p, d_frame, plan[(size_t)i].root_list, plan[(size_t)i].spec.num_tiles, tiles_x, W, H, 1, s0), "de-interleaving tiles");
+        else RT_HIP(root, copy_bands(L, i, d_frame, stage[(size_t)i]->d.p, true, s0), "de-interleaving bands");
         RT_HIP(root, hipEventRecord(stage[(size_t)i]->ev_free, s0), "recording the staging event");
         stage[(size_t)i]->used = true;
     }
@@ -1780,15 +1698,15 @@ extern "C" rt_status rt_render_multi(const rt_rank *ranks, int32_t n_ranks, cons
     const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
     rt_status st = ensure_frame_buffers(ctx, bytes);
     if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpy(ctx->d_out, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
-    st = rt_render_multi_device(ranks, n_ranks, cam, rs, times_ms, n_frames, *frame_num, 0, ctx->d_out, nullptr);
+    RT_HIP(ctx, hipMemcpy(ctx->d_out.p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
+    st = rt_render_multi_device(ranks, n_ranks, cam, rs, times_ms, n_frames, *frame_num, 0, ctx->d_out.p, nullptr);
     if (st != RT_OK) return st;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     RT_HIP(ctx, hipStreamSynchronize(nullptr), "render kernels");
     for (int i = 0; i < n_ranks; i++)
         if ((st = rt_ctx_synchronize(ranks[i].ctx)) != RT_OK) return set_err(ctx, st, rt_last_error(ranks[i].ctx));
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out, bytes, hipMemcpyDeviceToHost), "copying frame to host");
+    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
     *frame_num += n_frames;
     RT_HIP(ctx, hipPeekAtLastError(), "final check after render");
     return RT_OK;

@@ -1,0 +1,185 @@
+/*
+ * rt_schedule.h — the host arithmetic of the render schedule: which tiles a launch renders, in which order its waves take
+ * them, and which rank of a multi-GPU call renders which.  Plain functions of vectors and scalars; no HIP.  Any order
+ * renders the same image: the schedule only decides how long a launch takes ("Multi-frame launches and their
+ * schedule").  A tile is 8 x 8 pixels; "local tile" t is the t-th tile of a launch, tiles[t] its index in the image.
+ * Header only: rt_capi.cpp, and the host-only sanitizer build of it, need nothing else to link.
+ */
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "rt_amd.h"
+#include "rt_device_scene.h"
+
+namespace rt_sched {
+
+/* the refined one-frame order moves at most this many measured tiles to its front */
+constexpr uint32_t HEAVY_TOP = 1024;
+/* a new view's first launch is preceded by a one-sample-per-pixel pilot from this many samples per pixel on */
+constexpr int PILOT_MIN_SPP = 32;
+
+/* a stride near n / golden ratio, coprime to n (1 for n <= 2) */
+inline uint32_t coprime_stride(uint32_t n)
+{
+    auto gcd = [](uint32_t x, uint32_t y) { while (y) { uint32_t t = x % y; x = y; y = t; } return x; };
+    if (n <= 2u) return 1u;
+    uint32_t st = (uint32_t)(n * 0.6180339887) | 1u;
+    while (gcd(st, n) != 1u) st += 2u;
+    return st % n ? st % n : 1u;
+}
+
+/* appends cls[(i * st) % m] for i < m, st = coprime_stride(m): the m entries spread out, so that neighbouring tickets
+ * (waves of one workgroup, workgroups of one CU) take tiles far apart */
+inline void append_scattered(const uint32_t *cls, uint32_t m, std::vector<uint32_t> &out)
+{
+    const uint32_t st = coprime_stride(m);
+    for (uint32_t i = 0; i < m; i++) out.push_back(cls[(size_t)(((uint64_t)i * st) % m)]);
+}
+
+/* What is wrong with a tile spec for an image of tiles_x x tiles_y tiles (nullptr: nothing).  Listed tiles are checked
+ * here for their number only: tiles_in_image / view_tiles check the indices. */
+inline const char *tile_spec_error(const rt_tile_spec &t, int tiles_x, int tiles_y)
+{
+    if (t.tile_list) return t.num_tiles < 0 || t.num_tiles > tiles_x * tiles_y ? "bad tile spec (num_tiles)" : nullptr;
+    if (t.band_rows <= 0 || (t.band_rows & 7) || t.band_stride <= 0 || t.band_first < 0 || t.band_first >= t.band_stride)
+        return "bad tile spec (band_rows must be a positive multiple of 8, 0 <= band_first < band_stride)";
+    return nullptr;
+}
+
+inline bool tiles_in_image(const uint32_t *list, int32_t n, int tiles_x, int tiles_y)
+{
+    for (int32_t i = 0; i < n; i++)
+        if (list[i] >= (uint32_t)(tiles_x * tiles_y)) return false;
+    return true;
+}
+
+/* A valid spec's tiles: tiles[t] is local tile t's index in a width x height image.  A list is taken as it is (false if
+ * an index is outside the image or listed twice); bands give rt_tile_owned_rows / 8 rows of tiles, band after band. */
+inline bool view_tiles(const rt_tile_spec &t, int width, int height, std::vector<uint32_t> &tiles)
+{
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    if (t.tile_list) {
+        const uint32_t n = (uint32_t)t.num_tiles;
+        std::vector<char> seen((size_t)tiles_x * tiles_y, 0);
+        tiles.assign(n, 0u);
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t g = t.tile_list[i];
+            if (g >= (uint32_t)(tiles_x * tiles_y) || seen[g]) return false;
+            seen[g] = 1;
+            tiles[i] = g;
+        }
+        return true;
+    }
+    const uint32_t n = (uint32_t)(rt_tile_owned_rows(&t, height) / 8) * (uint32_t)tiles_x;
+    const int tiles_per_band = tiles_x * (t.band_rows >> 3);
+    tiles.assign(n, 0u);
+    for (uint32_t i = 0; i < n; i++) {
+        const int band_local = (int)i / tiles_per_band, in_band = (int)i % tiles_per_band;
+        const int band = t.band_first + band_local * t.band_stride;
+        tiles[i] = (uint32_t)((band * (t.band_rows >> 3) + in_band / tiles_x) * tiles_x + in_band % tiles_x);
+    }
+    return true;
+}
+
+/* The first guess of a view's order (ticket -> local tile), before anything is measured: tiles whose centre ray enters
+ * the root box of a mesh, enlarged by a margin, first, then the others; each class scattered.  cam: rt_kernel_args::cam. */
+inline std::vector<uint32_t> guessed_order(const std::vector<uint32_t> &tiles, int tiles_x, const float cam[12], const std::vector<rt_object> &objects)
+{
+    /* Host float math, a heuristic only */
+    const uint32_t n = (uint32_t)tiles.size();
+    std::vector<uint32_t> heavy, light;
+    for (uint32_t i = 0; i < n; i++) {
+        const int ty = (int)(tiles[i] / (uint32_t)tiles_x), tx = (int)(tiles[i] % (uint32_t)tiles_x);
+        const float px = tx * 8 + 4.0f, py = ty * 8 + 4.0f;
+        float d[3], o[3];
+        for (int k = 0; k < 3; k++) { o[k] = cam[k]; d[k] = cam[3 + k] + cam[6 + k] * px + cam[9 + k] * py - o[k]; }
+        bool hit = false;
+        for (size_t m = 0; m < objects.size() && !hit; m++) {
+            const rt_object &ob = objects[m];
+            if (ob.type != RT_OBJ_MESH) continue;
+            float tmin = 0.0f, tmax = 3.0e38f;
+            for (int k = 0; k < 3; k++) {
+                /* grow the box by a margin: the tile is 8 pixels wide and paths leave it */
+                const float ext = 0.15f * (ob.v[3 + k] - ob.v[k]) + 1e-3f;
+                const float inv = 1.0f / d[k];
+                float t1 = (ob.v[k] - ext - o[k]) * inv, t2 = (ob.v[3 + k] + ext - o[k]) * inv;
+                if (t1 > t2) { float s = t1; t1 = t2; t2 = s; }
+                if (t1 > tmin) tmin = t1;
+                if (t2 < tmax) tmax = t2;
+            }
+            hit = tmin <= tmax;
+        }
+        (hit ? heavy : light).push_back(i);
+    }
+    std::vector<uint32_t> order;
+    order.reserve(n);
+    append_scattered(heavy.data(), (uint32_t)heavy.size(), order);
+    append_scattered(light.data(), (uint32_t)light.size(), order);
+    return order;
+}
+
+/* The order once the tiles are measured: the HEAVY_TOP mesh tiles (bit 0 of cost[t]: a ray of the tile entered a mesh) of
+ * largest cost, most expensive first and scattered, then every other tile in `order`'s order.  Returns how many lead. */
+inline uint32_t refined_order(const std::vector<uint32_t> &order, const std::vector<uint32_t> &cost, std::vector<uint32_t> &out)
+{
+    const uint32_t n = (uint32_t)order.size();
+    std::vector<uint32_t> idx;
+    idx.reserve(n);
+    for (uint32_t t : order) if (cost[t] & 1u) idx.push_back(t);          /* tiles with a ray in a mesh */
+    /* by the tile's summed cost (by its peak pixel instead, same-box A/B, one 1080p frame: monkey 526 against 509 ms, cube 178
+     * against 171, reference scene 0 3,083 against 3,104) */
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return cost[x] > cost[y]; });
+    const uint32_t top = HEAVY_TOP < (uint32_t)idx.size() ? HEAVY_TOP : (uint32_t)idx.size();
+    out.clear();
+    out.reserve(n);
+    append_scattered(idx.data(), top, out);
+    std::vector<char> taken(n, 0);
+    for (uint32_t i = 0; i < top; i++) taken[idx[i]] = 1;
+    for (uint32_t t : order) if (!taken[t]) out.push_back(t);
+    return top;
+}
+
+/* The ticket -> (tile | frame << RT_JOB_FRAME_SHIFT) table of a multi-frame launch, longest job first: the mesh tiles by
+ * decreasing peak pixel cost, the frames of a tile together; the other tiles follow frame by frame in `order`'s order. */
+inline void build_job_order(const std::vector<uint32_t> &order, const std::vector<uint32_t> &cost, const std::vector<uint32_t> &peak,
+                            uint32_t frames, std::vector<uint32_t> &jobs)
+{
+    const uint32_t n = (uint32_t)order.size();
+    std::vector<uint32_t> idx;
+    idx.reserve(n);
+    for (uint32_t t : order) if (cost[t] & 1u) idx.push_back(t);
+    /* a job lasts as long as its longest pixel: by decreasing peak pixel cost (measured at N = 8, 1024 spp: ordering by
+     * the tile's SUM left a rank in four with a long pixel started late - ranks 611-718 ms; by peak 612-631) */
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return peak[x] > peak[y]; });
+    const uint32_t top = (uint32_t)idx.size();
+    jobs.clear();
+    jobs.reserve((size_t)n * frames);
+    /* by decreasing cost, the frames of a tile together */
+    for (uint32_t r = 0; r < top; r++)
+        for (uint32_t f = 0; f < frames; f++) jobs.push_back(idx[r] | (f << RT_JOB_FRAME_SHIFT));
+    /* everything else frame by frame, in the launch's tile order */
+    std::vector<char> taken(n, 0);
+    for (uint32_t r = 0; r < top; r++) taken[idx[r]] = 1;
+    for (uint32_t f = 0; f < frames; f++)
+        for (uint32_t t : order) if (!taken[t]) jobs.push_back(t | (f << RT_JOB_FRAME_SHIFT));
+}
+
+/* rt_partition_tiles' owner table dealt out per rank: its tiles (ascending image indices) and, with cost and peak
+ * (indexed by image tile), their costs and peaks; without them the rank's costs and peaks stay empty */
+inline void deal_tiles(const std::vector<int32_t> &owner, int n_ranks, const uint32_t *cost, const uint32_t *peak, std::vector<std::vector<uint32_t>> &lists,
+                       std::vector<std::vector<uint32_t>> &costs, std::vector<std::vector<uint32_t>> &peaks)
+{
+    lists.assign((size_t)n_ranks, std::vector<uint32_t>());
+    costs.assign((size_t)n_ranks, std::vector<uint32_t>());
+    peaks.assign((size_t)n_ranks, std::vector<uint32_t>());
+    for (size_t g = 0; g < owner.size(); g++) {
+        const size_t r = (size_t)owner[g];
+        lists[r].push_back((uint32_t)g);
+        if (cost) { costs[r].push_back(cost[g]); peaks[r].push_back(peak[g]); }
+    }
+}
+
+}  // namespace rt_sched

@@ -1,17 +1,22 @@
 // The GPU-free entry points of rt_capi.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; test infrastructure):
-// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, and every entry point's refusal of null / bad
-// arguments before it touches HIP.  rt_capi.cpp is compiled as host C++ against the HIP runtime's API header and linked with the
-// runtime library; the kernel launchers (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
+// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule (rt_schedule.h) with
+// its properties asserted, and every entry point's refusal of null / bad arguments before it touches HIP.  rt_capi.cpp is
+// compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the kernel launchers
+// (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <set>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
 
 #include "rt_amd.h"
 #include "rt_device_scene.h"
+#include "rt_schedule.h"
 
 extern "C" hipError_t rt_launch_render(const rt_kernel_args *, int, int, int, int, size_t, hipStream_t) { return hipErrorUnknown; }
 extern "C" int rt_kernel_blocks_per_cu(int, int, int, size_t) { return 1; }
@@ -21,6 +26,202 @@ extern "C" hipError_t rt_launch_tiles_copy(float *, float *, const uint32_t *, i
 extern "C" hipError_t rt_launch_eval(int, const uint32_t *, uint32_t *, int, hipStream_t) { return hipErrorUnknown; }
 extern "C" hipError_t rt_launch_rgba8(const float *, int, uint8_t *, hipStream_t) { return hipErrorUnknown; }
 extern "C" hipError_t rt_launch_exhaustive(unsigned long long *, hipStream_t) { return hipErrorUnknown; }
+
+#define CHECK(cond, what)                                                      \
+    do {                                                                       \
+        if (!(cond)) { std::fprintf(stderr, "schedule: %s\n", what); return false; } \
+    } while (0)
+
+static bool is_permutation_of_iota(const std::vector<uint32_t> &v, uint32_t n)
+{
+    if (v.size() != n) return false;
+    std::vector<char> seen(n, 0);
+    for (uint32_t t : v) {
+        if (t >= n || seen[t]) return false;
+        seen[t] = 1;
+    }
+    return true;
+}
+
+/* the guess's rule on a ray from the origin (doubles): 1 enters the enlarged box, 0 misses it, -1 too close to call */
+static int enters_box(const double d[3], const rt_object &ob)
+{
+    double tmin = 0.0, tmax = 3.0e38;
+    for (int k = 0; k < 3; k++) {
+        const double ext = 0.15 * ((double)ob.v[3 + k] - ob.v[k]) + 1e-3;
+        double t1 = (ob.v[k] - ext) / d[k], t2 = (ob.v[3 + k] + ext) / d[k];
+        if (t1 > t2) std::swap(t1, t2);
+        tmin = std::max(tmin, t1);
+        tmax = std::min(tmax, t2);
+    }
+    if (!std::isfinite(tmin) || !std::isfinite(tmax) || std::fabs(tmin - tmax) <= 1e-3 * std::fabs(tmax)) return -1;
+    return tmin <= tmax ? 1 : 0;
+}
+
+/* one random view through the schedule functions: tile map, guessed and refined order, job order, stride */
+template <class Rng> static bool check_schedule(Rng &rng)
+{
+    auto irand = [&](long long lo, long long hi) { return (long long)std::uniform_int_distribution<long long>(lo, hi)(rng); };
+    const int W = (int)irand(1, 420), H = (int)irand(1, 300);
+    const int tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8, tiles = tiles_x * tiles_y;
+    rt_tile_spec ts;
+    std::memset(&ts, 0, sizeof ts);
+    std::vector<uint32_t> map;
+    std::vector<uint32_t> list;
+    if (irand(0, 1)) {
+        /* bands: every owned band's tiles, row by row; a ragged last band is padded to whole bands */
+        ts.band_rows = 8 * (int)irand(1, 6); ts.band_stride = (int)irand(1, 5); ts.band_first = (int)irand(0, ts.band_stride - 1);
+        CHECK(rt_sched::tile_spec_error(ts, tiles_x, tiles_y) == nullptr, "a valid band spec refused");
+        CHECK(rt_sched::view_tiles(ts, W, H, map), "a band spec has no tile map");
+        CHECK(map.size() == (size_t)(rt_tile_owned_rows(&ts, H) / 8) * tiles_x, "band tile count");
+        const int rows_per_band = ts.band_rows / 8, bands_total = (H + ts.band_rows - 1) / ts.band_rows;
+        std::set<uint32_t> distinct(map.begin(), map.end());
+        CHECK(distinct.size() == map.size(), "a band tile mapped twice");
+        size_t in_image = 0;
+        for (uint32_t g : map) {
+            const int band = (int)(g / tiles_x) / rows_per_band;
+            CHECK(band < bands_total && band % ts.band_stride == ts.band_first, "a band tile outside the spec's bands");
+            in_image += g < (uint32_t)tiles;
+        }
+        size_t want = 0;
+        for (int r = 0; r < tiles_y; r++) want += (r / rows_per_band) % ts.band_stride == ts.band_first ? tiles_x : 0;
+        CHECK(in_image == want, "a band tile of the image missing");
+    } else {
+        std::vector<uint32_t> all((size_t)tiles);
+        for (int i = 0; i < tiles; i++) all[(size_t)i] = (uint32_t)i;
+        std::shuffle(all.begin(), all.end(), rng);
+        list.assign(all.begin(), all.begin() + irand(0, tiles));
+        static const uint32_t none = 0;                      /* (an empty vector's data() may be null, which would read as "no list") */
+        ts.tile_list = list.empty() ? &none : list.data(); ts.num_tiles = (int32_t)list.size();
+        CHECK(rt_sched::tile_spec_error(ts, tiles_x, tiles_y) == nullptr && rt_sched::tiles_in_image(list.data(), ts.num_tiles, tiles_x, tiles_y), "a valid list refused");
+        CHECK(rt_sched::view_tiles(ts, W, H, map) && map == list, "list tile map");
+        if (!list.empty()) {
+            std::vector<uint32_t> bad = list;
+            const size_t i = (size_t)irand(0, (long long)bad.size() - 1);
+            const bool dup = bad.size() > 1 && irand(0, 1);
+            bad[i] = dup ? bad[(i + 1) % bad.size()] : (uint32_t)irand(tiles, tiles + 100);
+            rt_tile_spec tb = ts;
+            tb.tile_list = bad.data();
+            std::vector<uint32_t> m2;
+            CHECK(!rt_sched::view_tiles(tb, W, H, m2), "a tile outside the image or listed twice accepted");
+            CHECK(dup || !rt_sched::tiles_in_image(bad.data(), tb.num_tiles, tiles_x, tiles_y), "a tile outside the image accepted");
+        }
+        ts.num_tiles = tiles + 1;
+        CHECK(rt_sched::tile_spec_error(ts, tiles_x, tiles_y) != nullptr, "more tiles than the image has accepted");
+    }
+    const uint32_t n = (uint32_t)map.size();
+    for (uint32_t m : {n, (uint32_t)irand(0, 5000000)}) {
+        const uint32_t st = rt_sched::coprime_stride(m);
+        uint32_t a = st, b = m;
+        while (b) { const uint32_t t = a % b; a = b; b = t; }
+        CHECK(m <= 2 ? st == 1 : (a == 1 && st < m), "coprime_stride");
+    }
+    if (n == 0) return true;
+
+    /* guessed order: a camera at the origin looking down -z, meshes beyond z = -5 (and a sphere, which never counts) */
+    float cam[12] = {0, 0, 0, -0.5f, 0.5f * H / W, -1, 1.0f / W, 0, 0, 0, -1.0f / W, 0};
+    std::vector<rt_object> objects((size_t)irand(0, 3));
+    for (rt_object &ob : objects) {
+        std::memset(&ob, 0, sizeof ob);
+        ob.type = irand(0, 3) ? RT_OBJ_MESH : RT_OBJ_SPHERE;
+        const float z0 = -5.0f - (float)irand(0, 100) * 0.1f;
+        ob.v[2] = z0 - 1.0f; ob.v[5] = z0;
+        for (int k = 0; k < 2; k++) { ob.v[k] = (float)irand(-40, 40) * 0.1f + 0.0123f; ob.v[3 + k] = ob.v[k] + (float)irand(1, 30) * 0.1f; }
+    }
+    const std::vector<uint32_t> guess = rt_sched::guessed_order(map, tiles_x, cam, objects);
+    CHECK(is_permutation_of_iota(guess, n), "the guessed order is not a permutation");
+    long long last_heavy = -1, first_light = (long long)n;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t g = map[guess[k]];
+        const double px = (g % tiles_x) * 8 + 4.0, py = (g / tiles_x) * 8 + 4.0;
+        const double d[3] = {cam[3] + cam[6] * px + cam[9] * py, cam[4] + cam[7] * px + cam[10] * py, cam[5] + cam[8] * px + cam[11] * py};
+        int cls = 0;
+        for (const rt_object &ob : objects)
+            if (ob.type == RT_OBJ_MESH) {
+                const int e = enters_box(d, ob);
+                if (e != 0) cls = e == 1 && cls != -1 ? 1 : -1;
+                if (cls == 1) break;
+            }
+        if (cls == 1) last_heavy = k;
+        if (cls == 0 && first_light == (long long)n) first_light = k;
+    }
+    CHECK(last_heavy < first_light, "a light tile ahead of a heavy one in the guessed order");
+
+    /* refined order: the top mesh tiles by summed cost lead, the others keep the guess's order */
+    std::vector<uint32_t> cost(n), peak(n);
+    const int kind = (int)irand(0, 2);
+    for (uint32_t t = 0; t < n; t++) {
+        cost[t] = kind == 0 ? (uint32_t)irand(0, 3) : kind == 1 ? (uint32_t)irand(0, 0xffffffffll) : (uint32_t)irand(0, 1) | (uint32_t)irand(0, 50) << 1;
+        peak[t] = (uint32_t)irand(0, kind == 0 ? 3 : 100000);
+    }
+    std::vector<uint32_t> refined;
+    const uint32_t top = rt_sched::refined_order(guess, cost, refined);
+    uint32_t mesh = 0;
+    for (uint32_t t = 0; t < n; t++) mesh += cost[t] & 1u;
+    CHECK(is_permutation_of_iota(refined, n), "the refined order is not a permutation");
+    CHECK(top == std::min(rt_sched::HEAVY_TOP, mesh), "the refined order's number of leading tiles");
+    std::vector<char> lead(n, 0);
+    uint32_t least = 0xffffffffu;
+    for (uint32_t k = 0; k < top; k++) {
+        CHECK(cost[refined[k]] & 1u, "a tile without a mesh among the leading ones");
+        lead[refined[k]] = 1;
+        least = std::min(least, cost[refined[k]]);
+    }
+    std::vector<uint32_t> rest;
+    for (uint32_t t : guess) {
+        if (lead[t]) continue;
+        CHECK(!(cost[t] & 1u) || cost[t] <= least, "a more expensive mesh tile left out of the leading ones");
+        rest.push_back(t);
+    }
+    CHECK(std::equal(rest.begin(), rest.end(), refined.begin() + top), "the other tiles do not keep their order");
+
+    /* job order: each (tile, frame) once; the mesh tiles first, frames together and ascending, by non-increasing peak; the
+     * others frame by frame in the launch's order */
+    const uint32_t frames = (uint32_t)irand(2, RT_MAX_BATCH_FRAMES);
+    std::vector<uint32_t> jobs;
+    rt_sched::build_job_order(refined, cost, peak, frames, jobs);
+    CHECK(jobs.size() == (size_t)n * frames, "job count");
+    std::vector<char> done((size_t)n * frames, 0);
+    for (uint32_t j : jobs) {
+        const uint32_t t = j & RT_JOB_TILE_MASK, f = j >> RT_JOB_FRAME_SHIFT;
+        CHECK(t < n && f < frames && !done[(size_t)t * frames + f], "a job outside the launch or listed twice");
+        done[(size_t)t * frames + f] = 1;
+    }
+    for (uint32_t r = 0; r < mesh; r++)
+        for (uint32_t f = 0; f < frames; f++) {
+            const uint32_t j = jobs[(size_t)r * frames + f], t = j & RT_JOB_TILE_MASK;
+            CHECK((cost[t] & 1u) && (j >> RT_JOB_FRAME_SHIFT) == f && t == (jobs[(size_t)r * frames] & RT_JOB_TILE_MASK), "a leading tile's frames are not together in order");
+            CHECK(r == 0 || peak[t] <= peak[jobs[(size_t)(r - 1) * frames] & RT_JOB_TILE_MASK], "leading tiles not by non-increasing peak");
+        }
+    size_t k = (size_t)mesh * frames;
+    for (uint32_t f = 0; f < frames; f++)
+        for (uint32_t t : refined)
+            if (!(cost[t] & 1u)) {
+                CHECK(jobs[k] == (t | f << RT_JOB_FRAME_SHIFT), "the other tiles do not follow frame by frame");
+                k++;
+            }
+    return true;
+}
+
+/* rt_partition_tiles' owner table dealt out: a partition of the image's tiles, with each tile's cost and peak */
+static bool check_deal(const std::vector<int32_t> &owner, int n_ranks, const std::vector<uint32_t> &cost, const std::vector<uint32_t> &peak)
+{
+    std::vector<std::vector<uint32_t>> lists, costs, peaks;
+    rt_sched::deal_tiles(owner, n_ranks, cost.data(), peak.data(), lists, costs, peaks);
+    CHECK(lists.size() == (size_t)n_ranks && costs.size() == (size_t)n_ranks && peaks.size() == (size_t)n_ranks, "deal: number of ranks");
+    std::vector<int> seen(owner.size(), 0);
+    for (int r = 0; r < n_ranks; r++) {
+        CHECK(costs[(size_t)r].size() == lists[(size_t)r].size() && peaks[(size_t)r].size() == lists[(size_t)r].size(), "deal: costs per tile");
+        for (size_t i = 0; i < lists[(size_t)r].size(); i++) {
+            const uint32_t g = lists[(size_t)r][i];
+            CHECK(g < owner.size() && owner[g] == r && (i == 0 || lists[(size_t)r][i - 1] < g), "deal: a tile in the wrong rank or out of order");
+            CHECK(costs[(size_t)r][i] == cost[g] && peaks[(size_t)r][i] == peak[g], "deal: a tile's cost");
+            seen[g]++;
+        }
+    }
+    for (int c : seen) CHECK(c == 1, "deal: not a partition of the image");
+    return true;
+}
 
 int main(int argc, char **argv)
 {
@@ -42,7 +243,12 @@ int main(int argc, char **argv)
                 load[(size_t)owner[(size_t)i]] += cost[(size_t)i];
             }
             if (owner[(size_t)tiles] != -7) { std::fprintf(stderr, "wrote past the end\n"); return 1; }
+            std::vector<int32_t> own(owner.begin(), owner.end() - 1);
+            std::vector<uint32_t> cs(cost.begin(), cost.end() - 1), pk(cs.size());
+            for (auto &x : pk) x = (uint32_t)irand(0, 1000);
+            if (!check_deal(own, n, cs, pk)) return 1;
         }
+        if (!check_schedule(rng)) return 1;
         rt_tile_spec ts;
         std::memset(&ts, 0, sizeof ts);
         ts.band_rows = (int32_t)irand(-8, 64); ts.band_first = (int32_t)irand(-1, 5); ts.band_stride = (int32_t)irand(-1, 5);
@@ -80,6 +286,6 @@ int main(int argc, char **argv)
     (void)rt_peer_access(nullptr, nullptr);
     (void)rt_scene_commit(nullptr, nullptr, nullptr);
     (void)rt_scene_get_info(nullptr, nullptr);
-    std::printf("capi host fuzz: %d partitions, sanitizers silent\n", cases);
+    std::printf("capi host fuzz: %d partitions and deals, %d schedules, sanitizers silent\n", cases, cases);
     return 0;
 }
