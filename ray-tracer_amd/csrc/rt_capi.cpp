@@ -87,10 +87,13 @@ struct Stage {
     ~Stage() { if (ev_free) (void)hipEventDestroy(ev_free); }
 };
 
+/* cost-balanced multi-GPU calls: a new view's interleaved deal (calls on it measure the tiles), measured, dealt by cost */
+enum class Owners { interleaved, measured, balanced };
+
 /* rt_render_multi[_device] with cost-balanced tile lists: what the root remembers between calls */
 struct MultiState {
     std::vector<uint32_t> key;           /* camera, image size, number of ranks, scene ids */
-    int stage = 0;                       /* 0 nothing; 1 the interleaved lists are in use and a call has collected costs; 2 balanced */
+    Owners owners = Owners::interleaved;
     std::vector<std::vector<uint32_t>> lists, costs, peaks;   /* per rank: its tiles (image indices), their measured costs and peak pixel costs */
 };
 
@@ -127,9 +130,7 @@ struct FrameSlot {
     hipEvent_t ev_free = nullptr;       /* the blend that read the plane has finished (recorded on `stream` too: the blend runs there) */
     hipEvent_t ev_call = nullptr;       /* where the collector's stream stood when it asked for the frame */
     bool used = false, folded = false;  /* ev_done / ev_free have been recorded at least once */
-    /* what rt_frame_collect needs to fold the plane into the caller's frame (the launch's output layout) */
-    size_t plane_floats = 0;
-    int compact = 0, listed = 0, band_rows = 8, band_first = 0, band_stride = 1, width = 0, height = 0, tiles_x = 0, n_tiles = 0;
+    rt_sched::Layout layout;            /* the launch's output layout: how rt_frame_collect folds the plane into the caller's frame */
 };
 
 struct Pipeline {
@@ -534,9 +535,9 @@ extern "C" rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *out)
 extern "C" int32_t rt_tile_owned_rows(const rt_tile_spec *t, int32_t height)
 {
     if (!t || t->band_rows <= 0 || t->band_stride <= 0 || t->band_first < 0 || t->band_first >= t->band_stride) return -1;
-    int32_t bands_total = (height + t->band_rows - 1) / t->band_rows;
-    int32_t owned = bands_total > t->band_first ? (bands_total - t->band_first + t->band_stride - 1) / t->band_stride : 0;
-    return owned * t->band_rows;
+    rt_tile_spec bands = *t;
+    bands.tile_list = nullptr;           /* (the band fields of any spec) */
+    return rt_sched::Layout(bands, 0, height).owned_rows();
 }
 
 /* Longest-processing-time-first ownership (see include/rt_amd.h) */
@@ -594,6 +595,18 @@ rt_status drain_pipeline(rt_ctx *ctx, bool with_folds)
     return RT_OK;
 }
 
+/* d_prev and d_out of exactly `bytes` */
+rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes)
+{
+    const size_t floats = bytes / 4;
+    if (ctx->d_prev.cap == floats && ctx->d_out.cap == floats) return RT_OK;
+    ctx->d_prev.release();
+    ctx->d_out.release();
+    RT_HIP(ctx, ctx->d_prev.grow(floats), "allocating previous-frame buffer");
+    RT_HIP(ctx, ctx->d_out.grow(floats), "allocating frame buffer");
+    return RT_OK;
+}
+
 /* `v` into `buf` (grown to fit) on `stream`; the host waits for the copy, as `v` is often a local */
 rt_status upload(rt_ctx *ctx, DevBuf<uint32_t> &buf, const std::vector<uint32_t> &v, hipStream_t stream, const char *what)
 {
@@ -637,23 +650,21 @@ rt_status read_costs_and_refine(rt_ctx *ctx, hipStream_t stream)
 }  // namespace
 
 /* (c + prev * n) / (n + 1) over the pixels a launch owns, frame by frame (src/raytracer.cu:109-112): `planes` holds n_frames planes of
- * per-pixel means in the launch's output layout.  Compact layouts, and a full frame rendered whole: one pass over the buffer; a
- * full-layout frame of which the launch owns some bands / tiles: only those are folded */
-static rt_status fold_planes(rt_ctx *ctx, const float *planes, size_t plane_floats, int n_frames, int frame_num, float *d_out, int compact, bool listed,
-                             const uint32_t *d_tile_list, int n_tiles, int tiles_x, int band_rows, int band_first, int band_stride, int width, int height,
-                             hipStream_t stream)
+ * per-pixel means in the output layout L.  Compact layouts, and a full frame rendered whole: one pass over the buffer; a
+ * full-layout frame of which the launch owns some bands / tiles: only those are folded (tiles: d_tile_list, the list on the device) */
+static rt_status fold(rt_ctx *ctx, const rt_sched::Layout &L, const float *planes, int n_frames, int frame_num, float *d_out, const uint32_t *d_tile_list,
+                      hipStream_t stream)
 {
-    if (compact || (!listed && band_stride == 1)) {
-        RT_HIP(ctx, rt_launch_blend(planes, (long long)plane_floats, n_frames, frame_num, d_out, (long long)plane_floats, stream), "launching blend kernel");
-    } else if (listed) {
-        RT_HIP(ctx, rt_launch_blend_tiles(planes, (long long)plane_floats, n_frames, frame_num, d_out, d_tile_list, n_tiles, tiles_x, width, height, stream),
+    const long long plane = (long long)L.plane_floats();
+    if (L.compact || L.whole_frame()) {
+        RT_HIP(ctx, rt_launch_blend(planes, plane, n_frames, frame_num, d_out, plane, stream), "launching blend kernel");
+    } else if (L.listed) {
+        RT_HIP(ctx, rt_launch_blend_tiles(planes, plane, n_frames, frame_num, d_out, d_tile_list, L.num_tiles, L.tiles_x, L.width, L.height, stream),
                "launching blend kernel");
     } else {
-        const int bands_total = (height + band_rows - 1) / band_rows;
-        for (int b = band_first; b < bands_total; b += band_stride) {
-            const int row0 = b * band_rows, row1 = row0 + band_rows < height ? row0 + band_rows : height;
-            const long long off = (long long)row0 * width * 3, cnt = (long long)(row1 - row0) * width * 3;
-            RT_HIP(ctx, rt_launch_blend(planes + off, (long long)plane_floats, n_frames, frame_num, d_out + off, cnt, stream), "launching blend kernel");
+        for (int k = 0; k < L.owned_bands(); k++) {
+            const long long off = (long long)L.band(k) * L.band_rows * L.width * 3, cnt = (long long)L.rows_of(L.band(k)) * L.width * 3;
+            RT_HIP(ctx, rt_launch_blend(planes + off, plane, n_frames, frame_num, d_out + off, cnt, stream), "launching blend kernel");
         }
     }
     return RT_OK;
@@ -674,9 +685,8 @@ static rt_status check_launch(rt_ctx *ctx, const rt_scene *scene, const rt_camer
 }
 
 static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
-                                  int32_t n_frames, int32_t frame_num, const rt_tile_spec *t, const float *d_prev, float *d_out, uint32_t *tile_counter)
+                                  int32_t n_frames, int32_t frame_num, const rt_sched::Layout &L, const float *d_prev, float *d_out, uint32_t *tile_counter)
 {
-    const bool listed = t->tile_list != nullptr;
     rt_kernel_args a;
     std::memset(&a, 0, sizeof a);
     std::memcpy(a.cam + 0, cam->cam_pos, 12);
@@ -692,12 +702,12 @@ static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, cons
     for (int i = 0; i < n_frames; i++) a.seeds[i] = (uint32_t)times_ms[i] * 6291469u;       /* src/raytracer.cu:127 */
     a.num_frames = n_frames;
     a.frame_num = frame_num;
-    a.band_rows = listed ? 8 : t->band_rows;
-    a.band_first = listed ? 0 : t->band_first;
-    a.band_stride = listed ? 1 : t->band_stride;
-    a.compact = t->compact ? 1 : 0;
-    a.tiles_x = (cam->width + 7) / 8;
-    a.num_tiles = listed ? t->num_tiles : (rt_tile_owned_rows(t, cam->height) / 8) * a.tiles_x;
+    a.band_rows = L.band_rows;
+    a.band_first = L.band_first;
+    a.band_stride = L.band_stride;
+    a.compact = L.compact ? 1 : 0;
+    a.tiles_x = L.tiles_x;
+    a.num_tiles = L.num_tiles;
     a.tile_stride = rt_sched::coprime_stride((uint32_t)a.num_tiles);
 
     a.objects = scene->d_objects;
@@ -783,7 +793,7 @@ static rt_status pipeline_view(rt_ctx *ctx, const rt_render_settings *rs, const 
     const bool list_changed = listed && (pl.list_host.size() != (size_t)n || std::memcmp(pl.list_host.data(), t->tile_list, (size_t)n * 4) != 0);
     if (list_changed)
         for (int j = 0; j < pl.pending; j++)
-            if (pl.slots[pl.order[j]].listed)
+            if (pl.slots[pl.order[j]].layout.listed)
                 return set_err(ctx, RT_ERR_BUSY, "frames of another tile list are waiting to be collected (rt_frame_collect; d_frame == NULL discards one)");
     if (new_view || list_changed || (v.costs == Costs::none && (cost_fits || wants_pilot(v, rs))) || (v.costs == Costs::on_device && v.use_order) || provisional) {
         rt_status st = drain_pipeline(ctx, new_view || list_changed);
@@ -917,15 +927,14 @@ static rt_status prepare_view(rt_ctx *ctx, const rt_scene *scene, const rt_camer
 
 /* where the launch's per-frame means go: a pipelined frame's plane, the planes of a multi-frame launch, or nowhere (a plain
  * one-frame launch writes d_out itself) */
-static rt_status bind_output(rt_ctx *ctx, rt_kernel_args &a, size_t plane_floats, bool listed, bool in_place, FrameSlot *slot)
+static rt_status bind_output(rt_ctx *ctx, rt_kernel_args &a, const rt_sched::Layout &L, bool in_place, FrameSlot *slot)
 {
+    const size_t plane_floats = L.plane_floats();
     if (slot) {
         if (slot->plane.cap < plane_floats && slot->folded) RT_HIP(ctx, hipEventSynchronize(slot->ev_free), "waiting for a frame's blend");   /* (the plane is about to be replaced) */
         RT_HIP(ctx, slot->plane.grow(plane_floats), "allocating a pipelined frame's plane");
         a.partial = slot->plane.p;
-        slot->plane_floats = plane_floats; slot->compact = a.compact; slot->listed = listed ? 1 : 0;
-        slot->band_rows = a.band_rows; slot->band_first = a.band_first; slot->band_stride = a.band_stride;
-        slot->width = a.width; slot->height = a.height; slot->tiles_x = a.tiles_x; slot->n_tiles = a.num_tiles;
+        slot->layout = L;
     } else if (in_place) {
         RT_HIP(ctx, ctx->d_partial.grow(plane_floats * (size_t)a.num_frames), "allocating the per-frame planes of a multi-frame launch");
         a.partial = ctx->d_partial.p;
@@ -959,11 +968,9 @@ static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_came
                                const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
                                const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot = nullptr)
 {
-    rt_tile_spec full;
-    std::memset(&full, 0, sizeof full);
+    rt_tile_spec full{};
     full.band_rows = 8; full.band_stride = 1;
     const rt_tile_spec *t = tiles ? tiles : &full;
-    const bool listed = t->tile_list != nullptr;
     rt_status st = check_launch(ctx, scene, cam, rs, t, d_out || slot);
     if (st != RT_OK) return st;
     hipStream_t stream = slot ? slot->stream : (hipStream_t)hip_stream;
@@ -976,13 +983,11 @@ static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_came
         for (FrameSlot &fs : ctx->pipe.slots)
             if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
 
-    rt_kernel_args a = kernel_args(ctx, scene, cam, rs, times_ms, n_frames, frame_num, t, d_prev, d_out, slot ? slot->counter : ctx->tile_counter);
-    /* one plane of the launch's output layout (floats) */
-    const size_t plane_floats = !a.compact ? (size_t)a.height * (size_t)a.width * 3
-                                           : listed ? (size_t)a.num_tiles * 192 : (size_t)(a.num_tiles / a.tiles_x) * 8 * (size_t)a.width * 3;
+    const rt_sched::Layout L(*t, cam->width, cam->height);
+    rt_kernel_args a = kernel_args(ctx, scene, cam, rs, times_ms, n_frames, frame_num, L, d_prev, d_out, slot ? slot->counter : ctx->tile_counter);
     bool collecting = false;
-    if (a.num_tiles > 0 && (st = prepare_view(ctx, scene, cam, rs, t, a, plane_floats, in_place, slot, stream, &collecting)) != RT_OK) return st;
-    if ((st = bind_output(ctx, a, plane_floats, listed, in_place, slot)) != RT_OK) return st;
+    if (a.num_tiles > 0 && (st = prepare_view(ctx, scene, cam, rs, t, a, L.plane_floats(), in_place, slot, stream, &collecting)) != RT_OK) return st;
+    if ((st = bind_output(ctx, a, L, in_place, slot)) != RT_OK) return st;
     if (!slot) {
         RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");
         ctx->have_timing = false;
@@ -996,10 +1001,7 @@ static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_came
         slot->used = true;
         return RT_OK;
     }
-    if (in_place && a.num_tiles > 0 &&
-        (st = fold_planes(ctx, ctx->d_partial.p, plane_floats, n_frames, frame_num, d_out, a.compact, listed, a.tile_list, a.num_tiles, a.tiles_x,
-                          a.band_rows, a.band_first, a.band_stride, a.width, a.height, stream)) != RT_OK)
-        return st;
+    if (in_place && a.num_tiles > 0 && (st = fold(ctx, L, ctx->d_partial.p, n_frames, frame_num, d_out, a.tile_list, stream)) != RT_OK) return st;
     RT_HIP(ctx, hipEventRecord(ctx->ev_stop, stream), "recording stop event");
     ctx->have_timing = true;
     ctx->launched = true;
@@ -1085,7 +1087,7 @@ extern "C" rt_status rt_frame_collect(rt_ctx *ctx, int32_t frame_num, float *d_f
     if (frame_num < 0) return set_err(ctx, RT_ERR_INVALID, "bad frame number");
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     FrameSlot &fs = pl.slots[pl.order[0]];
-    if (d_frame && fs.n_tiles > 0) {
+    if (d_frame && fs.layout.num_tiles > 0) {
         /* The blend runs on the frame's own stream, right behind its render kernel, and the caller's stream only waits for it
          * (a kernel queued on the caller's stream may sit behind whatever shares that stream's hardware queue).  Ordered behind
          * what the caller has queued so far (it may still be reading d_frame) and behind the previous frame's blend. */
@@ -1094,8 +1096,7 @@ extern "C" rt_status rt_frame_collect(rt_ctx *ctx, int32_t frame_num, float *d_f
         RT_HIP(ctx, hipStreamWaitEvent(fs.stream, fs.ev_call, 0), "ordering the blend behind the collector's stream");
         if (pl.last_fold >= 0 && pl.last_fold != pl.order[0])
             RT_HIP(ctx, hipStreamWaitEvent(fs.stream, pl.slots[pl.last_fold].ev_free, 0), "ordering the blend behind the previous frame's");
-        rt_status st = fold_planes(ctx, fs.plane.p, fs.plane_floats, 1, frame_num, d_frame, fs.compact, fs.listed != 0, pl.d_list.p, fs.n_tiles, fs.tiles_x,
-                                   fs.band_rows, fs.band_first, fs.band_stride, fs.width, fs.height, fs.stream);
+        rt_status st = fold(ctx, fs.layout, fs.plane.p, 1, frame_num, d_frame, pl.d_list.p, fs.stream);
         if (st != RT_OK) return st;
         RT_HIP(ctx, hipEventRecord(fs.ev_free, fs.stream), "recording a pipelined frame's blend");
         fs.folded = true;
@@ -1118,8 +1119,6 @@ extern "C" rt_status rt_frame_depth(rt_ctx *ctx, int32_t depth)
     return RT_OK;
 }
 
-namespace { rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes); }
-
 /* host-buffer form of rt_frame_collect, with rt_render's contract for previous_render and *frame_num */
 extern "C" rt_status rt_frame_collect_host(rt_ctx *ctx, int32_t *frame_num, float *previous_render)
 {
@@ -1129,9 +1128,9 @@ extern "C" rt_status rt_frame_collect_host(rt_ctx *ctx, int32_t *frame_num, floa
     if (!previous_render) return rt_frame_collect(ctx, 0, nullptr, nullptr);          /* discard */
     if (*frame_num < 0) return set_err(ctx, RT_ERR_INVALID, "bad frame number");
     FrameSlot &fs = pl.slots[pl.order[0]];
-    if (fs.compact || fs.listed || fs.band_stride != 1) return set_err(ctx, RT_ERR_INVALID, "the host-buffer form collects whole frames (submitted without a tile spec)");
+    if (!fs.layout.whole_frame()) return set_err(ctx, RT_ERR_INVALID, "the host-buffer form collects whole frames (submitted without a tile spec)");
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    const size_t bytes = (size_t)fs.width * (size_t)fs.height * 3 * sizeof(float);
+    const size_t bytes = (size_t)fs.layout.width * (size_t)fs.layout.height * 3 * sizeof(float);
     rt_status st = ensure_frame_buffers(ctx, bytes);
     if (st != RT_OK) return st;
     /* everything on the frame's own stream, behind its render kernel; the host waits for that stream only - the younger frames
@@ -1246,22 +1245,6 @@ extern "C" rt_status rt_last_kernel_ms(rt_ctx *ctx, float *ms)
     return RT_OK;
 }
 
-namespace {
-
-/* d_prev and d_out of exactly `bytes` */
-rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes)
-{
-    const size_t floats = bytes / 4;
-    if (ctx->d_prev.cap == floats && ctx->d_out.cap == floats) return RT_OK;
-    ctx->d_prev.release();
-    ctx->d_out.release();
-    RT_HIP(ctx, ctx->d_prev.grow(floats), "allocating previous-frame buffer");
-    RT_HIP(ctx, ctx->d_out.grow(floats), "allocating frame buffer");
-    return RT_OK;
-}
-
-}  // namespace
-
 extern "C" rt_status rt_render(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
                                int32_t time_ms, int32_t *frame_num, float *previous_render)
 {
@@ -1330,35 +1313,26 @@ extern "C" rt_status rt_ctx_synchronize(rt_ctx *ctx)
  * ============================================================================================= */
 namespace {
 
-struct BandLayout {
-    int W = 0, H = 0, band_rows = 8, n = 1;
-    size_t chunk() const { return (size_t)band_rows * (size_t)W * 3; }            /* floats per band */
-    int bands_total() const { return (H + band_rows - 1) / band_rows; }
-    int bands_of(int i) const { const int t = bands_total(); return t > i ? (t - i + n - 1) / n : 0; }
-    size_t floats_of(int i) const { return (size_t)bands_of(i) * chunk(); }
-};
-
-/* bands of rank i between a full frame and a compact buffer, both on the current device.  The last band
- * of the image may be ragged: only its valid rows exist in the full frame. */
-hipError_t copy_bands(const BandLayout &L, int i, float *full, float *compact, bool to_full, hipStream_t stream)
+/* A compact image of layout L and the width x height frame, both on the current device: the image into the frame (to_frame) or
+ * out of it.  A list's tiles go through rt_launch_tiles_copy (d_tile_list: the list on this device); bands through one 2D copy
+ * of the whole bands and one of the valid rows of a ragged last band (only those exist in the frame). */
+hipError_t exchange(const rt_sched::Layout &L, float *compact, float *frame, bool to_frame, const uint32_t *d_tile_list, hipStream_t stream)
 {
-    const int nb = L.bands_of(i);
-    if (nb == 0) return hipSuccess;
-    const size_t chunk_bytes = L.chunk() * 4, full_pitch = chunk_bytes * (size_t)L.n;
-    const int last_band = i + (nb - 1) * L.n;
-    const int last_rows = std::min(L.band_rows, L.H - last_band * L.band_rows);
-    const int whole = last_rows == L.band_rows ? nb : nb - 1;
-    float *full0 = full + (size_t)i * L.chunk();
+    if (L.listed) return rt_launch_tiles_copy(compact, frame, d_tile_list, L.num_tiles, L.tiles_x, L.width, L.height, to_frame ? 1 : 0, stream);
+    const int nb = L.owned_bands(), whole = L.whole_bands();
+    const size_t chunk_bytes = L.band_floats() * 4, frame_pitch = chunk_bytes * (size_t)L.band_stride;
+    float *frame0 = frame + (size_t)L.band_first * L.band_floats();
     hipError_t e = hipSuccess;
     if (whole > 0) {
-        e = to_full ? hipMemcpy2DAsync(full0, full_pitch, compact, chunk_bytes, chunk_bytes, (size_t)whole, hipMemcpyDeviceToDevice, stream)
-                    : hipMemcpy2DAsync(compact, chunk_bytes, full0, full_pitch, chunk_bytes, (size_t)whole, hipMemcpyDeviceToDevice, stream);
+        e = to_frame ? hipMemcpy2DAsync(frame0, frame_pitch, compact, chunk_bytes, chunk_bytes, (size_t)whole, hipMemcpyDeviceToDevice, stream)
+                     : hipMemcpy2DAsync(compact, chunk_bytes, frame0, frame_pitch, chunk_bytes, (size_t)whole, hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return e;
     }
     if (whole < nb) {
-        const size_t bytes = (size_t)last_rows * (size_t)L.W * 12;
-        float *f = full + (size_t)last_band * L.chunk(), *c = compact + (size_t)(nb - 1) * L.chunk();
-        e = to_full ? hipMemcpyAsync(f, c, bytes, hipMemcpyDeviceToDevice, stream) : hipMemcpyAsync(c, f, bytes, hipMemcpyDeviceToDevice, stream);
+        const int b = L.band(nb - 1);
+        const size_t bytes = (size_t)L.rows_of(b) * (size_t)L.width * 12;
+        float *f = frame + (size_t)b * L.band_floats(), *c = compact + (size_t)(nb - 1) * L.band_floats();
+        e = to_frame ? hipMemcpyAsync(f, c, bytes, hipMemcpyDeviceToDevice, stream) : hipMemcpyAsync(c, f, bytes, hipMemcpyDeviceToDevice, stream);
     }
     return e;
 }
@@ -1441,18 +1415,11 @@ extern "C" rt_status rt_gather(rt_ctx *root, float *d_frame, int32_t width, int3
 {
     if (!root || !src || !d_frame || !d_bands || !src_tiles) return set_err(root, RT_ERR_INVALID, "null argument");
     if (width <= 0 || height <= 0) return set_err(root, RT_ERR_INVALID, "bad image size");
-    const bool listed = src_tiles->tile_list != nullptr;
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
-    BandLayout L;
-    size_t floats;
     if (const char *bad = rt_sched::tile_spec_error(*src_tiles, tiles_x, tiles_y)) return set_err(root, RT_ERR_INVALID, bad);
-    if (listed) {
-        if (!rt_sched::tiles_in_image(src_tiles->tile_list, src_tiles->num_tiles, tiles_x, tiles_y)) return set_err(root, RT_ERR_INVALID, "a tile index outside the image");
-        floats = (size_t)src_tiles->num_tiles * 192;
-    } else {
-        L.W = width; L.H = height; L.band_rows = src_tiles->band_rows; L.n = src_tiles->band_stride;
-        floats = L.floats_of(src_tiles->band_first);
-    }
+    if (src_tiles->tile_list && !rt_sched::tiles_in_image(src_tiles->tile_list, src_tiles->num_tiles, tiles_x, tiles_y))
+        return set_err(root, RT_ERR_INVALID, "a tile index outside the image");
+    const rt_sched::Layout L(*src_tiles, width, height);
     rt_status st = multi_prepare(root);
     if (st != RT_OK) return st;
     hipStream_t s0 = (hipStream_t)root_stream;
@@ -1464,11 +1431,11 @@ extern "C" rt_status rt_gather(rt_ctx *root, float *d_frame, int32_t width, int3
          * root's stream (src may be a frame ahead of the root) */
         if ((st = multi_prepare(src)) != RT_OK) return set_err(root, st, rt_last_error(src));
         (void)peer_access(src, root);
-        if ((st = stage_for(root, src, floats, s0, &sg)) != RT_OK) return st;
+        if ((st = stage_for(root, src, L.compact_floats(), s0, &sg)) != RT_OK) return st;
         RT_HIP(src, hipSetDevice(src->device), "selecting device");
         if (sg->used) RT_HIP(src, hipStreamWaitEvent(src->multi_stream, sg->ev_free, 0), "ordering the copy behind the previous de-interleave");
         if (src->launched) RT_HIP(src, hipStreamWaitEvent(src->multi_stream, src->ev_stop, 0), "ordering the gather behind the render");
-        RT_HIP(src, copy_between(sg->d.p, root->device, d_bands, src->device, floats * 4, src->multi_stream), "copying the rank's image to the root GPU");
+        RT_HIP(src, copy_between(sg->d.p, root->device, d_bands, src->device, L.compact_floats() * 4, src->multi_stream), "copying the rank's image to the root GPU");
         RT_HIP(src, hipEventRecord(src->ev_multi, src->multi_stream), "recording the gather event");
         RT_HIP(root, hipSetDevice(root->device), "selecting device");
         RT_HIP(root, hipStreamWaitEvent(s0, src->ev_multi, 0), "ordering the de-interleave behind the copy");
@@ -1477,13 +1444,9 @@ extern "C" rt_status rt_gather(rt_ctx *root, float *d_frame, int32_t width, int3
         RT_HIP(root, hipSetDevice(root->device), "selecting device");
         if (src->launched) RT_HIP(root, hipStreamWaitEvent(s0, src->ev_stop, 0), "ordering the gather behind the render");
     }
-    if (listed) {
-        const uint32_t *d_list = nullptr;
-        if ((st = device_tile_list(root, src_tiles->tile_list, src_tiles->num_tiles, s0, &d_list)) != RT_OK) return st;
-        RT_HIP(root, rt_launch_tiles_copy(from, d_frame, d_list, src_tiles->num_tiles, tiles_x, width, height, 1, s0), "de-interleaving tiles");
-    } else {
-        RT_HIP(root, copy_bands(L, src_tiles->band_first, d_frame, from, true, s0), "de-interleaving bands");
-    }
+    const uint32_t *d_list = nullptr;
+    if (L.listed && (st = device_tile_list(root, src_tiles->tile_list, L.num_tiles, s0, &d_list)) != RT_OK) return st;
+    RT_HIP(root, exchange(L, from, d_frame, true, d_list, s0), L.listed ? "de-interleaving tiles" : "de-interleaving bands");
     if (sg) {
         RT_HIP(root, hipEventRecord(sg->ev_free, s0), "recording the staging event");
         sg->used = true;
@@ -1495,10 +1458,183 @@ namespace {
 
 /* what rank i of a multi-GPU call renders and where its image lives */
 struct RankPlan {
+    rt_ctx *c = nullptr;
+    const rt_scene *scene = nullptr;
     rt_tile_spec spec;
-    size_t floats = 0;                   /* size of its compact image */
+    rt_sched::Layout layout;             /* compact: the rank's bands, or its tile list */
     const uint32_t *root_list = nullptr; /* tile lists: the rank's list on the ROOT's GPU (for the copies to and from the frame) */
+    Stage *stage = nullptr;              /* the root's landing area for the rank's image */
 };
+
+/* the arguments; then every rank's stream and event, and direct xGMI copies to and from the root where the platform allows
+ * (instead of staging through the host).  Leaves the root's device current. */
+rt_status check_and_ready(rt_ctx *root, const std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
+                          int32_t n_frames, int32_t frame_num, int32_t band_rows, const float *d_frame)
+{
+    if (!cam || !rs || !times_ms || !d_frame || n_frames < 1 || frame_num < 0) return set_err(root, RT_ERR_INVALID, "null argument");
+    if (cam->width <= 0 || cam->height <= 0 || band_rows < 0 || (band_rows & 7)) return set_err(root, RT_ERR_INVALID, "bad image size or band_rows (0, or a positive multiple of 8)");
+    for (size_t i = 0; i < plan.size(); i++) {
+        if (!plan[i].c || !plan[i].scene || plan[i].scene->ctx != plan[i].c) return set_err(root, RT_ERR_INVALID, "rank without a context, or a scene committed on another context");
+        for (size_t j = 0; j < i; j++) if (plan[j].c == plan[i].c) return set_err(root, RT_ERR_INVALID, "a context may appear once (its launch scratch is not shared between ranks)");
+    }
+    rt_status st;
+    if ((st = multi_prepare(root)) != RT_OK) return st;
+    for (const RankPlan &p : plan) {
+        if ((st = multi_prepare(p.c)) != RT_OK) return set_err(root, st, rt_last_error(p.c));
+        (void)peer_access(p.c, root);
+    }
+    RT_HIP(root, hipSetDevice(root->device), "selecting device");
+    return RT_OK;
+}
+
+/* Cost-balanced ownership of the tiles, in root->multi.  A new view is dealt out interleaved, and the calls on it measure what
+ * the tiles cost until one has done so.  The call after that collects every rank's figures (this waits for those launches,
+ * which the caller has normally consumed already) and deals the tiles out again by cost.  All read-backs happen here,
+ * before any rank is launched, so no rank's launch waits on another rank's kernel. */
+rt_status balance(rt_ctx *root, const std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs)
+{
+    MultiState &ms = root->multi;
+    const int n = (int)plan.size(), tiles_x = (cam->width + 7) / 8, tiles_y = (cam->height + 7) / 8;
+    /* (the bounce limit, and preview (< 8 samples) or real: ownership measured on the one says little about the other) */
+    std::vector<uint32_t> key;
+    push_camera(key, cam);
+    key.push_back((uint32_t)cam->width); key.push_back((uint32_t)cam->height); key.push_back((uint32_t)n);
+    key.push_back((uint32_t)rs->reflection_limit); key.push_back(rs->rays_per_pixel < 8 ? 0u : 1u);
+    for (const RankPlan &p : plan) { key.push_back(p.scene->uid); key.push_back((uint32_t)p.c->device); }
+    std::vector<int32_t> owner((size_t)tiles_x * tiles_y);
+    rt_status st;
+    if (key != ms.key || ms.lists.size() != (size_t)n) {
+        if ((st = rt_partition_tiles(nullptr, tiles_x, tiles_y, n, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
+        rt_sched::deal_tiles(owner, n, nullptr, nullptr, ms.lists, ms.costs, ms.peaks);
+        ms.key = key;
+        ms.owners = Owners::interleaved;
+    } else if (ms.owners == Owners::measured) {
+        std::vector<uint32_t> cost(owner.size(), 0u), peak(owner.size(), 0u);
+        bool have_all = true;
+        for (size_t i = 0; i < plan.size() && have_all; i++) {
+            const std::vector<uint32_t> &list = ms.lists[i];
+            if (list.empty()) continue;
+            std::vector<uint32_t> ids(list.size()), cs(list.size()), ps(list.size());
+            int32_t got = 0;
+            have_all = rt_tile_costs(plan[i].c, ids.data(), cs.data(), ps.data(), (int32_t)list.size(), &got) == RT_OK && (size_t)got == list.size() && ids == list;
+            for (size_t k = 0; k < list.size() && have_all; k++) { cost[ids[k]] = cs[k]; peak[ids[k]] = ps[k]; }
+        }
+        RT_HIP(root, hipSetDevice(root->device), "selecting device");
+        if (!have_all) { ms.owners = Owners::interleaved; return RT_OK; }    /* (a rank's context has rendered another view since: measure again) */
+        if ((st = rt_partition_tiles(cost.data(), tiles_x, tiles_y, n, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
+        rt_sched::deal_tiles(owner, n, cost.data(), peak.data(), ms.lists, ms.costs, ms.peaks);
+        ms.owners = Owners::balanced;
+    }
+    return RT_OK;
+}
+
+/* who renders what, each rank into a compact image (a tile list goes to the root's GPU as well) */
+rt_status plan_ranks(rt_ctx *root, std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs, int32_t band_rows, hipStream_t s0)
+{
+    const bool listed = band_rows == 0;
+    rt_status st;
+    if (listed && (st = balance(root, plan, cam, rs)) != RT_OK) return st;
+    const MultiState &ms = root->multi;
+    for (size_t i = 0; i < plan.size(); i++) {
+        RankPlan &p = plan[i];
+        std::memset(&p.spec, 0, sizeof p.spec);
+        p.spec.compact = 1;
+        if (listed) {
+            const bool costed = ms.owners == Owners::balanced && !ms.lists[i].empty();
+            static const uint32_t none = 0;      /* (an empty vector's data() may be null, which would read as "no list") */
+            p.spec.tile_list = ms.lists[i].empty() ? &none : ms.lists[i].data();
+            p.spec.num_tiles = (int32_t)ms.lists[i].size();
+            p.spec.tile_cost = costed ? ms.costs[i].data() : nullptr;
+            p.spec.tile_peak = costed ? ms.peaks[i].data() : nullptr;
+        } else {
+            p.spec.band_rows = band_rows; p.spec.band_first = (int32_t)i; p.spec.band_stride = (int32_t)plan.size();
+        }
+        p.layout = rt_sched::Layout(p.spec, cam->width, cam->height);
+        if (listed && (st = device_tile_list(root, p.spec.tile_list, p.spec.num_tiles, s0, &p.root_list)) != RT_OK) return st;
+    }
+    return RT_OK;
+}
+
+/* RT_AMD_MULTI_CAREFUL=1 (diagnosis): the host waits for every stream involved after each phase, so that no ordering between
+ * devices rests on an event - if a frame is wrong or a call hangs in the asynchronous form but not in this one, the
+ * fault is in the event choreography, otherwise in the copies themselves; an error names the phase it was found in.
+ * bench.py's capi_multi leg falls back to it by itself (this path has never run on two physical GPUs). */
+rt_status careful(rt_ctx *root, const std::vector<RankPlan> &plan, hipStream_t s0, const char *phase)
+{
+    if (!root->multi_careful) return RT_OK;
+    for (const RankPlan &p : plan) {
+        hipError_t e = hipSetDevice(p.c->device);
+        if (e == hipSuccess) e = hipStreamSynchronize(p.c->multi_stream);
+        if (e != hipSuccess) { (void)hipSetDevice(root->device); return hip_fail(root, e, phase); }
+    }
+    hipError_t e = hipSetDevice(root->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(s0);
+    if (e != hipSuccess) return hip_fail(root, e, phase);
+    return RT_OK;
+}
+
+/* The ranks' buffers, then their images travel and are rendered, in three phases.  (root->ev_multi is recorded twice: in the
+ * first phase, on the caller's stream, as "the ranks may start", and in the second on rank 0's stream as "rank 0's image is
+ * in the staging area"; a hipStreamWaitEvent captures the record that precedes it, and the calls are in that order.) */
+rt_status render_ranks(rt_ctx *root, std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
+                       int32_t n_frames, int32_t frame_num, float *d_frame, hipStream_t s0)
+{
+    /* ---- every rank's compact image on its GPU, and a landing area per rank on the root's */
+    rt_status st;
+    for (RankPlan &p : plan) {
+        const size_t floats = p.layout.compact_floats();
+        if (p.c->d_bands.cap < floats || !p.c->d_bands.p) {
+            RT_HIP(p.c, hipSetDevice(p.c->device), "selecting device");
+            RT_HIP(p.c, hipStreamSynchronize(p.c->multi_stream), "waiting for the rank's image buffer");
+            if (hipError_t e = p.c->d_bands.grow(floats)) return set_err(root, hip_fail(p.c, e, "allocating the rank's image buffer"), p.c->err);
+        }
+        if ((st = stage_for(root, p.c, floats, s0, &p.stage)) != RT_OK) return st;
+    }
+
+    /* ---- the image so far goes out to its owners, through their landing areas.  (Frame 0 ignores the buffers' content, but
+     * the landing areas may still be read by an earlier call's de-interleave: stage_for has ordered s0 behind that.) */
+    RT_HIP(root, hipSetDevice(root->device), "selecting device");
+    for (const RankPlan &p : plan)
+        if (frame_num > 0 && p.layout.compact_floats() > 0)
+            RT_HIP(root, exchange(p.layout, p.stage->d.p, d_frame, false, p.root_list, s0), p.layout.listed ? "interleaving tiles" : "interleaving bands");
+    RT_HIP(root, hipEventRecord(root->ev_multi, s0), "recording the start event");
+    if ((st = careful(root, plan, s0, "careful mode: waiting for the caller's stream before the ranks start")) != RT_OK) return st;
+    for (const RankPlan &p : plan) {
+        RT_HIP(p.c, hipSetDevice(p.c->device), "selecting device");
+        RT_HIP(p.c, hipStreamWaitEvent(p.c->multi_stream, root->ev_multi, 0), "ordering the ranks behind the caller's stream");
+        if (frame_num > 0)
+            RT_HIP(p.c, copy_between(p.c->d_bands.p, p.c->device, p.stage->d.p, root->device, p.layout.compact_floats() * 4, p.c->multi_stream), "copying the image so far to its owner");
+    }
+    if ((st = careful(root, plan, s0, "careful mode: waiting for the image so far to reach its owners (scatter-out)")) != RT_OK) return st;
+
+    /* ---- every rank renders its tiles (asynchronous launches from this one thread) and sends its image to its landing area */
+    for (const RankPlan &p : plan) {
+        const size_t floats = p.layout.compact_floats();
+        if (floats == 0) continue;
+        RT_HIP(p.c, hipSetDevice(p.c->device), "selecting device");
+        const int32_t cap = batch_cap(p.c, floats);
+        for (int32_t done = 0; done < n_frames;) {
+            const int32_t k = std::min<int32_t>(n_frames - done, cap);
+            st = rt_render_device_batch(p.c, p.scene, cam, rs, times_ms + done, k, frame_num + done, &p.spec, p.c->d_bands.p, p.c->multi_stream);
+            if (st != RT_OK) return set_err(root, st, rt_last_error(p.c));
+            done += k;
+        }
+        RT_HIP(p.c, copy_between(p.stage->d.p, root->device, p.c->d_bands.p, p.c->device, floats * 4, p.c->multi_stream), "copying the rank's image to the root GPU");
+        RT_HIP(p.c, hipEventRecord(p.c->ev_multi, p.c->multi_stream), "recording the gather event");
+    }
+    if ((st = careful(root, plan, s0, "careful mode: waiting for the ranks' kernels and their copies to the root GPU")) != RT_OK) return st;
+
+    /* ---- every rank's image into the frame, in s0's order behind its copy */
+    RT_HIP(root, hipSetDevice(root->device), "selecting device");
+    for (const RankPlan &p : plan) {
+        if (p.layout.compact_floats() == 0) continue;
+        RT_HIP(root, hipStreamWaitEvent(s0, p.c->ev_multi, 0), "ordering the de-interleave behind the copies");
+        RT_HIP(root, exchange(p.layout, p.stage->d.p, d_frame, true, p.root_list, s0), p.layout.listed ? "de-interleaving tiles" : "de-interleaving bands");
+        RT_HIP(root, hipEventRecord(p.stage->ev_free, s0), "recording the staging event");
+        p.stage->used = true;
+    }
+    return careful(root, plan, s0, "careful mode: waiting for the de-interleave into the frame");
+}
 
 }  // namespace
 
@@ -1511,178 +1647,18 @@ extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_rank
 {
     if (!ranks || n_ranks < 1 || !ranks[0].ctx) return RT_ERR_INVALID;
     rt_ctx *root = ranks[0].ctx;
-    if (!cam || !rs || !times_ms || !d_frame || n_frames < 1 || frame_num < 0) return set_err(root, RT_ERR_INVALID, "null argument");
-    if (cam->width <= 0 || cam->height <= 0 || band_rows < 0 || (band_rows & 7)) return set_err(root, RT_ERR_INVALID, "bad image size or band_rows (0, or a positive multiple of 8)");
-    for (int i = 0; i < n_ranks; i++) {
-        if (!ranks[i].ctx || !ranks[i].scene || ranks[i].scene->ctx != ranks[i].ctx) return set_err(root, RT_ERR_INVALID, "rank without a context, or a scene committed on another context");
-        for (int j = 0; j < i; j++) if (ranks[j].ctx == ranks[i].ctx) return set_err(root, RT_ERR_INVALID, "a context may appear once (its launch scratch is not shared between ranks)");
-    }
-    const int W = cam->width, H = cam->height;
-    const int tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8;
-    const bool listed = band_rows == 0;
     hipStream_t s0 = (hipStream_t)hip_stream;
+    std::vector<RankPlan> plan((size_t)n_ranks);
+    for (int i = 0; i < n_ranks; i++) { plan[(size_t)i].c = ranks[i].ctx; plan[(size_t)i].scene = ranks[i].scene; }
     rt_status st;
-    if ((st = multi_prepare(root)) != RT_OK) return st;
-    for (int i = 0; i < n_ranks; i++) {
-        rt_ctx *c = ranks[i].ctx;
-        if ((st = multi_prepare(c)) != RT_OK) return set_err(root, st, rt_last_error(c));
-        (void)peer_access(c, root);      /* direct xGMI copies instead of staging through the host when the platform allows */
-    }
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
+    if ((st = check_and_ready(root, plan, cam, rs, times_ms, n_frames, frame_num, band_rows, d_frame)) != RT_OK) return st;
     /* this call holds every rank's list on the root's GPU at once (the copies to and from the frame), and rank 0's launch
      * looks its own up as well: what the cache hands out from here on is not recycled before the call has queued its work */
     struct Pin { rt_ctx *c; explicit Pin(rt_ctx *c_) : c(c_) { pin_tile_lists(c); } ~Pin() { unpin_tile_lists(c); } } pin(root);
-
-    /* ---- who renders what -------------------------------------------------------------------------- */
-    BandLayout L;
-    L.W = W; L.H = H; L.band_rows = listed ? 8 : band_rows; L.n = n_ranks;
-    std::vector<RankPlan> plan((size_t)n_ranks);
-    MultiState &ms = root->multi;
-    bool collect_after = false;
-    if (listed) {
-        std::vector<uint32_t> key;
-        push_camera(key, cam);
-        key.push_back((uint32_t)W); key.push_back((uint32_t)H); key.push_back((uint32_t)n_ranks);
-        /* the bounce limit, and whether this is a preview-quality launch (< 8 samples) or a real one: ownership measured on
-         * the one says little about the other */
-        key.push_back((uint32_t)rs->reflection_limit); key.push_back(rs->rays_per_pixel < 8 ? 0u : 1u);
-        for (int i = 0; i < n_ranks; i++) { key.push_back(ranks[i].scene->uid); key.push_back((uint32_t)ranks[i].ctx->device); }
-        std::vector<int32_t> owner((size_t)tiles_x * tiles_y);
-        if (key != ms.key || ms.lists.size() != (size_t)n_ranks) {
-            /* a new view: interleaved ownership; this call's first launches measure what the tiles cost */
-            if ((st = rt_partition_tiles(nullptr, tiles_x, tiles_y, n_ranks, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
-            rt_sched::deal_tiles(owner, n_ranks, nullptr, nullptr, ms.lists, ms.costs, ms.peaks);
-            ms.key = key;
-            ms.stage = 0;
-        } else if (ms.stage == 1) {
-            /* the previous call measured the tiles: collect every rank's figures (this waits for those launches, which
-             * the caller has normally consumed already), then deal the tiles out again by cost.  All read-backs happen
-             * here, before any rank is launched, so no rank's launch waits on another rank's kernel. */
-            std::vector<uint32_t> cost((size_t)tiles_x * tiles_y, 0u), peak((size_t)tiles_x * tiles_y, 0u);
-            bool have_all = true;
-            for (int i = 0; i < n_ranks && have_all; i++) {
-                const size_t cnt = ms.lists[(size_t)i].size();
-                if (cnt == 0) continue;
-                std::vector<uint32_t> ids(cnt), cs(cnt), ps(cnt);
-                int32_t got = 0;
-                if (rt_tile_costs(ranks[i].ctx, ids.data(), cs.data(), ps.data(), (int32_t)cnt, &got) != RT_OK || (size_t)got != cnt) { have_all = false; break; }
-                for (size_t k = 0; k < cnt && have_all; k++) {
-                    if (ids[k] != ms.lists[(size_t)i][k]) have_all = false;     /* the rank's context has rendered another view since */
-                    else { cost[ids[k]] = cs[k]; peak[ids[k]] = ps[k]; }
-                }
-            }
-            RT_HIP(root, hipSetDevice(root->device), "selecting device");
-            if (have_all) {
-                if ((st = rt_partition_tiles(cost.data(), tiles_x, tiles_y, n_ranks, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
-                rt_sched::deal_tiles(owner, n_ranks, cost.data(), peak.data(), ms.lists, ms.costs, ms.peaks);
-                ms.stage = 2;
-            } else {
-                ms.stage = 0;            /* (a rank's view was replaced in between: measure again) */
-            }
-        }
-        collect_after = ms.stage == 0;
-        for (int i = 0; i < n_ranks; i++) {
-            RankPlan &p = plan[(size_t)i];
-            std::memset(&p.spec, 0, sizeof p.spec);
-            p.spec.compact = 1;
-            p.spec.tile_list = ms.lists[(size_t)i].data();
-            p.spec.num_tiles = (int32_t)ms.lists[(size_t)i].size();
-            p.spec.tile_cost = (ms.stage == 2 && p.spec.num_tiles > 0) ? ms.costs[(size_t)i].data() : nullptr;
-            p.spec.tile_peak = (ms.stage == 2 && p.spec.num_tiles > 0) ? ms.peaks[(size_t)i].data() : nullptr;
-            /* (an empty vector's data() may be null, which would read as "no list") */
-            static const uint32_t none = 0;
-            if (!p.spec.tile_list) p.spec.tile_list = &none;
-            p.floats = (size_t)p.spec.num_tiles * 192;
-            if ((st = device_tile_list(root, p.spec.tile_list, p.spec.num_tiles, s0, &p.root_list)) != RT_OK) return st;
-        }
-    } else {
-        for (int i = 0; i < n_ranks; i++) {
-            RankPlan &p = plan[(size_t)i];
-            std::memset(&p.spec, 0, sizeof p.spec);
-            p.spec.band_rows = band_rows; p.spec.band_first = i; p.spec.band_stride = n_ranks; p.spec.compact = 1;
-            p.floats = L.floats_of(i);
-        }
-    }
-
-    /* ---- buffers: every rank's compact image on its GPU, a landing area per rank on the root's ---------- */
-    std::vector<Stage *> stage((size_t)n_ranks, nullptr);
-    for (int i = 0; i < n_ranks; i++) {
-        rt_ctx *c = ranks[i].ctx;
-        if (c->d_bands.cap < plan[(size_t)i].floats || !c->d_bands.p) {
-            RT_HIP(c, hipSetDevice(c->device), "selecting device");
-            RT_HIP(c, hipStreamSynchronize(c->multi_stream), "waiting for the rank's image buffer");
-            if (hipError_t e = c->d_bands.grow(plan[(size_t)i].floats)) return set_err(root, hip_fail(c, e, "allocating the rank's image buffer"), c->err);
-        }
-        if ((st = stage_for(root, c, plan[(size_t)i].floats, s0, &stage[(size_t)i])) != RT_OK) return st;
-    }
-
-    /* ---- the image so far goes out to its owners.  (root->ev_multi is recorded twice in this function: here, on the
-     * caller's stream, as "the ranks may start", and further down on rank 0's stream as "rank 0's image is in the
-     * staging area"; a hipStreamWaitEvent captures the record that precedes it, and the calls are in that order.) */
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
-    if (frame_num > 0) {
-        for (int i = 0; i < n_ranks; i++) {
-            if (plan[(size_t)i].floats == 0) continue;
-            if (listed) RT_HIP(root, rt_launch_tiles_copy(stage[(size_t)i]->d.p, d_frame, plan[(size_t)i].root_list, plan[(size_t)i].spec.num_tiles, tiles_x, W, H, 0, s0), "interleaving tiles");
-            else RT_HIP(root, copy_bands(L, i, d_frame, stage[(size_t)i]->d.p, false, s0), "interleaving bands");
-        }
-    }
-    /* RT_AMD_MULTI_CAREFUL=1 (diagnosis): the host waits for every stream involved after each phase, so that no ordering between
-     * devices rests on an event - if a frame is wrong or a call hangs in the asynchronous form but not in this one, the
-     * fault is in the event choreography, otherwise in the copies themselves; an error names the phase it was found in.
-     * bench.py's capi_multi leg falls back to it by itself (this path has never run on two physical GPUs). */
-    auto careful = [&](const char *phase) -> rt_status {
-        if (!root->multi_careful) return RT_OK;
-        for (int i = 0; i < n_ranks; i++) {
-            rt_ctx *c = ranks[i].ctx;
-            hipError_t e = hipSetDevice(c->device);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->multi_stream);
-            if (e != hipSuccess) { (void)hipSetDevice(root->device); return hip_fail(root, e, phase); }
-        }
-        hipError_t e = hipSetDevice(root->device);
-        if (e == hipSuccess) e = hipStreamSynchronize(s0);
-        if (e != hipSuccess) return hip_fail(root, e, phase);
-        return RT_OK;
-    };
-    /* (frame 0 ignores the buffers' content, but the staging areas may still be read by an earlier call's
-     * de-interleave: stage_for has ordered s0 behind that, and the ranks start behind s0) */
-    RT_HIP(root, hipEventRecord(root->ev_multi, s0), "recording the start event");
-    if ((st = careful("careful mode: waiting for the caller's stream before the ranks start")) != RT_OK) return st;
-    for (int i = 0; i < n_ranks; i++) {
-        rt_ctx *c = ranks[i].ctx;
-        RT_HIP(c, hipSetDevice(c->device), "selecting device");
-        RT_HIP(c, hipStreamWaitEvent(c->multi_stream, root->ev_multi, 0), "ordering the ranks behind the caller's stream");
-        if (frame_num > 0)
-            RT_HIP(c, copy_between(c->d_bands.p, c->device, stage[(size_t)i]->d.p, root->device, plan[(size_t)i].floats * 4, c->multi_stream), "copying the image so far to its owner");
-    }
-    if ((st = careful("careful mode: waiting for the image so far to reach its owners (scatter-out)")) != RT_OK) return st;
-    /* ---- every rank renders its tiles (asynchronous launches from this one thread) and sends them back ---- */
-    for (int i = 0; i < n_ranks; i++) {
-        rt_ctx *c = ranks[i].ctx;
-        if (plan[(size_t)i].floats == 0) continue;
-        RT_HIP(c, hipSetDevice(c->device), "selecting device");
-        const int32_t cap = batch_cap(c, plan[(size_t)i].floats);
-        for (int32_t done = 0; done < n_frames;) {
-            const int32_t k = std::min<int32_t>(n_frames - done, cap);
-            st = rt_render_device_batch(c, ranks[i].scene, cam, rs, times_ms + done, k, frame_num + done, &plan[(size_t)i].spec, c->d_bands.p, c->multi_stream);
-            if (st != RT_OK) return set_err(root, st, rt_last_error(c));
-            done += k;
-        }
-        RT_HIP(c, copy_between(stage[(size_t)i]->d.p, root->device, c->d_bands.p, c->device, plan[(size_t)i].floats * 4, c->multi_stream), "copying the rank's image to the root GPU");
-        RT_HIP(c, hipEventRecord(c->ev_multi, c->multi_stream), "recording the gather event");
-    }
-    if ((st = careful("careful mode: waiting for the ranks' kernels and their copies to the root GPU")) != RT_OK) return st;
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
-    for (int i = 0; i < n_ranks; i++) {
-        if (plan[(size_t)i].floats == 0) continue;
-        RT_HIP(root, hipStreamWaitEvent(s0, ranks[i].ctx->ev_multi, 0), "ordering the de-interleave behind the copies");
-        if (listed) RT_HIP(root, rt_launch_tiles_copy(stage[(size_t)i]->d.p, d_frame, plan[(size_t)i].root_list, plan[(size_t)i].spec.num_tiles, tiles_x, W, H, 1, s0), "de-interleaving tiles");
-        else RT_HIP(root, copy_bands(L, i, d_frame, stage[(size_t)i]->d.p, true, s0), "de-interleaving bands");
-        RT_HIP(root, hipEventRecord(stage[(size_t)i]->ev_free, s0), "recording the staging event");
-        stage[(size_t)i]->used = true;
-    }
-    if ((st = careful("careful mode: waiting for the de-interleave into the frame")) != RT_OK) return st;
-    if (listed && collect_after) ms.stage = 1;
+    if ((st = plan_ranks(root, plan, cam, rs, band_rows, s0)) != RT_OK) return st;
+    const bool measuring = band_rows == 0 && root->multi.owners == Owners::interleaved;    /* (this call's launches measure the tiles) */
+    if ((st = render_ranks(root, plan, cam, rs, times_ms, n_frames, frame_num, d_frame, s0)) != RT_OK) return st;
+    if (measuring) root->multi.owners = Owners::measured;
     return RT_OK;
 }
 

@@ -1,8 +1,8 @@
 /*
- * rt_schedule.h — the host arithmetic of the render schedule: which tiles a launch renders, in which order its waves take
- * them, and which rank of a multi-GPU call renders which.  Plain functions of vectors and scalars; no HIP.  Any order
- * renders the same image: the schedule only decides how long a launch takes ("Multi-frame launches and their
- * schedule").  A tile is 8 x 8 pixels; "local tile" t is the t-th tile of a launch, tiles[t] its index in the image.
+ * rt_schedule.h — the host arithmetic of the render schedule: which tiles a launch renders, where their pixels go, in which
+ * order its waves take them, and which rank of a multi-GPU call renders which.  Plain functions of vectors and scalars;
+ * no HIP.  Any order renders the same image: the schedule only decides how long a launch takes ("Multi-frame
+ * launches and their schedule").  A tile is 8 x 8 pixels; "local tile" t of a launch is its t-th, image tile tiles[t].
  * Header only: rt_capi.cpp, and the host-only sanitizer build of it, need nothing else to link.
  */
 #pragma once
@@ -56,8 +56,34 @@ inline bool tiles_in_image(const uint32_t *list, int32_t n, int tiles_x, int til
     return true;
 }
 
+/* The output layout of a launch with a valid tile spec over a width x height image: which tiles it renders and where their
+ * pixels go.  A full layout writes them in place in the frame; a compact one packs the owned bands one after another (a
+ * ragged last band padded to a whole one), or the listed tiles, 192 floats each in list order.  A list counts as bands
+ * of 8 rows, all of them (8 / 0 / 1, as the kernel sees it). */
+struct Layout {
+    int width = 0, height = 0, tiles_x = 0;
+    bool compact = false, listed = false;
+    int band_rows = 8, band_first = 0, band_stride = 1;
+    int num_tiles = 0;                   /* the tiles the launch renders */
+
+    Layout() = default;
+    Layout(const rt_tile_spec &t, int w, int h)
+        : width(w), height(h), tiles_x((w + 7) / 8), compact(t.compact != 0), listed(t.tile_list != nullptr), band_rows(listed ? 8 : t.band_rows),
+          band_first(listed ? 0 : t.band_first), band_stride(listed ? 1 : t.band_stride), num_tiles(listed ? t.num_tiles : owned_rows() / 8 * tiles_x) {}
+    int bands_total() const { return (height + band_rows - 1) / band_rows; }        /* the image's bands, a ragged last one included */
+    int owned_bands() const { const int t = bands_total(); return t > band_first ? (t - band_first + band_stride - 1) / band_stride : 0; }
+    int owned_rows() const { return owned_bands() * band_rows; }        /* a ragged last band counts whole (rt_tile_owned_rows) */
+    int band(int k) const { return band_first + k * band_stride; }      /* the k-th owned band's index in the image */
+    int rows_of(int b) const { return std::min(band_rows, height - b * band_rows); }   /* band b's rows inside the image */
+    int whole_bands() const { const int n = owned_bands(); return n > 0 && rows_of(band(n - 1)) < band_rows ? n - 1 : n; }   /* (all but a ragged last) */
+    bool whole_frame() const { return !compact && !listed && band_stride == 1; }
+    size_t band_floats() const { return (size_t)band_rows * (size_t)width * 3; }
+    size_t compact_floats() const { return listed ? (size_t)num_tiles * 192 : (size_t)owned_bands() * band_floats(); }
+    size_t plane_floats() const { return compact ? compact_floats() : (size_t)height * (size_t)width * 3; }   /* one plane of the layout */
+};
+
 /* A valid spec's tiles: tiles[t] is local tile t's index in a width x height image.  A list is taken as it is (false if
- * an index is outside the image or listed twice); bands give rt_tile_owned_rows / 8 rows of tiles, band after band. */
+ * an index is outside the image or listed twice); bands give their rows of tiles, band after band. */
 inline bool view_tiles(const rt_tile_spec &t, int width, int height, std::vector<uint32_t> &tiles)
 {
     const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
@@ -73,14 +99,11 @@ inline bool view_tiles(const rt_tile_spec &t, int width, int height, std::vector
         }
         return true;
     }
-    const uint32_t n = (uint32_t)(rt_tile_owned_rows(&t, height) / 8) * (uint32_t)tiles_x;
-    const int tiles_per_band = tiles_x * (t.band_rows >> 3);
-    tiles.assign(n, 0u);
-    for (uint32_t i = 0; i < n; i++) {
-        const int band_local = (int)i / tiles_per_band, in_band = (int)i % tiles_per_band;
-        const int band = t.band_first + band_local * t.band_stride;
-        tiles[i] = (uint32_t)((band * (t.band_rows >> 3) + in_band / tiles_x) * tiles_x + in_band % tiles_x);
-    }
+    const Layout L(t, width, height);
+    const int band_tiles = L.band_rows / 8 * tiles_x;       /* (a band's tiles are consecutive in the image) */
+    tiles.clear();
+    for (int k = 0; k < L.owned_bands(); k++)
+        for (int g = L.band(k) * band_tiles; g < (L.band(k) + 1) * band_tiles; g++) tiles.push_back((uint32_t)g);
     return true;
 }
 

@@ -1,8 +1,8 @@
 // The GPU-free entry points of rt_capi.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; test infrastructure):
-// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule (rt_schedule.h) with
-// its properties asserted, and every entry point's refusal of null / bad arguments before it touches HIP.  rt_capi.cpp is
-// compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the kernel launchers
-// (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
+// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule and the output layout
+// (rt_schedule.h) with their properties asserted, and every entry point's refusal of null / bad arguments before it touches
+// HIP.  rt_capi.cpp is compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
+// kernel launchers (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -58,7 +58,50 @@ static int enters_box(const double d[3], const rt_object &ob)
     return tmin <= tmax ? 1 : 0;
 }
 
-/* one random view through the schedule functions: tile map, guessed and refined order, job order, stride */
+/* the output layout of a valid spec whose tile map has n tiles, in full and compact form: its tile count is the map's; a plane
+ * holds the frame, or 192 floats per listed tile, or the owned (padded) rows */
+static bool check_layout(rt_tile_spec ts, int W, int H, size_t n)
+{
+    for (ts.compact = 0; ts.compact < 2; ts.compact++) {
+        const rt_sched::Layout L(ts, W, H);
+        const size_t compact = ts.tile_list ? 192 * n : (size_t)rt_tile_owned_rows(&ts, H) * W * 3;
+        CHECK(L.num_tiles >= 0 && (size_t)L.num_tiles == n, "layout: tile count");
+        CHECK(L.compact_floats() == compact && L.plane_floats() == (ts.compact ? compact : (size_t)W * H * 3), "layout: plane floats");
+        CHECK(L.whole_frame() == (!ts.compact && !ts.tile_list && ts.band_stride == 1), "layout: whole frame");
+    }
+    return true;
+}
+
+/* A band spec's layout for every band_first: the ranks' in-image rows add up to the image, and each rank's band copy (its
+ * whole bands, then a ragged last one) stays inside its compact image and the W x H frame and covers exactly its rows. */
+static bool check_band_layout(rt_tile_spec ts, int W, int H)
+{
+    std::vector<int> covered((size_t)H, 0);
+    long long rows = 0;
+    ts.compact = 1;
+    for (ts.band_first = 0; ts.band_first < ts.band_stride; ts.band_first++) {
+        const rt_sched::Layout L(ts, W, H);
+        const int nb = L.owned_bands(), whole = L.whole_bands();
+        CHECK(nb * ts.band_rows == rt_tile_owned_rows(&ts, H) && (whole == nb || whole == nb - 1), "band copy: whole bands");
+        for (int k = 0; k < nb; k++) {
+            const int b = L.band(k), r0 = b * ts.band_rows, in_image = L.rows_of(b);
+            const int copied = k < whole ? ts.band_rows : in_image;      /* exchange: one 2D copy of the whole bands, then the tail */
+            rows += in_image;
+            CHECK(in_image > 0 && copied == in_image && r0 + copied <= H, "band copy: rows outside the image");
+            CHECK((size_t)(k + 1) * L.band_floats() <= L.compact_floats() && (size_t)r0 * W * 3 + (size_t)copied * W * 3 <= (size_t)W * H * 3,
+                  "band copy: outside the compact image or the frame");
+            for (int r = r0; r < r0 + copied; r++) {
+                CHECK((r / ts.band_rows) % ts.band_stride == ts.band_first, "band copy: a row of another rank");
+                covered[(size_t)r]++;
+            }
+        }
+    }
+    CHECK(rows == H, "band layout: the ranks' in-image rows do not add up to the image");
+    for (int c : covered) CHECK(c == 1, "band copy: the ranks do not cover the image once");
+    return true;
+}
+
+/* one random view through the schedule functions: tile map, output layout, guessed and refined order, job order, stride */
 template <class Rng> static bool check_schedule(Rng &rng)
 {
     auto irand = [&](long long lo, long long hi) { return (long long)std::uniform_int_distribution<long long>(lo, hi)(rng); };
@@ -86,6 +129,7 @@ template <class Rng> static bool check_schedule(Rng &rng)
         size_t want = 0;
         for (int r = 0; r < tiles_y; r++) want += (r / rows_per_band) % ts.band_stride == ts.band_first ? tiles_x : 0;
         CHECK(in_image == want, "a band tile of the image missing");
+        if (!check_layout(ts, W, H, map.size()) || !check_band_layout(ts, W, H)) return false;
     } else {
         std::vector<uint32_t> all((size_t)tiles);
         for (int i = 0; i < tiles; i++) all[(size_t)i] = (uint32_t)i;
@@ -106,6 +150,7 @@ template <class Rng> static bool check_schedule(Rng &rng)
             CHECK(!rt_sched::view_tiles(tb, W, H, m2), "a tile outside the image or listed twice accepted");
             CHECK(dup || !rt_sched::tiles_in_image(bad.data(), tb.num_tiles, tiles_x, tiles_y), "a tile outside the image accepted");
         }
+        if (!check_layout(ts, W, H, map.size())) return false;
         ts.num_tiles = tiles + 1;
         CHECK(rt_sched::tile_spec_error(ts, tiles_x, tiles_y) != nullptr, "more tiles than the image has accepted");
     }
