@@ -27,17 +27,14 @@
 #include "rt_host.h"
 #include "rt_schedule.h"
 
-extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, int has_mesh, int scene_in_lds, int threads, int blocks, size_t lds_bytes, hipStream_t stream);
-extern "C" int rt_kernel_blocks_per_cu(int has_mesh, int scene_in_lds, int threads, size_t lds_bytes);
+extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
+extern "C" int rt_kernel_blocks_per_cu(rt_shape shape, size_t lds_bytes);
 extern "C" hipError_t rt_launch_blend(const float *partial, long long plane_floats, int num_frames, int frame_num, float *frame, long long n_floats, hipStream_t stream);
 extern "C" hipError_t rt_launch_blend_tiles(const float *partial, long long plane_floats, int num_frames, int frame_num, float *frame,
                                             const uint32_t *tile_list, int n_tiles, int tiles_x, int W, int H, hipStream_t stream);
 extern "C" hipError_t rt_launch_tiles_copy(float *compact, float *frame, const uint32_t *tile_list, int n_tiles, int tiles_x, int W, int H, int to_frame, hipStream_t stream);
 extern "C" hipError_t rt_launch_eval(int op, const uint32_t *in, uint32_t *out, int n, hipStream_t stream);
 extern "C" hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *out, hipStream_t stream);
-
-#define RT_LDS_LIMIT 163840   /* 160 KiB per CU / per workgroup on gfx950 */
-#define RT_MAX_BLOCKS_PER_CU 6
 
 namespace {
 
@@ -55,7 +52,7 @@ template <class T> struct DevBuf {
     {
         if (cap >= need && p) return hipSuccess;
         release();
-        const hipError_t e = hipMalloc((void **)&p, (need ? need : 16 / sizeof(T)) * sizeof(T));
+        const hipError_t e = hipMalloc((void **)&p, need ? need * sizeof(T) : 16);
         if (e == hipSuccess) cap = need; else p = nullptr;
         return e;
     }
@@ -185,16 +182,14 @@ struct rt_ctx {
 
 struct rt_scene {
     rt_ctx *ctx = nullptr;
-    rt_f4 *d_blob = nullptr;
-    rt_object *d_objects = nullptr;
-    float *d_tri_uv = nullptr;
-    float *d_tex = nullptr;
+    /* (members go in reverse order: the blob is freed first, the texels last) */
+    DevBuf<float> d_tex;
+    DevBuf<float> d_tri_uv;
+    DevBuf<rt_object> d_objects;
+    DevBuf<rt_f4> d_blob;
     FlatScene flat;          /* host copy (sizes, offsets) */
-    int threads = 0;         /* workgroup size chosen for this scene */
-    int blocks_per_cu = 1;   /* ... and how many of them are resident on a CU */
-    int scene_in_lds = RT_SCENE_LDS;    /* RT_SCENE_*: all of the scene in LDS, all but the triangles, or nothing */
+    rt_sched::KernelShape kernel;   /* the kernel shape chosen for this scene */
     uint32_t uid = 0;        /* distinguishes scenes in the tile-order cache (addresses get reused) */
-    size_t lds_bytes = 0;
 };
 
 namespace {
@@ -407,97 +402,34 @@ extern "C" rt_status rt_scene_commit(rt_ctx *ctx, const rt_scene_builder *b, rt_
     std::string err = rt_flatten(*b, s->flat);
     if (!err.empty()) { delete s; return set_err(ctx, RT_ERR_UNSUPPORTED, err); }
 
-    /* workgroup size: the largest one whose LDS (scene + per-lane traversal stacks) fits */
+    /* the kernel shape (rt_sched::choose_shape) from the runtime's occupancy answers; the RT_AMD_* overrides are development knobs */
+    rt_sched::ShapeOverrides ov;
+    if (const char *e = getenv("RT_AMD_THREADS")) { ov.threads_set = true; ov.threads = atoi(e); }
+    if (const char *e = getenv("RT_AMD_SCENE_MODE")) ov.hybrid = atoi(e) != RT_SCENE_GLOBAL;   /* 0: no hybrid kernels */
+    if (const char *e = getenv("RT_AMD_BLOCKS_PER_CU")) ov.blocks_per_cu = atoi(e);
     const size_t blob_bytes = s->flat.blob.size() * sizeof(rt_f4);
     /* one spare stack entry: the traversal loop always writes the slot above the top */
     const size_t per_thread = s->flat.has_mesh ? (size_t)(s->flat.stack_entries + 1) * 8 : 0;
-    s->threads = 0;
+    const char *shape_err = nullptr;
     (void)hipSetDevice(ctx->device);
-    if (!s->flat.has_mesh) {
-        /* 256-thread workgroups (six per CU) unless the object list is so long that only one or two copies of it
-         * fit a CU's LDS: then the workgroup that keeps the most waves resident */
-        int best_waves = 0;
-        const int flat_candidates[4] = {256, 512, 768, 1024};
-        for (int nt : flat_candidates) {
-            if (blob_bytes > RT_LDS_LIMIT) break;
-            int nb = rt_kernel_blocks_per_cu(0, 1, nt, blob_bytes);
-            if (nb > RT_MAX_BLOCKS_PER_CU) nb = RT_MAX_BLOCKS_PER_CU;
-            if (nb < 1) nb = 1;
-            if (nb * (nt / 64) > best_waves) { best_waves = nb * (nt / 64); s->threads = nt; s->lds_bytes = blob_bytes; s->blocks_per_cu = nb; }
-        }
-    } else {
-        /* the shape with the most resident waves per CU (registers, LDS: every workgroup stages its own copy of the
-         * scene); the larger workgroup on a tie (fewer copies to stage) */
-        int best_waves = 0;
-        const int mesh_candidates[4] = {1024, 768, 512, 256};
-        const char *force_nt = getenv("RT_AMD_THREADS");            /* development: force the workgroup size */
-        if (force_nt) {
-            const int v = atoi(force_nt);
-            if (v != 256 && v != 512 && v != 768 && v != 1024) { delete s; return set_err(ctx, RT_ERR_INVALID, "RT_AMD_THREADS must be 256, 512, 768 or 1024"); }
-        }
-        for (int nt : mesh_candidates) {
-            if (force_nt && atoi(force_nt) != nt) continue;
-            const size_t lds = blob_bytes + per_thread * (size_t)nt;
-            if (lds > RT_LDS_LIMIT) continue;
-            int nb = rt_kernel_blocks_per_cu(1, 1, nt, lds);
-            if (nb > RT_MAX_BLOCKS_PER_CU) nb = RT_MAX_BLOCKS_PER_CU;
-            if (nb < 1) nb = 1;
-            if (nb * (nt / 64) > best_waves) { best_waves = nb * (nt / 64); s->threads = nt; s->lds_bytes = lds; s->blocks_per_cu = nb; }
-        }
-    }
-    s->scene_in_lds = RT_SCENE_LDS;
-    const char *force_mode = getenv("RT_AMD_SCENE_MODE");           /* development: 0 forces the all-global kernel for scenes that do not fit LDS */
-    if (s->threads == 0 && s->flat.has_mesh && !(force_mode && atoi(force_mode) == RT_SCENE_GLOBAL)) {
-        /* The triangles do not fit, but everything before them in the blob may: BVH nodes (a depth-10 tree has at most
-         * 1,023, whatever the triangle count), object records, object list.  Then only the triangles are read from global
-         * memory (L2).  Worth it while at least half a CU's wave slots stay filled. */
-        const size_t prefix_bytes = (size_t)s->flat.off_tris * sizeof(rt_f4);
-        int best_waves = 0;
-        const int hybrid_candidates[3] = {1024, 768, 512};
-        for (int nt : hybrid_candidates) {
-            const size_t lds = prefix_bytes + per_thread * (size_t)nt;
-            if (lds > RT_LDS_LIMIT) continue;
-            int nb = rt_kernel_blocks_per_cu(1, RT_SCENE_HYBRID, nt, lds);
-            if (nb > RT_MAX_BLOCKS_PER_CU) nb = RT_MAX_BLOCKS_PER_CU;
-            if (nb < 1) nb = 1;
-            if (nb * (nt / 64) > best_waves) { best_waves = nb * (nt / 64); s->threads = nt; s->lds_bytes = lds; s->blocks_per_cu = nb; }
-        }
-        if (s->threads) s->scene_in_lds = RT_SCENE_HYBRID;
-    }
-    if (s->threads == 0) {
-        /* larger than a CU's LDS: the kernel reads the scene from global memory (L2-resident),
-         * LDS holds only the traversal stacks */
-        s->scene_in_lds = RT_SCENE_GLOBAL;
-        s->threads = s->flat.has_mesh ? 1024 : 256;
-        /* (five or six waves per SIMD as 5-6 x 256 threads were measured on the 50,880- and 6,000-triangle scenes: 80.3 / 80.2 against
-         * 80.6 Msamples/s and 57.4 / 57.5 against 57.5 - the path is bound by the L1's address processing, not by latency:
-         * profiles/r04/experiments/big_mesh_global_5_waves.txt, pmc_vmem_sphere50k.txt) */
-        s->lds_bytes = per_thread * (size_t)s->threads;
-        if (s->lds_bytes > RT_LDS_LIMIT) {
-            delete s;
-            return set_err(ctx, RT_ERR_UNSUPPORTED, "BVH too deep for the per-lane LDS traversal stack");
-        }
-        /* (a 256-thread workgroup is admitted at most 6 times at this kernel's SGPR count, whatever the API says:
-         * MI355X_MICROARCH.md, residency; surplus workgroups would only queue behind the resident ones) */
-        int nb = rt_kernel_blocks_per_cu(s->flat.has_mesh ? 1 : 0, RT_SCENE_GLOBAL, s->threads, s->lds_bytes);
-        s->blocks_per_cu = nb < 1 ? 1 : (nb > RT_MAX_BLOCKS_PER_CU ? RT_MAX_BLOCKS_PER_CU : nb);
-    }
-    if (const char *e = getenv("RT_AMD_BLOCKS_PER_CU")) { int v = atoi(e); if (v >= 1 && v <= 8) s->blocks_per_cu = v; }
-    /* the occupancy probes above discard their errors: a failed probe must not surface later as a launch error */
+    const rt_status st = rt_sched::choose_shape(s->flat.has_mesh, blob_bytes, (size_t)s->flat.off_tris * sizeof(rt_f4), per_thread, ov,
+                                                rt_kernel_blocks_per_cu, s->kernel, &shape_err);
+    if (st != RT_OK) { delete s; return set_err(ctx, st, shape_err); }
+    /* the occupancy probes discard their errors: a failed probe must not surface later as a launch error */
     (void)hipGetLastError();
 
-    hipError_t e = hipMalloc((void **)&s->d_blob, blob_bytes > 0 ? blob_bytes : 16);
-    if (e == hipSuccess && blob_bytes) e = hipMemcpy(s->d_blob, s->flat.blob.data(), blob_bytes, hipMemcpyHostToDevice);
+    hipError_t e = s->d_blob.grow(s->flat.blob.size());
+    if (e == hipSuccess && blob_bytes) e = hipMemcpy(s->d_blob.p, s->flat.blob.data(), blob_bytes, hipMemcpyHostToDevice);
     const size_t obj_bytes = s->flat.objects.size() * sizeof(rt_object);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_objects, obj_bytes > 0 ? obj_bytes : 16);
-    if (e == hipSuccess && obj_bytes) e = hipMemcpy(s->d_objects, s->flat.objects.data(), obj_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = s->d_objects.grow(s->flat.objects.size());
+    if (e == hipSuccess && obj_bytes) e = hipMemcpy(s->d_objects.p, s->flat.objects.data(), obj_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && !s->flat.tri_uv.empty()) {
-        e = hipMalloc((void **)&s->d_tri_uv, s->flat.tri_uv.size() * 4);
-        if (e == hipSuccess) e = hipMemcpy(s->d_tri_uv, s->flat.tri_uv.data(), s->flat.tri_uv.size() * 4, hipMemcpyHostToDevice);
+        e = s->d_tri_uv.grow(s->flat.tri_uv.size());
+        if (e == hipSuccess) e = hipMemcpy(s->d_tri_uv.p, s->flat.tri_uv.data(), s->flat.tri_uv.size() * 4, hipMemcpyHostToDevice);
     }
     if (e == hipSuccess && !s->flat.tex_data.empty()) {
-        e = hipMalloc((void **)&s->d_tex, s->flat.tex_data.size() * 4);
-        if (e == hipSuccess) e = hipMemcpy(s->d_tex, s->flat.tex_data.data(), s->flat.tex_data.size() * 4, hipMemcpyHostToDevice);
+        e = s->d_tex.grow(s->flat.tex_data.size());
+        if (e == hipSuccess) e = hipMemcpy(s->d_tex.p, s->flat.tex_data.data(), s->flat.tex_data.size() * 4, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         rt_scene_destroy(s);
@@ -511,11 +443,7 @@ extern "C" void rt_scene_destroy(rt_scene *s)
 {
     if (!s) return;
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
-    if (s->d_blob) (void)hipFree(s->d_blob);
-    if (s->d_objects) (void)hipFree(s->d_objects);
-    if (s->d_tri_uv) (void)hipFree(s->d_tri_uv);
-    if (s->d_tex) (void)hipFree(s->d_tex);
-    delete s;
+    delete s;                            /* (the device buffers go with it) */
 }
 
 extern "C" rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *out)
@@ -524,11 +452,11 @@ extern "C" rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *out)
     out->num_objects = (int32_t)s->flat.objects.size();
     out->num_triangles = s->flat.num_tris;
     out->num_nodes = s->flat.num_nodes;
-    out->lds_bytes = (int32_t)s->lds_bytes;
-    out->scene_in_lds = s->scene_in_lds;
-    out->threads_per_block = s->threads;
+    out->lds_bytes = (int32_t)s->kernel.lds_bytes;
+    out->scene_in_lds = s->kernel.shape.mode;
+    out->threads_per_block = s->kernel.shape.threads;
     out->stack_entries = s->flat.stack_entries;
-    out->blocks_per_cu = s->blocks_per_cu;
+    out->blocks_per_cu = s->kernel.blocks_per_cu;
     return RT_OK;
 }
 
@@ -576,8 +504,8 @@ extern "C" int32_t rt_max_batch_frames(rt_ctx *ctx, int32_t width, int32_t heigh
 /* persistent waves: enough workgroups to fill the chip, each wave pulls 8x8 tiles */
 static int launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles)
 {
-    const int waves_per_block = scene->threads / 64;
-    int blocks = ctx->num_cus * scene->blocks_per_cu;
+    const int waves_per_block = scene->kernel.shape.threads / 64;
+    int blocks = ctx->num_cus * scene->kernel.blocks_per_cu;
     const int needed = (num_tiles + waves_per_block - 1) / waves_per_block;
     return blocks > needed ? needed : blocks;
 }
@@ -710,9 +638,9 @@ static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, cons
     a.num_tiles = L.num_tiles;
     a.tile_stride = rt_sched::coprime_stride((uint32_t)a.num_tiles);
 
-    a.objects = scene->d_objects;
+    a.objects = scene->d_objects.p;
     a.num_objects = (int32_t)scene->flat.objects.size();
-    a.blob = scene->d_blob;
+    a.blob = scene->d_blob.p;
     a.blob_f4 = (int32_t)scene->flat.blob.size();
     a.off_nodes = scene->flat.off_nodes;
     a.off_tris = scene->flat.off_tris;
@@ -724,13 +652,13 @@ static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, cons
     a.work_threshold = ctx->work_threshold;
     a.ready_break = ctx->ready_break;
     a.hit_break = ctx->hit_break;
-    const int mix_break = ctx->mix_break >= 0 ? ctx->mix_break : (scene->threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
+    const int mix_break = ctx->mix_break >= 0 ? ctx->mix_break : (scene->kernel.shape.threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
     a.hit_low = ctx->hit_low > 0 && mix_break > 0 ? ctx->hit_low : ctx->hit_break;
     a.mix_break = ctx->hit_low > 0 && mix_break > 0 ? mix_break : 1000;
     a.shade_batch = ctx->shade_batch;
     a.descend_keep = ctx->descend_keep;
-    a.tri_uv = scene->d_tri_uv;
-    a.tex_data = scene->d_tex;
+    a.tri_uv = scene->d_tri_uv.p;
+    a.tex_data = scene->d_tex.p;
     a.prev = d_prev;
     a.out = d_out;
     a.tile_counter = tile_counter;
@@ -856,7 +784,7 @@ static rt_status run_pilot(rt_ctx *ctx, const rt_scene *scene, const rt_kernel_a
     rt_status st = collect_costs(ctx, ap, stream);
     if (st != RT_OK) return st;
     RT_HIP(ctx, hipMemsetAsync(ap.tile_counter, 0, 512, stream), "clearing tile counter");
-    RT_HIP(ctx, rt_launch_render(&ap, scene->flat.has_mesh ? 1 : 0, scene->scene_in_lds, scene->threads, launch_blocks(ctx, scene, ap.num_tiles), scene->lds_bytes, stream),
+    RT_HIP(ctx, rt_launch_render(&ap, scene->kernel.shape, launch_blocks(ctx, scene, ap.num_tiles), scene->kernel.lds_bytes, stream),
            "launching the pilot");
     v.costs = Costs::on_device;
     v.cost_spp = 1;
@@ -954,9 +882,9 @@ static rt_status launch(rt_ctx *ctx, const rt_scene *scene, const rt_kernel_args
      * 1024 spp, 4 in flight: 286 ms per frame with full-size launches, 242 with quarter-size ones).
      * Only where a workgroup has its CU to itself (a mesh that fills the LDS): smaller workgroups of several launches share
      * CUs anyway, and full-size launches are then the faster ones (three-sphere 61.7 against 65.1 ms, cube 112.8 against 118.0). */
-    if (pipelined && scene->blocks_per_cu == 1) blocks = (blocks + ctx->pipe.depth - 1) / ctx->pipe.depth;
+    if (pipelined && scene->kernel.blocks_per_cu == 1) blocks = (blocks + ctx->pipe.depth - 1) / ctx->pipe.depth;
     RT_HIP(ctx, hipMemsetAsync(a.tile_counter, 0, 512, stream), "clearing tile counter");
-    RT_HIP(ctx, rt_launch_render(&a, scene->flat.has_mesh ? 1 : 0, scene->scene_in_lds, scene->threads, blocks, scene->lds_bytes, stream), "launching render kernel");
+    RT_HIP(ctx, rt_launch_render(&a, scene->kernel.shape, blocks, scene->kernel.lds_bytes, stream), "launching render kernel");
     return RT_OK;
 }
 

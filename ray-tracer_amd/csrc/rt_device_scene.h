@@ -36,12 +36,30 @@
 #define RT_SCENE_GLOBAL 0            /* every section from global memory; LDS holds only the traversal stacks */
 #define RT_SCENE_LDS 1               /* the whole blob staged into LDS */
 #define RT_SCENE_HYBRID 2            /* everything but the triangles in LDS, the triangles from global memory */
+/* A shape of the render kernel: rt_render_kernel<threads, has_mesh, mode>.  RT_SHAPES are the ones built (rt_kernel.hip
+ * instantiates exactly these), in the order a scene's shape is chosen from them (rt_sched::choose_shape): without a mesh
+ * the smaller workgroup first, with one the larger. */
+struct rt_shape {
+    int32_t has_mesh, mode, threads;
+    constexpr bool operator==(const rt_shape &o) const { return has_mesh == o.has_mesh && mode == o.mode && threads == o.threads; }
+};
+inline constexpr rt_shape RT_SHAPES[] = {
+    {0, RT_SCENE_LDS, 256}, {0, RT_SCENE_LDS, 512}, {0, RT_SCENE_LDS, 768}, {0, RT_SCENE_LDS, 1024},
+    {1, RT_SCENE_LDS, 1024}, {1, RT_SCENE_LDS, 768}, {1, RT_SCENE_LDS, 512}, {1, RT_SCENE_LDS, 256},
+    {1, RT_SCENE_HYBRID, 1024}, {1, RT_SCENE_HYBRID, 768}, {1, RT_SCENE_HYBRID, 512},
+    {0, RT_SCENE_GLOBAL, 256}, {1, RT_SCENE_GLOBAL, 1024},
+};
+/* a shape's index in RT_SHAPES, or -1 if it is not built */
+inline constexpr int rt_shape_index(rt_shape s)
+{
+    for (int i = 0; i < (int)(sizeof RT_SHAPES / sizeof RT_SHAPES[0]); i++)
+        if (RT_SHAPES[i] == s) return i;
+    return -1;
+}
 #define RT_STACK_ENTRIES RT_BVH_DEPTH /* at most one pending sibling per level below the root */
 #define RT_FRAME_BITS 5               /* a pixel keeps the index of its frame within the launch in this many bits */
 #define RT_MAX_BATCH_FRAMES (1 << RT_FRAME_BITS)   /* frames one launch can render */
-#ifndef RT_SMALL_WG_WAVES
 #define RT_SMALL_WG_WAVES 5            /* workgroups of fewer than 1024 threads are compiled for this many waves per SIMD (<= 96 VGPRs) */
-#endif
 /* Defaults of the render kernel's scheduling thresholds (lanes of a wave; see rt_kernel.hip; RT_AMD_* overrides them).
  * None of them changes an image.  Values: same-box sweeps over four scenes in the multi-frame regime,
  * profiles/r02/experiments/.  (Compiling them in as immediates instead of launch arguments was measured: no difference.) */

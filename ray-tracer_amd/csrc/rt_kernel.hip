@@ -45,6 +45,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <array>
+#include <iterator>
+#include <utility>
+
 #include "rt_pixel.h"
 
 /* LLVM integer-compare predicates for __builtin_amdgcn_uicmp / sicmp (lane mask of a compare, straight into an SGPR pair) */
@@ -534,33 +538,6 @@ static int rt_blocks_one(size_t lds_bytes)
     return n;
 }
 
-/* workgroups of this shape of rt_render_kernel that are resident on one CU (registers, LDS, wave slots), as the
- * runtime reports it; 0 if the shape is not built */
-extern "C" int rt_kernel_blocks_per_cu(int has_mesh, int scene_in_lds, int threads, size_t lds_bytes)
-{
-    if (scene_in_lds == RT_SCENE_GLOBAL) {
-        if (has_mesh && threads == 1024) return rt_blocks_one<1024, true, RT_SCENE_GLOBAL>(lds_bytes);
-        if (!has_mesh && threads == 256) return rt_blocks_one<256, false, RT_SCENE_GLOBAL>(lds_bytes);
-        return 0;
-    }
-    if (scene_in_lds == RT_SCENE_HYBRID) {
-        if (!has_mesh) return 0;
-        switch (threads) {
-            case 512: return rt_blocks_one<512, true, RT_SCENE_HYBRID>(lds_bytes);
-            case 768: return rt_blocks_one<768, true, RT_SCENE_HYBRID>(lds_bytes);
-            case 1024: return rt_blocks_one<1024, true, RT_SCENE_HYBRID>(lds_bytes);
-            default: return 0;
-        }
-    }
-    switch (threads) {
-        case 256: return has_mesh ? rt_blocks_one<256, true, RT_SCENE_LDS>(lds_bytes) : rt_blocks_one<256, false, RT_SCENE_LDS>(lds_bytes);
-        case 512: return has_mesh ? rt_blocks_one<512, true, RT_SCENE_LDS>(lds_bytes) : rt_blocks_one<512, false, RT_SCENE_LDS>(lds_bytes);
-        case 768: return has_mesh ? rt_blocks_one<768, true, RT_SCENE_LDS>(lds_bytes) : rt_blocks_one<768, false, RT_SCENE_LDS>(lds_bytes);
-        case 1024: return has_mesh ? rt_blocks_one<1024, true, RT_SCENE_LDS>(lds_bytes) : rt_blocks_one<1024, false, RT_SCENE_LDS>(lds_bytes);
-        default: return 0;
-    }
-}
-
 template <int NT, bool HAS_MESH, int MODE>
 static void rt_launch_one(const rt_kernel_args *args, int blocks, size_t lds_bytes, hipStream_t stream)
 {
@@ -568,38 +545,31 @@ static void rt_launch_one(const rt_kernel_args *args, int blocks, size_t lds_byt
     hipLaunchKernelGGL((rt_render_kernel<NT, HAS_MESH, MODE>), dim3(blocks), dim3(NT), lds_bytes, stream, *args);
 }
 
-extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, int has_mesh, int scene_in_lds, int threads, int blocks, size_t lds_bytes, hipStream_t stream)
+/* the occupancy probe and the launcher of every built shape, in RT_SHAPES' order: the kernel is instantiated from that list alone */
+struct rt_shape_fns {
+    int (*blocks)(size_t lds_bytes);
+    void (*launch)(const rt_kernel_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
+};
+template <size_t... I> static constexpr std::array<rt_shape_fns, sizeof...(I)> rt_shape_fns_of(std::index_sequence<I...>)
 {
-    if (scene_in_lds == RT_SCENE_GLOBAL) {
-        /* global-memory scene: one shape per mesh flag is enough */
-        if (has_mesh && threads == 1024) rt_launch_one<1024, true, RT_SCENE_GLOBAL>(args, blocks, lds_bytes, stream);
-        else if (!has_mesh && threads == 256) rt_launch_one<256, false, RT_SCENE_GLOBAL>(args, blocks, lds_bytes, stream);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (scene_in_lds == RT_SCENE_HYBRID) {
-        if (!has_mesh) return hipErrorInvalidValue;
-        switch (threads) {
-            case 512: rt_launch_one<512, true, RT_SCENE_HYBRID>(args, blocks, lds_bytes, stream); break;
-            case 768: rt_launch_one<768, true, RT_SCENE_HYBRID>(args, blocks, lds_bytes, stream); break;
-            case 1024: rt_launch_one<1024, true, RT_SCENE_HYBRID>(args, blocks, lds_bytes, stream); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-#define RT_CASE(NTV)                                                                                   \
-    case NTV:                                                                                          \
-        if (has_mesh) rt_launch_one<NTV, true, RT_SCENE_LDS>(args, blocks, lds_bytes, stream);         \
-        else rt_launch_one<NTV, false, RT_SCENE_LDS>(args, blocks, lds_bytes, stream);                 \
-        break;
-    switch (threads) {
-        RT_CASE(256)
-        RT_CASE(512)
-        RT_CASE(768)
-        RT_CASE(1024)
-        default: return hipErrorInvalidValue;
-    }
-#undef RT_CASE
+    return {{{rt_blocks_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
+              rt_launch_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>}...}};
+}
+static constexpr auto rt_shape_table = rt_shape_fns_of(std::make_index_sequence<std::size(RT_SHAPES)>());
+
+/* workgroups of this shape of rt_render_kernel that are resident on one CU (registers, LDS, wave slots), as the
+ * runtime reports it; 0 if the shape is not built */
+extern "C" int rt_kernel_blocks_per_cu(rt_shape shape, size_t lds_bytes)
+{
+    const int i = rt_shape_index(shape);
+    return i < 0 ? 0 : rt_shape_table[i].blocks(lds_bytes);
+}
+
+extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream)
+{
+    const int i = rt_shape_index(shape);
+    if (i < 0) return hipErrorInvalidValue;
+    rt_shape_table[i].launch(args, blocks, lds_bytes, stream);
     return hipGetLastError();
 }
 

@@ -35,11 +35,7 @@
 #define RT_HD static inline
 #endif
 
-#ifdef RT_MATH_NO_FMA        /* A/B builds only (tools/build_variants.py): the unfused forms, round 3's functions exactly */
-#define RT_FMAF(a, b, c) ((a) * (b) + (c))
-#else
 #define RT_FMAF(a, b, c) __builtin_fmaf((a), (b), (c))
-#endif
 
 RT_HD uint32_t rt_f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 RT_HD float rt_u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
@@ -284,19 +280,13 @@ RT_HD double rt__asin_series(double x)
     return x * p;
 }
 
-#if defined(__HIPCC__)
-#define RT_SQRT_F64(x) __builtin_sqrt(x)
-#else
-#define RT_SQRT_F64(x) __builtin_sqrt(x)
-#endif
-
 RT_HD double rt_asin(double x)
 {
     const double PIO2_HI = 1.5707963267948966, PIO2_LO = 6.123233995736766e-17;
     const double ax = x < 0 ? -x : x;
     if (!(ax <= 1.0)) return (x - x) / (x - x);                 /* |x| > 1 or NaN -> NaN */
     if (ax <= 0.5) return rt__asin_series(x);
-    const double s = RT_SQRT_F64((1.0 - ax) * 0.5);
+    const double s = __builtin_sqrt((1.0 - ax) * 0.5);
     const double r = (PIO2_HI - 2.0 * rt__asin_series(s)) + PIO2_LO;
     return x < 0 ? -r : r;
 }
@@ -307,7 +297,7 @@ RT_HD double rt_acos(double x)
     const double ax = x < 0 ? -x : x;
     if (!(ax <= 1.0)) return (x - x) / (x - x);
     if (ax <= 0.5) return (PIO2_HI - rt__asin_series(x)) + PIO2_LO;
-    const double s = RT_SQRT_F64((1.0 - ax) * 0.5);
+    const double s = __builtin_sqrt((1.0 - ax) * 0.5);
     const double t = 2.0 * rt__asin_series(s);
     return x > 0 ? t : (2.0 * PIO2_HI - t) + 2.0 * PIO2_LO;
 }

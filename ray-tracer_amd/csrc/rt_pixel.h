@@ -25,7 +25,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
  * The compiler expands `1.0f / x` into 11 instructions (v_div_scale x 2, v_rcp, five fma, v_div_fmas, v_div_fixup) and sqrtf
  * into 17 + 5 s_nop, most of it for inputs a renderer never sees: denormals, results that underflow, zero, infinity.  On gfx950
  *   v_rcp_f32 + one Newton step (two fma)                is 1.0f / x bit for bit for every x with 2^-126 <= |x| <= 2^126,
- *   v_sqrt_f32 + the -1 / +1 ulp residual test (2 fma)   is sqrtf(x) bit for bit for every x with 2^-64 <= x < inf,
+ *   v_rsq_f32 + two multiplies + one residual step (2 fma) is sqrtf(x) bit for bit for every x with 2^-64 <= x < inf,
  * checked EXHAUSTIVELY - all 2^32 inputs against the compiler's expansions on the device, tests/test_gpu_math.py
  * (tools/ubench/exact_div_sqrt.hip, profiles/r04/experiments/exact_div_sqrt.txt: outside those ranges every single input fails,
  * inside none).  rt_sqrt / rt_rcp_sqrt take the short forms when EVERY active lane's operand is inside the range (one subtract,
@@ -43,21 +43,13 @@ __device__ __forceinline__ float rt_rcp_short(float x)
  * s0 + (x - s0^2) * (rsq / 2) with the residual as an fma lands on the correctly rounded value for EVERY binary32 from 2^-102 up
  * (tools/ubench/rsq_forms.hip on the device; tests/test_gpu_math.py's exhaustive test runs this very function against sqrtf over
  * all 2^32 patterns).  Five instructions - v_rsq_f32, two multiplies, two fma - where round 4's first form (v_sqrt_f32, then a
- * residual test of the neighbours one ulp down and up: RT_SQRT_BY_NEIGHBOURS keeps it for A/B builds) took nine, four of them
- * compares and selects. */
+ * residual test of the neighbours one ulp down and up) took nine, four of them compares and selects
+ * (profiles/r04/experiments/sqrt_from_rsq.txt). */
 __device__ __forceinline__ float rt_sqrt_short(float x)
 {
-#ifdef RT_SQRT_BY_NEIGHBOURS
-    float s = __builtin_amdgcn_sqrtf(x);
-    const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
-    const float rdn = __builtin_fmaf(-dn, s, x), rup = __builtin_fmaf(-up, s, x);
-    s = rdn <= 0.0f ? dn : s;
-    return rup > 0.0f ? up : s;
-#else
     const float y = __builtin_amdgcn_rsqf(x);
     const float s0 = x * y, h = 0.5f * y;
     return __builtin_fmaf(__builtin_fmaf(-s0, s0, x), h, s0);
-#endif
 }
 __device__ __forceinline__ float rt_sqrt(float x)       /* == sqrtf(x) */
 {
@@ -99,18 +91,14 @@ template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS>
 __device__ __forceinline__ float normal_num(uint32_t &state)
 {
     float theta = rt_theta(rt_pcg_next(&state));
-#ifdef RT_GENERIC_BOX_MULLER       /* (A/B builds: the general-purpose log and cos) */
-    float rho = rt_sqrt(-2.0f * rt_logf(rt_u01(rt_pcg_next(&state))));
-    return rho * rt_cosf(theta);
-#else
     if (GENERAL_FUNCTIONS) {         /* (the hybrid kernels: see px_shade) */
         float rho_g = rt_sqrt(-2.0f * rt_logf(rt_u01(rt_pcg_next(&state))));
         return rho_g * rt_cosf(theta);
     }
-    /* log on [0, 1] and cos on [0, 6.28318]: rt_logf / rt_cosf without the cases these arguments cannot be (rt_math.h) */
+    /* log on [0, 1] and cos on [0, 6.28318]: rt_logf / rt_cosf without the cases these arguments cannot be (rt_math.h; the
+     * general-purpose pair everywhere was measured against it: profiles/r04/experiments/box_muller_on_its_domain.txt) */
     float rho = rt_sqrt(-2.0f * rt_logf_0_1(rt_u01(rt_pcg_next(&state)), SHORT_DIVIDE ? 1 : 0));
     return rho * rt_cosf_0_2pi(theta);
-#endif
 }
 
 /* the scene sections (LDS, or global memory for what of a large scene does not fit a CU's LDS) */
@@ -668,9 +656,6 @@ __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds
                 float qc = dot(cq, cq) - ob.v[3] * ob.v[3];
                 float disc = qb * qb - 4.0f * qa * qc;
                 if (disc >= 0.0f) {
-#if defined(RT_SPHERE_IEEE_DIVIDE)
-                    float dist = (-qb - rt_sqrt(disc)) / (2.0f * qa);
-#else
                     /* The near root's division in its short form (rt_math.h rt__div_benign).  d comes out of normalised(): a unit vector to a
                      * few ulp, so the divisor is 2 to a few ulp - or d has a NaN (divisor NaN: the quotient is NaN either way), or it is the
                      * zero vector (a vector whose squared length overflowed: then b and the dividend are zeros too and both forms give
@@ -678,9 +663,9 @@ __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds
                      * or infinite - it may return another value than the operator, but never one that changes what follows: such a quotient is
                      * below RT_EPS_F (rejected), or - an infinite dividend: inf from the operator, NaN from the short form - fails
                      * `dist > RT_EPS_F` or `t <= best_t` (best_t <= 2^30) alike; every distance that IS accepted comes from a dividend between
-                     * 2e-6 and 2^31, where the two agree bit for bit. */
+                     * 2e-6 and 2^31, where the two agree bit for bit.  The operator's form, should parity ever need it, is
+                     * `float dist = (-qb - rt_sqrt(disc)) / (2.0f * qa);` (profiles/r04/experiments/sphere_divide.txt). */
                     float dist = rt__div_benign(-qb - rt_sqrt(disc), 2.0f * qa);
-#endif
                     if (dist > RT_EPS_F) { hit = true; t = dist; }
                 }
                 break;

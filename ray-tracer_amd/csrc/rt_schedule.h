@@ -1,14 +1,17 @@
 /*
- * rt_schedule.h — the host arithmetic of the render schedule: which tiles a launch renders, where their pixels go, in which
- * order its waves take them, and which rank of a multi-GPU call renders which.  Plain functions of vectors and scalars;
- * no HIP.  Any order renders the same image: the schedule only decides how long a launch takes ("Multi-frame
- * launches and their schedule").  A tile is 8 x 8 pixels; "local tile" t of a launch is its t-th, image tile tiles[t].
+ * rt_schedule.h — the host arithmetic of the render schedule: which kernel shape a scene runs, which tiles a launch renders,
+ * where their pixels go, in which order its waves take them, and which rank of a multi-GPU call renders which.  Plain
+ * functions of vectors and scalars; no HIP.  Any order renders the same image: the schedule only decides how long a launch
+ * takes ("Multi-frame launches and their schedule").  A tile is 8 x 8 pixels; "local tile" t of a launch is its
+ * t-th, image tile tiles[t].
  * Header only: rt_capi.cpp, and the host-only sanitizer build of it, need nothing else to link.
  */
 #pragma once
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
+#include <iterator>
 #include <vector>
 
 #include "rt_amd.h"
@@ -188,6 +191,74 @@ inline void build_job_order(const std::vector<uint32_t> &order, const std::vecto
     for (uint32_t r = 0; r < top; r++) taken[idx[r]] = 1;
     for (uint32_t f = 0; f < frames; f++)
         for (uint32_t t : order) if (!taken[t]) jobs.push_back(t | (f << RT_JOB_FRAME_SHIFT));
+}
+
+#define RT_LDS_LIMIT 163840   /* 160 KiB per CU / per workgroup on gfx950 */
+#define RT_MAX_BLOCKS_PER_CU 6
+
+/* The development overrides of a scene's kernel shape, as read from the environment */
+struct ShapeOverrides {
+    bool threads_set = false;
+    int threads = 0;              /* RT_AMD_THREADS: the workgroup size of a mesh scene in LDS (256, 512, 768 or 1024) */
+    bool hybrid = true;           /* RT_AMD_SCENE_MODE=0 turns the hybrid kernels off */
+    int blocks_per_cu = 0;        /* RT_AMD_BLOCKS_PER_CU: replaces the probed figure when 1..8 */
+};
+
+/* the kernel shape a scene runs, the dynamic LDS it launches with, and how many of its workgroups are resident on a CU */
+struct KernelShape {
+    rt_shape shape{};
+    size_t lds_bytes = 0;
+    int blocks_per_cu = 1;
+};
+
+/* The kernel shape of a scene with a blob of blob_bytes, the first prefix_bytes of it before the triangles, and per_thread
+ * bytes of traversal stack per lane (0 without a mesh).  probe(shape, lds_bytes) is the runtime's count of resident
+ * workgroups, clamped to [1, RT_MAX_BLOCKS_PER_CU] here; it is called for the candidates in RT_SHAPES' order.  On an error
+ * returns its status and sets *err.
+ *   The whole scene in LDS (every workgroup stages its own copy) when a shape fits: the one with the most resident waves per
+ *   CU, on a tie the earlier one of RT_SHAPES - the smaller workgroup without a mesh (six 256-thread workgroups unless the
+ *   object list is so long that only one or two copies fit), the larger with one (fewer copies to stage).
+ *   Else, for a mesh, everything before the triangles in LDS when that fits (a depth-10 tree is at most 1,023 nodes whatever
+ *   the triangle count), the triangles from global memory: worth it while at least half a CU's wave slots stay filled.
+ *   Else the scene in global memory (L2-resident), LDS holding only the traversal stacks. */
+template <class Probe>
+inline rt_status choose_shape(bool has_mesh, size_t blob_bytes, size_t prefix_bytes, size_t per_thread, const ShapeOverrides &o, Probe &&probe,
+                              KernelShape &out, const char **err)
+{
+    if (has_mesh && o.threads_set && o.threads != 256 && o.threads != 512 && o.threads != 768 && o.threads != 1024) {
+        *err = "RT_AMD_THREADS must be 256, 512, 768 or 1024";
+        return RT_ERR_INVALID;
+    }
+    auto blocks = [&](rt_shape s, size_t lds) { return std::min(std::max(probe(s, lds), 1), RT_MAX_BLOCKS_PER_CU); };
+    auto best_of = [&](int mode, size_t scene_bytes) {
+        int best_waves = 0;
+        for (const rt_shape &s : RT_SHAPES) {
+            if (s.has_mesh != (int)has_mesh || s.mode != mode) continue;
+            if (mode == RT_SCENE_LDS && has_mesh && o.threads_set && o.threads != s.threads) continue;
+            const size_t lds = scene_bytes + per_thread * (size_t)s.threads;
+            if (lds > RT_LDS_LIMIT) continue;
+            const int nb = blocks(s, lds);
+            if (nb * (s.threads / 64) > best_waves) { best_waves = nb * (s.threads / 64); out = {s, lds, nb}; }
+        }
+        return best_waves > 0;
+    };
+    if (!best_of(RT_SCENE_LDS, blob_bytes) && !(o.hybrid && best_of(RT_SCENE_HYBRID, prefix_bytes))) {   /* (hybrid shapes have a mesh) */
+        /* (one global shape per mesh flag: five or six waves per SIMD as 5-6 x 256 threads were measured on the 50,880- and
+         * 6,000-triangle scenes: 80.3 / 80.2 against 80.6 Msamples/s and 57.4 / 57.5 against 57.5 - the path is bound by the
+         * L1's address processing, not by latency: profiles/r04/experiments/big_mesh_global_5_waves.txt, pmc_vmem_sphere50k.txt) */
+        const rt_shape s = *std::find_if(std::begin(RT_SHAPES), std::end(RT_SHAPES),
+                                         [&](const rt_shape &t) { return t.has_mesh == (int)has_mesh && t.mode == RT_SCENE_GLOBAL; });
+        const size_t lds = per_thread * (size_t)s.threads;
+        if (lds > RT_LDS_LIMIT) {
+            *err = "BVH too deep for the per-lane LDS traversal stack";
+            return RT_ERR_UNSUPPORTED;
+        }
+        /* (a 256-thread workgroup is admitted at most 6 times at this kernel's SGPR count, whatever the API says:
+         * MI355X_MICROARCH.md, residency; surplus workgroups would only queue behind the resident ones) */
+        out = {s, lds, blocks(s, lds)};
+    }
+    if (o.blocks_per_cu >= 1 && o.blocks_per_cu <= 8) out.blocks_per_cu = o.blocks_per_cu;
+    return RT_OK;
 }
 
 /* rt_partition_tiles' owner table dealt out per rank: its tiles (ascending image indices) and, with cost and peak

@@ -1,7 +1,7 @@
 // The GPU-free entry points of rt_capi.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; test infrastructure):
-// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule and the output layout
-// (rt_schedule.h) with their properties asserted, and every entry point's refusal of null / bad arguments before it touches
-// HIP.  rt_capi.cpp is compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
+// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule, the output layout and
+// the kernel shape choice (rt_schedule.h) with their properties asserted, and every entry point's refusal of null / bad
+// arguments before it touches HIP.  rt_capi.cpp is compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
 // kernel launchers (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
 #include <algorithm>
 #include <cmath>
@@ -18,8 +18,8 @@
 #include "rt_device_scene.h"
 #include "rt_schedule.h"
 
-extern "C" hipError_t rt_launch_render(const rt_kernel_args *, int, int, int, int, size_t, hipStream_t) { return hipErrorUnknown; }
-extern "C" int rt_kernel_blocks_per_cu(int, int, int, size_t) { return 1; }
+extern "C" hipError_t rt_launch_render(const rt_kernel_args *, rt_shape, int, size_t, hipStream_t) { return hipErrorUnknown; }
+extern "C" int rt_kernel_blocks_per_cu(rt_shape, size_t) { return 1; }
 extern "C" hipError_t rt_launch_blend(const float *, long long, int, int, float *, long long, hipStream_t) { return hipErrorUnknown; }
 extern "C" hipError_t rt_launch_blend_tiles(const float *, long long, int, int, float *, const uint32_t *, int, int, int, int, hipStream_t) { return hipErrorUnknown; }
 extern "C" hipError_t rt_launch_tiles_copy(float *, float *, const uint32_t *, int, int, int, int, int, hipStream_t) { return hipErrorUnknown; }
@@ -248,6 +248,73 @@ template <class Rng> static bool check_schedule(Rng &rng)
     return true;
 }
 
+/* rt_sched::choose_shape with a fake occupancy probe on random scene sizes and overrides: the shape is built and its LDS fits;
+ * blocks per CU are the clamped probe or the override; within the chosen mode no candidate keeps more waves resident and a tie
+ * goes to the smaller workgroup without a mesh, the larger with one; the mode is LDS, then hybrid, then global; the two errors */
+template <class Rng> static bool check_shape(Rng &rng)
+{
+    auto irand = [&](long long lo, long long hi) { return (long long)std::uniform_int_distribution<long long>(lo, hi)(rng); };
+    const int n_shapes = (int)(sizeof RT_SHAPES / sizeof RT_SHAPES[0]);
+    int probe_table[sizeof RT_SHAPES / sizeof RT_SHAPES[0]][4];
+    for (auto &row : probe_table) for (int &v : row) v = (int)irand(-1, 9);
+    auto probe_of = [&](rt_shape s, size_t lds) { return probe_table[rt_shape_index(s)][(lds >> 12) & 3]; };
+    auto blocks_of = [&](rt_shape s, size_t lds) { return std::min(std::max(probe_of(s, lds), 1), RT_MAX_BLOCKS_PER_CU); };
+    const bool mesh = irand(0, 2) != 0;
+    const size_t per_thread = mesh ? (size_t)irand(2, 27) * 8 : 0;
+    const size_t blob = (size_t)std::max(0ll, irand(0, 1) ? irand(0, 2 * RT_LDS_LIMIT) : RT_LDS_LIMIT + irand(-8192, 4096)) & ~(size_t)15;
+    const size_t prefix = (size_t)irand(0, (long long)blob) & ~(size_t)15;
+    rt_sched::ShapeOverrides o;
+    const int forced[] = {256, 512, 768, 1024, 0, 300};
+    if (irand(0, 3) == 0) { o.threads_set = true; o.threads = forced[irand(0, 5)]; }
+    o.hybrid = irand(0, 3) != 0;
+    o.blocks_per_cu = irand(0, 2) == 0 ? (int)irand(-1, 10) : 0;
+    std::vector<int> calls;
+    rt_sched::KernelShape k;
+    const char *err = nullptr;
+    const rt_status st = rt_sched::choose_shape(mesh, blob, prefix, per_thread, o, [&](rt_shape s, size_t lds) {
+        calls.push_back(rt_shape_index(s));
+        return probe_of(s, lds);
+    }, k, &err);
+    for (size_t i = 1; i < calls.size(); i++) CHECK(calls[i - 1] < calls[i], "shape: probes out of RT_SHAPES' order");
+    const bool bad_threads = mesh && o.threads_set && o.threads != 256 && o.threads != 512 && o.threads != 768 && o.threads != 1024;
+    CHECK((st == RT_ERR_INVALID) == bad_threads, "shape: RT_AMD_THREADS refused iff invalid for a mesh scene");
+    if (bad_threads) {
+        CHECK(calls.empty() && err, "shape: probed before refusing RT_AMD_THREADS");
+        return true;
+    }
+    /* the candidates of a mode: base LDS bytes, and whether a shape takes part */
+    auto base_of = [&](int mode) { return mode == RT_SCENE_LDS ? blob : mode == RT_SCENE_HYBRID ? prefix : (size_t)0; };
+    auto candidate = [&](const rt_shape &s, int mode) {
+        return s.has_mesh == (int)mesh && s.mode == mode && base_of(mode) + per_thread * (size_t)s.threads <= RT_LDS_LIMIT &&
+               !(mode == RT_SCENE_LDS && mesh && o.threads_set && o.threads != s.threads) && (mode != RT_SCENE_HYBRID || o.hybrid);
+    };
+    auto any_of_mode = [&](int mode) { for (const rt_shape &s : RT_SHAPES) if (candidate(s, mode)) return true; return false; };
+    const int want_mode = any_of_mode(RT_SCENE_LDS) ? RT_SCENE_LDS : any_of_mode(RT_SCENE_HYBRID) ? RT_SCENE_HYBRID : RT_SCENE_GLOBAL;
+    const bool too_deep = want_mode == RT_SCENE_GLOBAL && per_thread * (mesh ? 1024 : 256) > RT_LDS_LIMIT;
+    CHECK((st == RT_ERR_UNSUPPORTED) == too_deep, "shape: BVH too deep iff the global kernel's stacks do not fit");
+    if (too_deep) {
+        CHECK(err, "shape: no message");
+        return true;
+    }
+    CHECK(st == RT_OK, "shape: status");
+    const int ki = rt_shape_index(k.shape);
+    CHECK(ki >= 0 && ki < n_shapes && k.shape.has_mesh == (int)mesh, "shape: not a built shape of the scene's mesh flag");
+    CHECK(k.shape.mode == want_mode, "shape: fallback order LDS, hybrid, global");
+    CHECK(k.lds_bytes == base_of(want_mode) + per_thread * (size_t)k.shape.threads && k.lds_bytes <= RT_LDS_LIMIT, "shape: LDS bytes");
+    const bool overridden = o.blocks_per_cu >= 1 && o.blocks_per_cu <= 8;
+    CHECK(k.blocks_per_cu == (overridden ? o.blocks_per_cu : blocks_of(k.shape, k.lds_bytes)), "shape: blocks per CU");
+    CHECK(overridden || (k.blocks_per_cu >= 1 && k.blocks_per_cu <= RT_MAX_BLOCKS_PER_CU), "shape: blocks per CU out of [1, 6]");
+    if (want_mode == RT_SCENE_GLOBAL) return true;
+    const int waves = blocks_of(k.shape, k.lds_bytes) * k.shape.threads / 64;
+    for (const rt_shape &s : RT_SHAPES) {
+        if (!candidate(s, want_mode)) continue;
+        const int w = blocks_of(s, base_of(want_mode) + per_thread * (size_t)s.threads) * s.threads / 64;
+        CHECK(w <= waves, "shape: a candidate keeps more waves resident");
+        CHECK(w < waves || s.threads == k.shape.threads || (mesh ? s.threads < k.shape.threads : s.threads > k.shape.threads), "shape: tie rule");
+    }
+    return true;
+}
+
 /* rt_partition_tiles' owner table dealt out: a partition of the image's tiles, with each tile's cost and peak */
 static bool check_deal(const std::vector<int32_t> &owner, int n_ranks, const std::vector<uint32_t> &cost, const std::vector<uint32_t> &peak)
 {
@@ -293,7 +360,7 @@ int main(int argc, char **argv)
             for (auto &x : pk) x = (uint32_t)irand(0, 1000);
             if (!check_deal(own, n, cs, pk)) return 1;
         }
-        if (!check_schedule(rng)) return 1;
+        if (!check_schedule(rng) || !check_shape(rng)) return 1;
         rt_tile_spec ts;
         std::memset(&ts, 0, sizeof ts);
         ts.band_rows = (int32_t)irand(-8, 64); ts.band_first = (int32_t)irand(-1, 5); ts.band_stride = (int32_t)irand(-1, 5);
@@ -331,6 +398,6 @@ int main(int argc, char **argv)
     (void)rt_peer_access(nullptr, nullptr);
     (void)rt_scene_commit(nullptr, nullptr, nullptr);
     (void)rt_scene_get_info(nullptr, nullptr);
-    std::printf("capi host fuzz: %d partitions and deals, %d schedules, sanitizers silent\n", cases, cases);
+    std::printf("capi host fuzz: %d partitions and deals, %d schedules, %d kernel shapes, sanitizers silent\n", cases, cases, cases);
     return 0;
 }

@@ -43,7 +43,7 @@ def kernel_notes(rt, tmp_path):
 def test_render_kernel_register_budget(rt, tmp_path):
     notes = kernel_notes(rt, tmp_path)
     render = {n: v for n, v in notes.items() if "rt_render_kernel" in n}
-    # every instantiation the launcher can pick (rt_kernel.hip rt_launch_render): NT x HAS_MESH for LDS scenes, three hybrid
+    # every instantiation the launcher can pick (RT_SHAPES, rt_device_scene.h): NT x HAS_MESH for LDS scenes, three hybrid
     # shapes (BVH in LDS, triangles from L2) and two all-global ones
     assert len(render) == 13, sorted(render)
     report = []
