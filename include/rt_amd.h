@@ -314,6 +314,53 @@ rt_status rt_last_kernel_ms(rt_ctx *ctx, float *ms);
  * asynchronous device-buffer entry points. */
 rt_status rt_ctx_synchronize(rt_ctx *ctx);
 
+/* ---- closest-hit ray queries and first-hit planes ------------------------------------------------
+ * What get_ray_collision (src/raytracer.cu:24-46) answers for one ray, for n rays at once, with the hit written out instead
+ * of shaded: picking, focus, visibility and collision probes need a closest hit and no path.  The rules are the render
+ * kernel's (objects in list order, the later one wins a tie; one-way quads; the BVH meshes), the bits are the reference
+ * algorithm's (tests/test_gpu_query.py: equal to the CPU oracle's orc_trace_one as uint32, not to a tolerance).
+ * The ray is taken as given (Ray::change_direction src/ray.cu:198-202): the direction is NOT normalised and the distance is in
+ * units of its length; a direction with a NaN component hits nothing. */
+typedef struct rt_hit {
+    float t;               /* distance along the ray; RT_HIT_MISS_T for a miss */
+    float point[3];        /* direction * t + origin (Ray::get_pos src/ray.cu:63-65) */
+    float normal[3];       /* the shading normal: sphere normalised(point - centre) (src/objects.cu:66); triangle its unit normal, negated when it faces along the ray (:158) */
+    int32_t object;        /* index in the scene's object list (call order of rt_scene_add_*); -1: a miss */
+    int32_t triangle;      /* index of the triangle in the flattened scene (rt_debug_flatten order); -1 for a sphere or a miss */
+    float u, v;            /* texture coordinates when the object's material needs them (rt_material.need_uv; src/objects.cu:82-97, :196-199), else 0 */
+    int32_t reserved;      /* 0 */
+} rt_hit;                  /* 48 bytes.  A miss is {RT_HIT_MISS_T, {0,0,0}, {0,0,0}, -1, -1, 0, 0, 0} bit for bit */
+#define RT_HIT_MISS_T 1073741824.0f   /* the reference's "infinity", `1 << 31 - 1` == 1 << 30 (src/objects.cu:6) */
+
+/* Device-buffer form: d_origins, d_directions (n x 3 floats each) and d_hits (n records, 16-byte aligned) are device memory of
+ * ctx's GPU; asynchronous on hip_stream and ordered like rt_render_device (one launch in flight per context).  n == 0 succeeds
+ * and touches nothing; n < 0, n > 2^30, a null pointer with n > 0, a misaligned d_hits and a scene committed on another context
+ * are RT_ERR_INVALID.  rt_last_kernel_ms then reports the query kernel.  The grid grows with n (a wave per 64 rays, up to every
+ * CU filled): a few rays stage the scene into LDS once, not once per CU. */
+rt_status rt_trace_rays_device(rt_ctx *ctx, const rt_scene *scene, const float *d_origins, const float *d_directions, int64_t n,
+                               rt_hit *d_hits, void *hip_stream);
+/* Host-buffer form: uploads the rays, traces, downloads the records and returns when they are in `hits` (the context keeps the
+ * device buffers). */
+rt_status rt_trace_rays(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions, int64_t n, rt_hit *hits);
+
+/* The first-hit planes of a view (what a denoiser, an edge-aware filter or a compositor wants beside the colour): for every pixel
+ * the renderer's primary ray with antialiasing off (normalised((tl_pixel_pos + (delta_u * px + delta_v * py)) - cam_pos),
+ * src/camera.cu:24-29, src/raytracer.cu:123-127), its closest hit, and the planes below in rt_render's full-frame row-major
+ * layout.  Every plane is optional: a NULL pointer is not written; all NULL is RT_ERR_INVALID.
+ *   depth   W*H   floats   rt_hit.t                                                          miss: RT_HIT_MISS_T
+ *   normal  W*H*3 floats   rt_hit.normal                                                     miss: 0, 0, 0
+ *   albedo  W*H*3 floats   what trace_ray (src/raytracer.cu:86-90) does with the first hit:  miss: sky_colour
+ *                          the material's texture colour at (u, v) that multiplies the
+ *                          throughput; for an emissive material the emitted light it adds
+ *   object  W*H   int32    rt_hit.object                                                     miss: -1
+ *   ray     W*H*3 floats   the primary direction itself (origin cam_pos): rt_trace_rays on these rays gives these planes
+ * Device-buffer form: the planes are device memory; asynchronous on hip_stream like rt_render_device. */
+rt_status rt_render_aov_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float sky_colour[3],
+                               float *d_depth, float *d_normal, float *d_albedo, int32_t *d_object, float *d_ray, void *hip_stream);
+/* Host-buffer form: returns when the requested planes are in host memory. */
+rt_status rt_render_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float sky_colour[3],
+                        float *depth, float *normal, float *albedo, int32_t *object, float *ray);
+
 /* ---- several GPUs of one node from one host thread ---------------------------------------------
  * What run_ray_tracer (src/dispatch.cu:127-153) does on one device, n devices do for the bands they
  * own: rank i of n_ranks renders the bands b with b % n_ranks == i (a pixel depends

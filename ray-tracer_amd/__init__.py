@@ -66,6 +66,12 @@ class rt_flat_view(C.Structure):
                 ("num_triangles", C.c_int32), ("num_nodes", C.c_int32), ("has_mesh", C.c_int32)]
 
 
+# rt_hit (include/rt_amd.h) as a NumPy record: what trace_rays returns
+HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal", np.float32, (3,)), ("object", np.int32),
+                      ("triangle", np.int32), ("u", np.float32), ("v", np.float32), ("reserved", np.int32)])
+HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
+AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
+
 # every symbol include/rt_amd.h declares (tests/test_abi.py checks the .so exports them all)
 ABI_SYMBOLS = [
     "rt_material_standard", "rt_material_checkerboard", "rt_material_gradient", "rt_material_emissive",
@@ -81,6 +87,7 @@ ABI_SYMBOLS = [
     "rt_tile_costs", "rt_partition_tiles", "rt_tiles_copy_device", "rt_max_batch_frames", "rt_peer_access",
     "rt_ctx_synchronize", "rt_render_multi", "rt_render_multi_device", "rt_gather",
     "rt_frame_submit", "rt_frame_collect", "rt_frames_pending", "rt_frame_wait", "rt_frame_depth", "rt_frame_collect_host",
+    "rt_trace_rays", "rt_trace_rays_device", "rt_render_aov", "rt_render_aov_device",
     "rt_to_rgba8_device", "rt_debug_flatten", "rt_debug_read_stats", "rt_debug_eval", "rt_debug_exhaustive", "rt_version",
 ]
 
@@ -191,6 +198,12 @@ def lib():
                                          C.c_int32, C.c_int32, vp, vp]
     L.rt_gather.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(rt_tile_spec), vp]
     L.rt_to_rgba8_device.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
+    if hasattr(L, "rt_trace_rays"):              # (absent from libraries of older revisions loaded through RT_AMD_LIB: tools/build_variants.py name@REV,
+        # and a same-call bench.py comparison with the parent commit's library; every build of this tree exports them, tests/test_abi.py)
+        L.rt_trace_rays.argtypes = [vp, vp, fp, fp, C.c_int64, vp]
+        L.rt_trace_rays_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp]
+        L.rt_render_aov.argtypes = [vp, vp, C.POINTER(rt_camera), fp, fp, fp, fp, C.POINTER(C.c_int32), fp]
+        L.rt_render_aov_device.argtypes = [vp, vp, C.POINTER(rt_camera), fp, vp, vp, vp, vp, vp, vp]
     L.rt_debug_flatten.argtypes = [vp, C.POINTER(rt_flat_view)]
     L.rt_debug_read_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_debug_eval.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32]
@@ -646,6 +659,48 @@ def render_frames(ctx, scene, camera, render_data, data, times_ms):
                                       C.byref(fn), buf.ctypes.data_as(C.POINTER(C.c_float))))
     data.frame_num = fn.value
     return buf
+
+
+def trace_rays(ctx, scene, origins, directions):
+    """The closest hit of every ray (rt_trace_rays): origins, directions [n, 3] float32, the direction taken as it is (not
+    normalised; t is in units of its length).  Returns n records of HIT_DTYPE; a miss has object -1 and t HIT_MISS_T."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    hits = np.zeros(o.shape[0], HIT_DTYPE)
+    ctx._check(lib().rt_trace_rays(ctx._h, scene._h, _fp(o)[1], _fp(d)[1], o.shape[0], C.c_void_p(hits.ctypes.data)))
+    return hits
+
+
+def trace_rays_device(ctx, scene, d_origins, d_directions, n, d_hits, stream=None):
+    """Device-buffer form (rt_trace_rays_device): device pointers (ints, e.g. torch.Tensor.data_ptr()) to n x 3 float32 origins and
+    directions and to n records of HIT_DTYPE.itemsize bytes (16-byte aligned); asynchronous on `stream`."""
+    ctx._check(lib().rt_trace_rays_device(ctx._h, scene._h, C.c_void_p(d_origins or 0), C.c_void_p(d_directions or 0), int(n),
+                                          C.c_void_p(d_hits or 0), C.c_void_p(stream or 0)))
+
+
+def render_aov(ctx, scene, camera, sky_colour=(0.0, 0.0, 0.0), planes=AOV_PLANES):
+    """The first-hit planes of a view (rt_render_aov): a dict with the requested ones of depth [H, W], normal [H, W, 3],
+    albedo [H, W, 3] (float32), object [H, W] (int32) and ray [H, W, 3] (the primary directions)."""
+    unknown = [p for p in planes if p not in AOV_PLANES]
+    if unknown:
+        raise ValueError("unknown planes: %s" % unknown)
+    W, H = camera.width, camera.height
+    shapes = {"depth": (H, W), "normal": (H, W, 3), "albedo": (H, W, 3), "object": (H, W), "ray": (H, W, 3)}
+    out = {p: np.zeros(shapes[p], np.int32 if p == "object" else np.float32) for p in AOV_PLANES if p in planes}
+    sky = np.ascontiguousarray(sky_colour, dtype=np.float32)
+    args = [out[p].ctypes.data_as(C.POINTER(C.c_int32 if p == "object" else C.c_float)) if p in out else None for p in AOV_PLANES]
+    ctx._check(lib().rt_render_aov(ctx._h, scene._h, C.byref(camera.c), _fp(sky)[1], *args))
+    return out
+
+
+def render_aov_device(ctx, scene, camera, sky_colour=(0.0, 0.0, 0.0), d_depth=None, d_normal=None, d_albedo=None, d_object=None,
+                      d_ray=None, stream=None):
+    """Device-buffer form (rt_render_aov_device): device pointers to the wanted planes (None: not wanted); asynchronous on `stream`."""
+    sky = np.ascontiguousarray(sky_colour, dtype=np.float32)
+    ctx._check(lib().rt_render_aov_device(ctx._h, scene._h, C.byref(camera.c), _fp(sky)[1], *[C.c_void_p(p or 0) for p in (d_depth, d_normal, d_albedo, d_object, d_ray)],
+                                          C.c_void_p(stream or 0)))
 
 
 def _tile_spec(band_rows, band_first, band_stride, compact, tile_list, tile_cost, tile_peak=None):

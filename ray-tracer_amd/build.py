@@ -11,8 +11,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libraytracer_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_host.cpp")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_query_capi.cpp", "rt_host.cpp")]
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h", "rt_internal.h", "rt_query.h", "rt_query_kernel.h")] + [
     os.path.join(ROOT, "include", "rt_amd.h")]
 # -fno-slp-vectorize: the SLP vectorizer pairs the scalar f32 adds / multiplies of the vector math into v_pk_*_f32, which
 # are not faster on gfx950 and need register pairs: 128 instead of ~90 VGPRs and ~10 % more time (same-box A/B, round 2).
@@ -52,15 +52,25 @@ def build(force=False, verbose=False):
 
 
 EXAMPLE = os.path.join(HERE, "host", "example_main")
+QUERY_EXAMPLE = os.path.join(HERE, "host", "example_query")
+
+
+def _build_host_program(source, exe):
+    build()
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", os.path.join(HERE, "host", source), "-o", exe,
+           "-L" + HERE, "-lraytracer_amd", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib", "-Wl,--allow-shlib-undefined"]
+    subprocess.check_call(cmd)
+    return exe
 
 
 def build_example():
     """The C++ host-side mirror (host/raytracer.hpp) compiled into a small program with g++."""
-    build()
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", os.path.join(HERE, "host", "example_main.cpp"), "-o", EXAMPLE,
-           "-L" + HERE, "-lraytracer_amd", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib", "-Wl,--allow-shlib-undefined"]
-    subprocess.check_call(cmd)
-    return EXAMPLE
+    return _build_host_program("example_main.cpp", EXAMPLE)
+
+
+def build_query_example():
+    """The mirror's ray queries and first-hit planes (host/example_query.cpp): what the centre pixel sees, the depth plane as a PGM."""
+    return _build_host_program("example_query.cpp", QUERY_EXAMPLE)
 
 
 if __name__ == "__main__":

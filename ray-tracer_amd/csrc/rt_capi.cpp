@@ -24,8 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "rt_host.h"
-#include "rt_schedule.h"
+#include "rt_internal.h"
 
 extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
 extern "C" int rt_kernel_blocks_per_cu(rt_shape shape, size_t lds_bytes);
@@ -38,184 +37,9 @@ extern "C" hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *o
 
 namespace {
 
-/* A device buffer of at least `cap` elements, freed with its owner.  grow() keeps a large enough buffer and otherwise
- * replaces it (the content is not kept; an empty request still gets 16 bytes); a failure leaves {nullptr, 0}. */
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t grow(size_t need)
-    {
-        if (cap >= need && p) return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc((void **)&p, need ? need * sizeof(T) : 16);
-        if (e == hipSuccess) cap = need; else p = nullptr;
-        return e;
-    }
-};
-
-/* a tile list on the device, found again by content (lists are a few KB to ~130 KB and change only with the view).
- * `host` is a pinned copy: what a hash hit is compared with (a 64-bit hash alone would render the wrong
- * tiles on a collision) and what the asynchronous upload reads.  An entry is recycled least-recently-used first; the
- * upload of its new content is ordered behind every launch that read the old one by events, never by a host wait. */
-struct DevList {
-    uint64_t hash = 0;
-    int n = 0;
-    DevBuf<uint32_t> d;
-    uint32_t *host = nullptr;            /* pinned, d.cap entries */
-    uint64_t seq = 0;                    /* rt_ctx::list_seq when last handed out (LRU order; > pin_floor: not recyclable) */
-    hipStream_t stream = nullptr;        /* the stream of the launches it was last handed out for */
-    hipEvent_t ev = nullptr;             /* scratch: "everything queued on `stream` so far" (orders a reuse on another stream) */
-    hipEvent_t ev_up = nullptr;          /* "the upload from `host` is done": the pinned copy may be rewritten */
-    ~DevList() { clear(); if (ev) (void)hipEventDestroy(ev); if (ev_up) (void)hipEventDestroy(ev_up); }
-    /* no content and no buffers: what every failure leaves behind */
-    void clear() { d.release(); if (host) (void)hipHostFree(host); host = nullptr; n = 0; hash = 0; }
-};
-
-/* the root's landing area for one source context's compact image (rt_gather, rt_render_multi_device) */
-struct Stage {
-    DevBuf<float> d;
-    hipEvent_t ev_free = nullptr;        /* recorded on the root's stream after the last de-interleave that read the area */
-    bool used = false;
-    ~Stage() { if (ev_free) (void)hipEventDestroy(ev_free); }
-};
-
-/* cost-balanced multi-GPU calls: a new view's interleaved deal (calls on it measure the tiles), measured, dealt by cost */
-enum class Owners { interleaved, measured, balanced };
-
-/* rt_render_multi[_device] with cost-balanced tile lists: what the root remembers between calls */
-struct MultiState {
-    std::vector<uint32_t> key;           /* camera, image size, number of ranks, scene ids */
-    Owners owners = Owners::interleaved;
-    std::vector<std::vector<uint32_t>> lists, costs, peaks;   /* per rank: its tiles (image indices), their measured costs and peak pixel costs */
-};
-
-/* where the measured tile costs of the current view are */
-enum class Costs { none, on_device, on_host };
-
-/* the current view: (scene, camera, image, tile spec).  Its tiles, their order and what they cost */
-struct View {
-    std::vector<uint32_t> key;           /* what the state below was built for */
-    std::vector<uint32_t> tiles;         /* local tile t of the launch -> the tile's index in the image */
-    bool use_order = false;              /* the scene has a mesh: tickets go through `order` (else the kernel scatters raster order) */
-    std::vector<uint32_t> order;         /* ticket -> local tile (host copy of d_order) */
-    DevBuf<uint32_t> d_order;
-    DevBuf<uint32_t> d_cost, d_peak;     /* per tile: the weighted work of its pixels and of its most expensive one, collected by a launch */
-    Costs costs = Costs::none;           /* on_device: a launch of this view collected them; on_host: cost / peak hold them and the order is refined */
-    int cost_spp = 0;                    /* rays_per_pixel of the launch the figures come from (a pilot: 1) */
-    std::vector<uint32_t> cost, peak;    /* the measured (or caller-supplied) costs and peak pixel costs, per local tile */
-    int num_heavy = 0;                   /* refined order: how many leading tiles go first for ALL frames of a multi-frame launch */
-    /* multi-frame launches, once the tile costs of the view are known: the whole schedule (ticket -> tile, frame),
-     * longest job first over all frames (rt_sched::build_job_order) */
-    DevBuf<uint32_t> d_jobs;
-    int job_frames = 0;                  /* what the uploaded schedule was built for */
-};
-
-}  // namespace
-
-/* One frame in flight of the pipelined per-frame entry points (rt_frame_submit / rt_frame_collect): everything a launch
- * writes that the context otherwise holds once - its stream, its ticket counter, the plane its pixels' means go to. */
-struct FrameSlot {
-    hipStream_t stream = nullptr;
-    uint32_t *counter = nullptr;        /* 1 KB like rt_ctx::tile_counter */
-    DevBuf<float> plane;
-    hipEvent_t ev_done = nullptr;       /* the frame's render kernel has finished (recorded on `stream`) */
-    hipEvent_t ev_free = nullptr;       /* the blend that read the plane has finished (recorded on `stream` too: the blend runs there) */
-    hipEvent_t ev_call = nullptr;       /* where the collector's stream stood when it asked for the frame */
-    bool used = false, folded = false;  /* ev_done / ev_free have been recorded at least once */
-    rt_sched::Layout layout;            /* the launch's output layout: how rt_frame_collect folds the plane into the caller's frame */
-};
-
-struct Pipeline {
-    FrameSlot slots[RT_PIPELINE_DEPTH];
-    int order[RT_PIPELINE_DEPTH];       /* submitted and not collected, oldest first */
-    int pending = 0;
-    int depth = RT_PIPELINE_DEFAULT_DEPTH;   /* rt_frame_depth: how many frames the caller keeps in flight */
-    int last_fold = -1;                 /* the slot whose frame was folded last (folds into one frame happen in collection order) */
-    DevBuf<uint32_t> d_list;            /* the view's tile list (listed tile specs), shared by the frames in flight */
-    std::vector<uint32_t> list_host;
-};
-
-struct rt_ctx {
-    int device = 0;
-    int num_cus = 0;
-    size_t total_mem = 0;
-    std::string err;
-    uint32_t *tile_counter = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool have_timing = false;
-    /* The launch scratch below (ticket counter, per-frame planes, tile order / costs, the two events) is
-     * per context, so launches of one context are kept in order: a launch on another stream than the
-     * previous one first waits for that one's stop event (one launch in flight per context). */
-    hipStream_t last_stream = nullptr;
-    bool launched = false;
-    /* multi-GPU entry points (rt_render_multi*): this rank's compact buffer, its stream and "my image is in the root's
-     * staging area" event; on the root also the staging areas, one per source context */
-    DevBuf<float> d_bands;
-    std::map<rt_ctx *, Stage> stages;
-    hipStream_t multi_stream = nullptr;
-    hipEvent_t ev_multi = nullptr;
-    MultiState multi;
-    std::map<int, int> peer_ok;          /* device -> 1 direct access both ways, 0 refused */
-    /* persistent frame buffers for the host-buffer entry point */
-    DevBuf<float> d_prev, d_out;
-    View view;
-    DevBuf<float> d_partial;             /* multi-frame launches: one plane of per-pixel frame means per frame; the pilot's scratch plane */
-    std::deque<DevList> dev_lists;       /* (a deque: an entry stays where it is while others are added) */
-    size_t dev_list_cap = 64;            /* cached tile lists; beyond that the least recently used entry is recycled (raised when one call pins more) */
-    uint64_t list_seq = 0, pin_floor = ~0ull;   /* entries handed out after pin_floor are held by the running call (rt_render_multi_device) */
-    /* knobs (RT_AMD_*), none changes an image */
-    int work_threshold = RT_DEF_WORK_THRESHOLD;      /* lanes; RT_AMD_WORK_THRESHOLD */
-    int descend_keep = RT_DEF_DESCEND_KEEP;       /* RT_AMD_DESCEND_KEEP (0..64): 0 = run every descent to its end */
-    int ready_break = RT_DEF_READY_BREAK;        /* lanes; RT_AMD_READY_BREAK; 65 = never */
-    int hit_break = RT_DEF_HIT_BREAK;          /* lanes; RT_AMD_HIT_BREAK */
-    int hit_low = RT_DEF_HIT_LOW, mix_break = -1;                 /* RT_AMD_HIT_LOW, RT_AMD_MIX_BREAK (0 = that rule off; -1 = not set: the default of the scene's workgroup shape) */
-    int shade_batch = RT_DEF_SHADE_BATCH;        /* lanes; RT_AMD_SHADE_BATCH (1..64) */
-    Pipeline pipe;
-    int multi_careful = 0;                       /* RT_AMD_MULTI_CAREFUL=1: rt_render_multi_device waits on the host after every phase (diagnosis) */
-};
-
-
-struct rt_scene {
-    rt_ctx *ctx = nullptr;
-    /* (members go in reverse order: the blob is freed first, the texels last) */
-    DevBuf<float> d_tex;
-    DevBuf<float> d_tri_uv;
-    DevBuf<rt_object> d_objects;
-    DevBuf<rt_f4> d_blob;
-    FlatScene flat;          /* host copy (sizes, offsets) */
-    rt_sched::KernelShape kernel;   /* the kernel shape chosen for this scene */
-    uint32_t uid = 0;        /* distinguishes scenes in the tile-order cache (addresses get reused) */
-};
-
-namespace {
-
 /* the live contexts: a root keeps a landing area per SOURCE context (rt_ctx::stages), which has to go when the source does */
 std::mutex g_ctx_mutex;
 std::set<rt_ctx *> g_live_ctxs;
-
-/* check_cuda_error src/utils.cu:5-10 */
-rt_status hip_fail(rt_ctx *ctx, hipError_t e, const char *what)
-{
-    if (ctx) ctx->err = std::string("Error from HIP (") + what + "): " + hipGetErrorString(e);
-    return RT_ERR_HIP;
-}
-
-#define RT_HIP(ctx, call, what)                         \
-    do {                                                \
-        hipError_t e_ = (call);                         \
-        if (e_ != hipSuccess) return hip_fail(ctx, e_, what); \
-    } while (0)
-
-rt_status set_err(rt_ctx *ctx, rt_status code, const std::string &msg)
-{
-    if (ctx) ctx->err = msg;
-    return code;
-}
 
 uint64_t fnv1a(const void *data, size_t bytes, uint64_t h = 1469598103934665603ull)
 {
@@ -318,7 +142,7 @@ int batch_cap(const rt_ctx *ctx, size_t plane_floats)
 
 }  // namespace
 
-extern "C" const char *rt_version(void) { return "ray-tracer_amd 0.3 (gfx950)"; }
+extern "C" const char *rt_version(void) { return "ray-tracer_amd 0.4 (gfx950)"; }
 
 extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
 {

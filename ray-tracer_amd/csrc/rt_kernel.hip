@@ -165,6 +165,90 @@ __device__ __forceinline__ void rt_descend(uint32_t &cur, int &sp, uint2 *my_sta
     }
 }
 
+/* Where a workgroup of the query kernels (rt_query_kernel.h) reads the scene from (MODE, below): stages the blob, or its part before the triangles,
+ * into LDS and points L's sections and the traversal stacks at their places.  The caller synchronises the workgroup.  This restates the first lines of
+ * rt_render_kernel, which keeps them in place: calling this function there changes 3 of its 13 instantiations (see below). */
+template <int NT, int MODE, class Args>
+__device__ __forceinline__ void rt_stage_scene(const Args &a, v4f *lds_raw, int tid, Lds &L, uint2 *&stack)
+{
+    if (MODE != RT_SCENE_GLOBAL) {
+        /* stage the scene (or its part before the triangles) into LDS: coalesced 16-byte loads, one pass per workgroup */
+        const int staged = MODE == RT_SCENE_LDS ? a.blob_f4 : a.off_tris;
+        for (int i = tid; i < staged; i += NT) lds_raw[i] = ((const v4f *)a.blob)[i];
+        L.nodes = lds_raw + a.off_nodes;
+        L.objs = lds_raw + a.off_objlds;
+        L.meshes = lds_raw + a.off_meshes;
+        L.objtab = lds_raw + a.off_objtab;
+        L.tris = MODE == RT_SCENE_LDS ? lds_raw + a.off_tris : (const v4f *)a.blob + a.off_tris;
+        stack = (uint2 *)(lds_raw + staged);
+    } else {
+        const v4f *g = (const v4f *)a.blob;
+        L.nodes = g + a.off_nodes;
+        L.tris = g + a.off_tris;
+        L.objs = g + a.off_objlds;
+        L.meshes = g + a.off_meshes;
+        L.objtab = g + a.off_objtab;
+        stack = (uint2 *)lds_raw;
+    }
+}
+
+/* rt_stage_scene above and rt_mesh_enter, rt_leaf_tris and rt_mesh_merge below serve the query kernels (rt_query_kernel.h) and restate what
+ * rt_render_kernel's prologue, MESH and WORK sections do in place: with the render kernel calling them, some or all of its instantiations come out
+ * with another register allocation or schedule (compared per function against the code object before the queries), and that kernel does not change
+ * with the queries.  rt_descend, rt_pop, the box and triangle tests and rt_closest_simple (rt_pixel.h) ARE one statement for both: those calls leave
+ * the render kernels byte-identical. */
+/* Does a ray start traversing the mesh (m0, m1: its rt_f4 pair of the `meshes` section)?  If so `cur` is its root and `zero_dir` says whether the
+ * direction has a component of exactly zero (box_enter_med3). */
+__device__ __forceinline__ bool rt_mesh_enter(const v4f m0, const v4f m1, V3 o, V3 d, V3 inv, uint32_t &cur, uint32_t &zero_dir)
+{
+    /* a NaN direction (Box-Muller on a zero draw) fails every
+     * triangle test: the mesh cannot be hit, no need to walk it */
+    if (d.x != d.x || d.y != d.y || d.z != d.z) return false;
+    /* the root is pushed unconditionally and tested when popped (src/objects.cu:494-501) */
+    const uint32_t root_ref = __float_as_uint(m1.z);
+    float rd;
+    const bool rh = box_test(m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, o, inv, rd);
+    if (!rh || rd > RT_INF_F || ((root_ref & RT_REF_CHAIN) && !(rd < RT_INF_F))) return false;
+    cur = root_ref;
+    zero_dir = (d.x == 0.0f || d.y == 0.0f || d.z == 0.0f) ? 1u : 0u;
+    return true;
+}
+
+/* The triangles of the leaf `cur`: strict <, first triangle wins ties (src/objects.cu:596) */
+__device__ __forceinline__ void rt_leaf_tris(uint32_t cur, const Lds &L, V3 o, V3 d, float &w_best, int &w_prim)
+{
+    const int start = (int)(cur & RT_REF_START_MASK);
+    const int count = (int)((cur >> RT_REF_COUNT_SHIFT) & RT_REF_COUNT_MAX);
+    for (int k = 0; k < count; k++) {
+        float t;
+        const unsigned long long closer = tri_closer_lanes(L.tris, start + k, o, d, w_best, t);
+        w_best = rt_sel_f32(closer, t, w_best);
+        w_prim = (int)rt_sel_u32(closer, (uint32_t)(start + k), (uint32_t)w_prim);
+    }
+}
+
+/* Pops one entry (sp > 0): it is taken iff !(dist > best) (src/objects.cu:501); through a collapsed chain iff dist < best (:517) - the distance is
+ * never NaN, so that is dist < best, or dist == best on a plain edge.  A refused entry leaves the lane on the empty leaf: it pops again next step. */
+template <int NT>
+__device__ __forceinline__ uint32_t rt_pop(int &sp, const uint2 *my_stack, float w_best)
+{
+    sp--;
+    const uint2 e = my_stack[sp * NT];
+    const float dd = __uint_as_float(e.x);
+    const bool take = dd < w_best || (dd == w_best && !(e.y & RT_REF_CHAIN));
+    return take ? e.y : RT_REF_EMPTY_LEAF;
+}
+
+/* A mesh is done: its closest triangle against the closest hit so far - smaller distance, or equal and later in the object list (the mesh's place in
+ * the list is read again here rather than kept in a register) */
+__device__ __forceinline__ void rt_mesh_merge(const Lds &L, int mesh, float w_best, int w_prim, float &best_t, int &best_obj, int &best_prim)
+{
+    const int w_obj = (int)__float_as_uint(L.meshes[2 * mesh + 1].w);
+    if (w_prim >= 0 && (w_best < best_t || (w_best == best_t && w_obj > best_obj))) {
+        best_t = w_best; best_obj = w_obj; best_prim = w_prim;
+    }
+}
+
 /* MODE (RT_SCENE_*): where the scene is read from.  RT_SCENE_LDS: the whole blob is staged into LDS.  For scenes larger
  * than a CU's LDS the same code reads the triangles (RT_SCENE_HYBRID: the BVH nodes and the object records still fit) or
  * every section (RT_SCENE_GLOBAL) from global memory - they stay L2 / Infinity-Cache resident.  (Requesting a leaf's next
@@ -344,11 +428,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
                          * is refused stays on the empty leaf and pops again next step (rare). */
                         if (sp > 0) {
                             RT_STAT(ST_POP);
-                            sp--;
-                            const uint2 e = my_stack[sp * NT];
-                            const float dd = __uint_as_float(e.x);
-                            const bool take = dd < w_best || (dd == w_best && !(e.y & RT_REF_CHAIN));
-                            cur = take ? e.y : RT_REF_EMPTY_LEAF;
+                            cur = rt_pop<NT>(sp, my_stack, w_best);
                         } else {
                             RT_STAT(ST_DONE_MESH);
                             /* this mesh is done: merge (smaller distance, or equal and later in the list);
@@ -369,6 +449,15 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
     }
     RT_STATS_FLUSH();
 }
+
+/* closest-hit ray queries and the AOV pass: rt_query_kernel and its launcher (not in the development builds, whose counters the
+ * shared traversal pieces would want) */
+#if !defined(RT_STATS) && !defined(RT_COSTMAP) && !defined(RT_MARK)
+#include "rt_query_kernel.h"
+#else
+#include "rt_query.h"
+extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+#endif
 
 /* The sequential part of a multi-frame launch (src/raytracer.cu:109-112, once per frame): the image
  * after frame n is (c_n + image * n) / (n + 1), c_n = that frame's per-pixel mean (plane n - frame_num

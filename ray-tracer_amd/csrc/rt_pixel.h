@@ -392,6 +392,72 @@ __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, co
     px_end_sample(p, a, f);
 }
 
+/* The surface at a closest hit for the query kernels (rt_query_kernel.h): the hit point, the shading normal and, when the object's material
+ * needs them (`packed` bit 4), the texture coordinates - else 0.  These are px_shade's expressions, stated a second time: px_shade calling
+ * this function (and rt_texture_colour below) compiles to render kernels with another register allocation, and the render kernels' code is
+ * not to change with the queries.  tests/test_gpu_query.py holds this copy to the oracle bit for bit, as test_gpu_parity.py holds px_shade. */
+__device__ __forceinline__ void rt_hit_surface(V3 o, V3 d, float best_t, int best_obj, int best_prim, uint32_t packed, const Lds &L, const float *tri_uv,
+                                               V3 &P, V3 &N, float &tex_u, float &tex_v)
+{
+    /* hit point and normal: Ray::get_pos src/ray.cu:63-65; Sphere :66; Triangle :158 */
+    P = d * best_t + o;
+    tex_u = 0.f; tex_v = 0.f;
+    if (packed & 32u) {
+        const v4f sc = L.objs[RT_OBJLDS_F4 * best_obj + 2];
+        N = normalised(P - v3(sc.x, sc.y, sc.z));
+        if (packed & 16u) {
+            /* Sphere::assign_texture_coords src/objects.cu:82-97 (latitude / longitude) */
+            const float PI = 3.141592653589793f;
+            const float theta = rt_asinf((P.y - sc.y) / sc.w);
+            const float phi = rt_acosf((P.x - sc.x) / sc.w);
+            tex_u = (theta + PI / 2) / PI;
+            const float v_ratio = (1 - phi / PI) / 2;
+            const int behind = P.z > sc.z ? 1 : 0;
+            const int mult = 1 - 2 * behind;
+            tex_v = (float)(1 * behind) + (float)mult * v_ratio;
+        }
+    } else {
+        const v4f q2 = L.tris[3 * best_prim + 2];
+        V3 n = v3(q2.y, q2.z, q2.w);
+        N = (dot(n, d) > 0.0f) ? neg(n) : n;
+        if (packed & 16u) {
+            /* Triangle::assign_texture_coords src/objects.cu:160,196-199, called as (w,u,v) */
+            float t, u, v;
+            tri_test(L.tris, best_prim, o, d, t, u, v);
+            float w = 1.0f - u - v;
+            const float *uv = tri_uv + 6 * best_prim;
+            tex_u = uv[0] * w + uv[2] * u + uv[4] * v;
+            tex_v = uv[1] * w + uv[3] * u + uv[5] * v;
+        }
+    }
+}
+
+/* Texture::get_texture_colour src/material.cu:53-69 for the object record (ma, mb) at (tex_u, tex_v): what trace_ray multiplies the
+ * throughput by, for the albedo plane of rt_query_kernel.h (px_shade's lookup, restated for the same reason) */
+__device__ __forceinline__ V3 rt_texture_colour(const v4f ma, const v4f mb, uint32_t packed, float tex_u, float tex_v, const float *tex_data)
+{
+    V3 tc;
+    const int tex = (int)((packed >> 2) & 3u);
+    if (tex == 0) {
+        tc = v3(ma.x, ma.y, ma.z);
+    } else if (tex == 1) {
+        tc = v3(tex_u, tex_v, 0.f);                              /* gradient src/material.cu:80-82 */
+    } else if (tex == 3) {
+        /* image src/material.cu:119-124: nearest texel; an out-of-range index is clamped */
+        const int iw = (int)__float_as_uint(ma.x), ih = (int)__float_as_uint(ma.y);
+        const int uc = rt_f2i((float)(iw - 1) * tex_u), vc = rt_f2i((float)(ih - 1) * tex_v);
+        int idx = (int)((uint32_t)vc * (uint32_t)iw + (uint32_t)uc);       /* wraps like the 32-bit machine arithmetic */
+        idx = idx < 0 ? 0 : (idx > iw * ih - 1 ? iw * ih - 1 : idx);
+        const float *tx = tex_data + (size_t)__float_as_uint(ma.z) + 3 * (size_t)idx;
+        tc = v3(tx[0], tx[1], tx[2]);
+    } else {
+        const int nsq = (int)(packed >> 8);                      /* checkerboard :90-99 */
+        const int uc = rt_f2i(tex_u * (float)nsq), vc = rt_f2i(tex_v * (float)nsq);
+        tc = ((int)((uint32_t)uc + (uint32_t)vc) % 2 == 0) ? v3(ma.x, ma.y, ma.z) : v3(mb.x, mb.y, mb.z);
+    }
+    return tc;
+}
+
 /* ================= SHADE: the closest hit of this bounce is known (p.best_obj >= 0) ========= */
 /* SHORT_DIVIDE: the logarithm's division in its short form (rt_math.h rt__div_benign; the same values): faster in every kernel but the
  * 1024-thread mesh kernel (three-sphere -4.2 %, cube -1.4 %, monkey +0.4 %), which keeps the division operator */
@@ -613,29 +679,18 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
     /* a pixel outside the image (ragged edge tile): stay in M_FETCH */
 }
 
-/* ================= GEN: jitter the direction, test the simple objects ====================== */
-template <bool HAS_MESH>
-__device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds &L)
+/* The closest hit among the non-mesh objects: get_ray_collision src/raytracer.cu:24-46, shared by the render kernels (px_gen,
+ * UNIT_DIR: the direction comes out of normalised()) and the query kernels (rt_query_kernel.h: any direction). */
+template <bool UNIT_DIR>
+__device__ __forceinline__ void rt_closest_simple(V3 o, V3 d, int num_objects, const Lds &L, float &best_t_out, int &best_obj_out, int &best_prim_out)
 {
-    V3 &o = p.o, &d = p.d;
-    p.frame_steps += (unsigned)(RT_COST_GEN * RT_MAX_BATCH_FRAMES);
-    /* Ray::apply_antialias src/ray.cu:130-142 */
-    if (a.antialias) {
-        V3 off;
-        off.x = rt_jitter(rt_pcg_next(&p.rng));
-        off.y = rt_jitter(rt_pcg_next(&p.rng));
-        off.z = rt_jitter(rt_pcg_next(&p.rng));
-        d = normalised(d + off);
-    }
-    if (HAS_MESH) p.inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);   /* src/ray.cu:198-202 (three short reciprocals behind one range check: -0.3 % cube, +0.5 % monkey - not taken) */
-
     /* get_ray_collision src/raytracer.cu:24-46 over the non-mesh objects, in list order
      * (`<=`: the later object wins ties, :36; the precision_error term is a no-op for
      * accepted hits).  Meshes are merged afterwards with the same
      * rule made explicit: smaller distance, or equal distance and larger list index. */
     float best_t = RT_INF_F;
     int best_obj = -1, best_prim = -1;
-    for (int i = 0; i < a.num_objects; i++) {
+    for (int i = 0; i < num_objects; i++) {
         /* rt_object from LDS: every lane reads the same address (broadcast) */
         const v4f ob0 = L.objtab[3 * i], ob1 = L.objtab[3 * i + 1], ob2 = L.objtab[3 * i + 2];
         rt_object ob;
@@ -664,8 +719,9 @@ __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds
                      * below RT_EPS_F (rejected), or - an infinite dividend: inf from the operator, NaN from the short form - fails
                      * `dist > RT_EPS_F` or `t <= best_t` (best_t <= 2^30) alike; every distance that IS accepted comes from a dividend between
                      * 2e-6 and 2^31, where the two agree bit for bit.  The operator's form, should parity ever need it, is
-                     * `float dist = (-qb - rt_sqrt(disc)) / (2.0f * qa);` (profiles/r04/experiments/sphere_divide.txt). */
-                    float dist = rt__div_benign(-qb - rt_sqrt(disc), 2.0f * qa);
+                     * `float dist = (-qb - rt_sqrt(disc)) / (2.0f * qa);` (profiles/r04/experiments/sphere_divide.txt) - which is what a caller
+                     * whose direction is NOT a unit vector gets (!UNIT_DIR: the ray queries of rt_query_kernel.h take the ray as given). */
+                    float dist = UNIT_DIR ? rt__div_benign(-qb - rt_sqrt(disc), 2.0f * qa) : (-qb - rt_sqrt(disc)) / (2.0f * qa);
                     if (dist > RT_EPS_F) { hit = true; t = dist; }
                 }
                 break;
@@ -696,6 +752,28 @@ __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds
         }
         if (hit && t <= best_t) { best_t = t; best_obj = i; best_prim = prim; }
     }
+    best_t_out = best_t; best_obj_out = best_obj; best_prim_out = best_prim;
+}
+
+/* ================= GEN: jitter the direction, test the simple objects ====================== */
+template <bool HAS_MESH>
+__device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds &L)
+{
+    V3 &o = p.o, &d = p.d;
+    p.frame_steps += (unsigned)(RT_COST_GEN * RT_MAX_BATCH_FRAMES);
+    /* Ray::apply_antialias src/ray.cu:130-142 */
+    if (a.antialias) {
+        V3 off;
+        off.x = rt_jitter(rt_pcg_next(&p.rng));
+        off.y = rt_jitter(rt_pcg_next(&p.rng));
+        off.z = rt_jitter(rt_pcg_next(&p.rng));
+        d = normalised(d + off);
+    }
+    if (HAS_MESH) p.inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);   /* src/ray.cu:198-202 (three short reciprocals behind one range check: -0.3 % cube, +0.5 % monkey - not taken) */
+
+    float best_t;
+    int best_obj, best_prim;
+    rt_closest_simple<true>(o, d, a.num_objects, L, best_t, best_obj, best_prim);
     p.best_t = best_t; p.best_obj = best_obj; p.best_prim = best_prim;
     p.next_mesh = 0;
     p.mode = (HAS_MESH && a.num_meshes > 0) ? M_MESH : M_SHADE;

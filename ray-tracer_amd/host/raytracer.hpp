@@ -353,6 +353,34 @@ public:
         check(rt_last_kernel_ms(ctx_, &ms));
         return ms;
     }
+    /* The closest hit of every ray (rt_trace_rays; get_ray_collision src/raytracer.cu:24-46 with the hit written out): origins and
+     * directions hold n x 3 floats, the direction is taken as it is (not normalised).  A miss has object -1 and t RT_HIT_MISS_T. */
+    std::vector<rt_hit> trace_rays(const std::vector<float> &origins, const std::vector<float> &directions)
+    {
+        if (origins.size() != directions.size() || origins.size() % 3 != 0) throw std::invalid_argument("origins and directions must hold n x 3 floats each");
+        std::vector<rt_hit> hits(origins.size() / 3);
+        check(rt_trace_rays(ctx_, scene_, origins.data(), directions.data(), (int64_t)hits.size(), hits.data()));
+        return hits;
+    }
+    rt_hit trace_ray(Vec3 origin, Vec3 direction)
+    {
+        rt_hit h;
+        check(rt_trace_rays(ctx_, scene_, origin.data(), direction.data(), 1, &h));
+        return h;
+    }
+    /* The first-hit planes of a view (rt_render_aov), all five of them: depth W*H, normal / albedo / ray W*H*3, object W*H */
+    struct Aov {
+        std::vector<float> depth, normal, albedo, ray;
+        std::vector<int32_t> object;
+    };
+    Aov render_aov(const Camera &cam, Vec3 sky_colour = Vec3(0, 0, 0))
+    {
+        const size_t px = (size_t)cam.c.width * (size_t)cam.c.height;
+        Aov a;
+        a.depth.resize(px); a.normal.resize(px * 3); a.albedo.resize(px * 3); a.ray.resize(px * 3); a.object.resize(px);
+        check(rt_render_aov(ctx_, scene_, &cam.c, sky_colour.data(), a.depth.data(), a.normal.data(), a.albedo.data(), a.object.data(), a.ray.data()));
+        return a;
+    }
     /* The main loop (src/main.cu:415-431) with frames in flight: submit_frame(get_time()) queues a frame and returns at once,
      * collect_frame() waits for the OLDEST submitted frame and blends it into data like render() would have.  With `depth`
      * frames submitted ahead the GPU stays full although every frame is seeded when it is submitted (rt_frame_submit):
