@@ -361,6 +361,42 @@ rt_status rt_render_aov_device(rt_ctx *ctx, const rt_scene *scene, const rt_came
 rt_status rt_render_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float sky_colour[3],
                         float *depth, float *normal, float *albedo, int32_t *object, float *ray);
 
+/* ---- occlusion (any-hit) ray queries and the light-visibility plane ------------------------------
+ * "Is anything in the way?": line of sight, shadow masks, reachability probes.  For a ray (o, d) taken as given and a limit tmax,
+ *     occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_trace_rays answers) finds a hit AND its t <= tmax.
+ * The direction is not normalised and t, tmax are in units of its length (Ray::change_direction src/ray.cu:198-202); the reference's
+ * acceptance rules (dist > 1e-6 in Sphere::hit and Triangle::hit src/objects.cu:40-79,135-163, one-way quads :273-280, the strict slab
+ * test) are unchanged; a direction with a NaN component hits nothing; a NaN tmax compares false (not occluded); tmax >= RT_HIT_MISS_T
+ * means "any hit at all".  The answer is exact, not approximate: the kernel stops a ray as soon as one object's running best
+ * (src/objects.cu:487-532) is within the limit, which is when the final distance is (tests/test_gpu_occlusion.py: equal to the CPU
+ * oracle's orc_trace_one, every byte).  One byte per ray instead of rt_trace_rays' 48.
+ *
+ * Device-buffer form: d_origins, d_directions (n x 3 floats each), d_tmax (n floats, or NULL = RT_HIT_MISS_T for every ray) and
+ * d_occluded (n bytes: 1 occluded, 0 not) are device memory of ctx's GPU; asynchronous on hip_stream and ordered like
+ * rt_render_device.  n == 0 succeeds and touches nothing; n < 0, n > 2^30, a null pointer (other than d_tmax) with n > 0 and a scene
+ * committed on another context are RT_ERR_INVALID.  rt_last_kernel_ms then reports the occlusion kernel. */
+rt_status rt_occluded_rays_device(rt_ctx *ctx, const rt_scene *scene, const float *d_origins, const float *d_directions,
+                                  const float *d_tmax, int64_t n, uint8_t *d_occluded, void *hip_stream);
+/* Host-buffer form: uploads the rays, answers, downloads the bytes and returns when they are in `occluded`. */
+rt_status rt_occluded_rays(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions,
+                           const float *tmax, int64_t n, uint8_t *occluded);
+
+/* The light-visibility plane of a view: a shadow mask for a point light, W*H bytes in rt_render's row-major layout.  Per pixel
+ *   1. rt_render_aov's primary ray (antialiasing off, src/camera.cu:24-29, src/raytracer.cu:123-127) and its closest hit; none:
+ *      RT_VIS_NO_SURFACE;
+ *   2. from the hit's point P and shading normal N exactly as rt_hit reports them (Ray::get_pos src/ray.cu:63-65, src/objects.cu:66,
+ *      :158): o' = P + N * bias per component in two binary32 roundings (N.x * bias, then + P.x), d' = light_pos - o' (not normalised);
+ *   3. occluded(o', d', 1.0f): RT_VIS_BLOCKED, otherwise RT_VIS_LIT.
+ * A visibility bit: no facing test, no falloff, no light radius; an emissive first hit is a surface like any other. */
+#define RT_VIS_BLOCKED 0
+#define RT_VIS_LIT 1
+#define RT_VIS_NO_SURFACE 2
+rt_status rt_render_visibility_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float light_pos[3], float bias,
+                                      uint8_t *d_visibility, void *hip_stream);
+/* Host-buffer form: returns when the plane is in host memory. */
+rt_status rt_render_visibility(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float light_pos[3], float bias,
+                               uint8_t *visibility);
+
 /* ---- several GPUs of one node from one host thread ---------------------------------------------
  * What run_ray_tracer (src/dispatch.cu:127-153) does on one device, n devices do for the bands they
  * own: rank i of n_ranks renders the bands b with b % n_ranks == i (a pixel depends

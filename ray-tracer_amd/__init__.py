@@ -71,6 +71,7 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal",
                       ("triangle", np.int32), ("u", np.float32), ("v", np.float32), ("reserved", np.int32)])
 HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
+VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
 
 # every symbol include/rt_amd.h declares (tests/test_abi.py checks the .so exports them all)
 ABI_SYMBOLS = [
@@ -88,6 +89,7 @@ ABI_SYMBOLS = [
     "rt_ctx_synchronize", "rt_render_multi", "rt_render_multi_device", "rt_gather",
     "rt_frame_submit", "rt_frame_collect", "rt_frames_pending", "rt_frame_wait", "rt_frame_depth", "rt_frame_collect_host",
     "rt_trace_rays", "rt_trace_rays_device", "rt_render_aov", "rt_render_aov_device",
+    "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_visibility", "rt_render_visibility_device",
     "rt_to_rgba8_device", "rt_debug_flatten", "rt_debug_read_stats", "rt_debug_eval", "rt_debug_exhaustive", "rt_version",
 ]
 
@@ -204,6 +206,11 @@ def lib():
         L.rt_trace_rays_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp]
         L.rt_render_aov.argtypes = [vp, vp, C.POINTER(rt_camera), fp, fp, fp, fp, C.POINTER(C.c_int32), fp]
         L.rt_render_aov_device.argtypes = [vp, vp, C.POINTER(rt_camera), fp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "rt_occluded_rays"):           # (the same: absent from libraries of older revisions)
+        L.rt_occluded_rays.argtypes = [vp, vp, fp, fp, fp, C.c_int64, vp]
+        L.rt_occluded_rays_device.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp]
+        L.rt_render_visibility.argtypes = [vp, vp, C.POINTER(rt_camera), fp, C.c_float, vp]
+        L.rt_render_visibility_device.argtypes = [vp, vp, C.POINTER(rt_camera), fp, C.c_float, vp, vp]
     L.rt_debug_flatten.argtypes = [vp, C.POINTER(rt_flat_view)]
     L.rt_debug_read_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_debug_eval.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32]
@@ -701,6 +708,55 @@ def render_aov_device(ctx, scene, camera, sky_colour=(0.0, 0.0, 0.0), d_depth=No
     sky = np.ascontiguousarray(sky_colour, dtype=np.float32)
     ctx._check(lib().rt_render_aov_device(ctx._h, scene._h, C.byref(camera.c), _fp(sky)[1], *[C.c_void_p(p or 0) for p in (d_depth, d_normal, d_albedo, d_object, d_ray)],
                                           C.c_void_p(stream or 0)))
+
+
+def occluded_rays(ctx, scene, origins, directions, tmax=None):
+    """Is anything in the way (rt_occluded_rays)?  origins, directions [n, 3] float32, the direction taken as it is; tmax None ("any hit
+    at all"), a scalar or n float32 limits in units of the direction's length.  Returns n uint8: 1 where the closest hit exists and lies
+    at t <= tmax, else 0 (a NaN direction or a NaN limit: 0)."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    n = o.shape[0]
+    t = None
+    if tmax is not None:
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,)))
+    out = np.zeros(n, np.uint8)
+    ctx._check(lib().rt_occluded_rays(ctx._h, scene._h, _fp(o)[1], _fp(d)[1], _fp(t)[1] if t is not None else None, n, C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def occluded_rays_device(ctx, scene, d_origins, d_directions, d_tmax, n, d_occluded, stream=None):
+    """Device-buffer form (rt_occluded_rays_device): device pointers to n x 3 float32 origins and directions, n float32 limits (None: any
+    hit at all) and n bytes of answers; asynchronous on `stream`."""
+    ctx._check(lib().rt_occluded_rays_device(ctx._h, scene._h, C.c_void_p(d_origins or 0), C.c_void_p(d_directions or 0), C.c_void_p(d_tmax or 0), int(n),
+                                             C.c_void_p(d_occluded or 0), C.c_void_p(stream or 0)))
+
+
+def visible_between(ctx, scene, a, b, shrink=1e-4):
+    """Line of sight between the points a[i] and b[i] ([n, 3]): True where nothing lies on the segment.  The ray is (a, b - a) with the
+    difference formed in float32, the limit 1 - shrink, so that a surface b itself lies on does not count as a blocker."""
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+    d = (b - a).astype(np.float32)
+    return occluded_rays(ctx, scene, a, d, np.float32(1.0) - np.float32(shrink)) == 0
+
+
+def render_visibility(ctx, scene, camera, light_pos, bias=1e-3):
+    """The light-visibility plane of a view (rt_render_visibility): [H, W] uint8 of VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE - per pixel the
+    primary ray's closest hit, then the segment from P + N * bias to the point light."""
+    out = np.zeros((camera.height, camera.width), np.uint8)
+    light = np.ascontiguousarray(light_pos, dtype=np.float32).reshape(3)
+    ctx._check(lib().rt_render_visibility(ctx._h, scene._h, C.byref(camera.c), _fp(light)[1], float(bias), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def render_visibility_device(ctx, scene, camera, light_pos, bias, d_visibility, stream=None):
+    """Device-buffer form (rt_render_visibility_device): a device pointer to W * H bytes; asynchronous on `stream`."""
+    light = np.ascontiguousarray(light_pos, dtype=np.float32).reshape(3)
+    ctx._check(lib().rt_render_visibility_device(ctx._h, scene._h, C.byref(camera.c), _fp(light)[1], float(bias), C.c_void_p(d_visibility or 0),
+                                                 C.c_void_p(stream or 0)))
 
 
 def _tile_spec(band_rows, band_first, band_stride, compact, tile_list, tile_cost, tile_peak=None):

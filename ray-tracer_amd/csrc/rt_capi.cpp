@@ -142,7 +142,7 @@ int batch_cap(const rt_ctx *ctx, size_t plane_floats)
 
 }  // namespace
 
-extern "C" const char *rt_version(void) { return "ray-tracer_amd 0.4 (gfx950)"; }
+extern "C" const char *rt_version(void) { return "ray-tracer_amd 0.4.1 (gfx950)"; }
 
 extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
 {

@@ -454,9 +454,13 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
  * shared traversal pieces would want) */
 #if !defined(RT_STATS) && !defined(RT_COSTMAP) && !defined(RT_MARK)
 #include "rt_query_kernel.h"
+/* occlusion (any-hit) ray queries and the light-visibility plane: rt_occlusion_kernel and its launcher */
+#include "rt_occlusion_kernel.h"
 #else
 #include "rt_query.h"
+#include "rt_occlusion.h"
 extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 /* The sequential part of a multi-frame launch (src/raytracer.cu:109-112, once per frame): the image

@@ -8,6 +8,8 @@
  *   centre ray: object <index> triangle <index> t <distance, %.9g> point <x y z> normal <x y z>
  *   probe: object <index> t <distance>          (one ray traced on its own, straight ahead from the origin; the same hit)
  *   planes: <hits> of <pixels> pixels hit, nearest <t> farthest <t>
+ *   line of sight: whole <0|1> half <0|1>       (is the segment from the origin to (0, 0, 2), and its first half, blocked?)
+ *   shadow mask: blocked <n> lit <n> no surface <n>      (the view's visibility plane for a point light at (0, 0.3, 1.7))
  *
  * Build:  g++ -std=c++17 -O2 example_query.cpp -L.. -lraytracer_amd -Wl,-rpath,'$ORIGIN/..'
  */
@@ -51,6 +53,12 @@ int main(int argc, char **argv)
             if (aov.depth[i] > farthest) farthest = aov.depth[i];
         }
         std::printf("planes: %zu of %zu pixels hit, nearest %.9g farthest %.9g\n", hits, aov.depth.size(), nearest, farthest);
+        /* occlusion queries: the direction is the segment itself, so the limit is a fraction of it */
+        std::printf("line of sight: whole %d half %d\n", (int)renderer.occluded(Vec3(0, 0, 0), Vec3(0, 0, 2), 1.0f), (int)renderer.occluded(Vec3(0, 0, 0), Vec3(0, 0, 2), 0.5f));
+        const std::vector<uint8_t> mask = renderer.render_visibility(camera, Vec3(0.0f, 0.3f, 1.7f), 1e-3f);
+        size_t codes[3] = {0, 0, 0};
+        for (uint8_t b : mask) codes[b]++;
+        std::printf("shadow mask: blocked %zu lit %zu no surface %zu\n", codes[RT_VIS_BLOCKED], codes[RT_VIS_LIT], codes[RT_VIS_NO_SURFACE]);
         FILE *fp = std::fopen(argv[5], "wb");
         if (!fp) throw std::runtime_error("cannot open output file");
         std::fprintf(fp, "P5\n%d %d\n255\n", W, H);

@@ -381,6 +381,29 @@ public:
         check(rt_render_aov(ctx_, scene_, &cam.c, sky_colour.data(), a.depth.data(), a.normal.data(), a.albedo.data(), a.object.data(), a.ray.data()));
         return a;
     }
+    /* Is anything in the way (rt_occluded_rays)?  One byte per ray: 1 where the closest hit exists and lies at t <= tmax (in units of the
+     * direction's length), else 0.  An empty tmax means "any hit at all". */
+    std::vector<uint8_t> occluded_rays(const std::vector<float> &origins, const std::vector<float> &directions, const std::vector<float> &tmax = {})
+    {
+        if (origins.size() != directions.size() || origins.size() % 3 != 0) throw std::invalid_argument("origins and directions must hold n x 3 floats each");
+        std::vector<uint8_t> out(origins.size() / 3);
+        if (!tmax.empty() && tmax.size() != out.size()) throw std::invalid_argument("tmax must hold n floats, or none");
+        check(rt_occluded_rays(ctx_, scene_, origins.data(), directions.data(), tmax.empty() ? nullptr : tmax.data(), (int64_t)out.size(), out.data()));
+        return out;
+    }
+    bool occluded(Vec3 origin, Vec3 direction, float tmax = RT_HIT_MISS_T)
+    {
+        uint8_t b = 0;
+        check(rt_occluded_rays(ctx_, scene_, origin.data(), direction.data(), &tmax, 1, &b));
+        return b != 0;
+    }
+    /* The light-visibility plane of a view (rt_render_visibility): W*H bytes of RT_VIS_BLOCKED / RT_VIS_LIT / RT_VIS_NO_SURFACE */
+    std::vector<uint8_t> render_visibility(const Camera &cam, Vec3 light_pos, float bias = 1e-3f)
+    {
+        std::vector<uint8_t> out((size_t)cam.c.width * (size_t)cam.c.height);
+        check(rt_render_visibility(ctx_, scene_, &cam.c, light_pos.data(), bias, out.data()));
+        return out;
+    }
     /* The main loop (src/main.cu:415-431) with frames in flight: submit_frame(get_time()) queues a frame and returns at once,
      * collect_frame() waits for the OLDEST submitted frame and blends it into data like render() would have.  With `depth`
      * frames submitted ahead the GPU stays full although every frame is seeded when it is submitted (rt_frame_submit):
