@@ -397,6 +397,58 @@ rt_status rt_render_visibility_device(rt_ctx *ctx, const rt_scene *scene, const 
 rt_status rt_render_visibility(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float light_pos[3], float bias,
                                uint8_t *visibility);
 
+/* ---- edge-avoiding a-trous denoiser driven by the first-hit planes ------------------------------
+ * An image-space filter for a noisy low-sample frame (Dammertz et al. 2010, "Edge-avoiding A-Trous wavelet transform for fast global
+ * illumination filtering"; the spatial filter of SVGF without its temporal part).  It takes plain planes in rt_render's row-major
+ * full-frame layout and needs no scene: C colour (W*H*3 floats), N normal (W*H*3), Z depth (W*H), O object id (W*H int32, optional:
+ * NULL means "all equal"), A albedo (W*H*3, optional) - N, Z, O, A are what rt_render_aov writes.
+ *
+ * The result is DEFINED, not approximated: only binary32 + - * /, comparisons and selects, every operation rounded once (no fused
+ * multiply-add), in the order written here, so tests/denoise_ref.py (NumPy float32) gives the same bits for every pixel.
+ *   1. Demodulate: F0[p].k = C[p].k / max(A[p].k, albedo_floor) per channel k when A is given (max(a, f) = a > f ? a : f), else F0 = C.
+ *   2. For level i = 0 .. iterations-1, s = 1 << i; sc = sigma_colour * 2^-i, kc = 1.0f / (sc * sc) (on the host, binary32).
+ *      Per centre pixel p: kz = 1.0f / (sigma_depth * Z[p]); acc = (0, 0, 0), wsum = 0.
+ *      Taps q = p + (dx*s, dy*s), dy = -2..2 outer, dx = -2..2 inner, in that order; a tap outside the image is skipped.
+ *        hw = h[dy+2] * h[dx+2] rounded once, h = {1/6, 2/3, 1, 2/3, 1/6} as the nearest binary32 values
+ *          = {0x3E2AAAAB, 0x3F2AAAAB, 0x3F800000, 0x3F2AAAAB, 0x3E2AAAAB} (the B3 spline 1:4:6:4:1 scaled so that the centre is 1).
+ *        The centre tap has w = 1.0f and its weight functions are not evaluated (a pixel whose neighbours are all rejected comes back
+ *        bit for bit).  Otherwise, with k(x) = (x < 1.0f) ? (1.0f - x) * (1.0f - x) : 0.0f (a NaN gives 0):
+ *          O[q] != O[p]: the tap is skipped;
+ *          dn = (N[p].x*N[q].x + N[p].y*N[q].y) + N[p].z*N[q].z; wn = dn > 0 ? dn : 0; then wn = wn * wn, normal_power_log2 times;
+ *          r = max(|dx|, |dy|) * s; g = ((Z[q] - Z[p]) * kz) * (1.0f / r); wz = k(g * g);
+ *          d = Fi[q] - Fi[p] per channel; x = ((d.r*d.r + d.g*d.g) + d.b*d.b) * kc; wc = k(x);
+ *          w = hw * ((wn * wz) * wc); a tap with w == 0 is skipped (a non-finite colour behind a zero weight does not spread).
+ *        acc.k = acc.k + w * Fi[q].k (two roundings), wsum = wsum + w, in tap order, the centre in its place.
+ *      F(i+1)[p].k = acc.k / wsum (wsum >= 1).  The guides N, Z, O are always the original planes; only the colour comes from level i.
+ *   3. Remodulate: out[p].k = F[p].k * max(A[p].k, albedo_floor) when A is given, else out = F.
+ * What follows: a miss (normal 0, 0, 0) keeps its own colour; the depth tolerance grows with the tap's distance in pixels (the 1 / r), so
+ * a slanted plane is not cut into strips at the large steps; sigma_depth is relative to the centre's depth; the colour tolerance halves
+ * per level.  d_out may be d_colour: the passes run on buffers of the context's own (48 bytes per pixel, kept until the context goes). */
+typedef struct rt_denoise_params {
+    int32_t iterations;          /* levels, 1 .. 8: level i has step 2^i; the last level's outermost tap is 1 << iterations pixels from its centre, the whole cascade gathers from up to 2 * ((1 << iterations) - 1) pixels away */
+    float sigma_colour;          /* > 0 and finite: the distance in (demodulated) colour at which the first level's weight reaches 0 */
+    float sigma_depth;           /* > 0 and finite: the same for |Z[q] - Z[p]| / Z[p] per pixel of distance */
+    int32_t normal_power_log2;   /* 0 .. 8: the normal weight is max(0, N[p].N[q]) ^ (2 ^ this) */
+    float albedo_floor;          /* > 0 and finite; only read (and only checked) when an albedo plane is given */
+    int32_t reserved[3];         /* 0 */
+} rt_denoise_params;             /* 32 bytes */
+/* The defaults: iterations 5, sigma_colour 4, sigma_depth 0.02, normal_power_log2 5, albedo_floor 0.01.  Tuned on the CPU oracle alone
+ * (three-sphere, cube and monkey scenes, 128 x 128, default camera, 8 bounces, input 4 spp x 1 frame, target 1024 spp): the one set of
+ * those scanned that lowers the RMSE against the target on all three markedly (to 0.28 / 0.37 / 0.58 of the noisy frame's) - a
+ * sigma_colour <= 1 leaves the monkey scene's fireflies (values of 4 .. 7.5) where they are, a looser sigma_depth starts to blur the
+ * two smooth scenes (tests/test_denoise_ref.py). */
+void rt_denoise_params_default(rt_denoise_params *p);
+/* Device-buffer form: every plane and d_out are device memory of ctx's GPU; asynchronous on hip_stream and ordered like
+ * rt_render_device (one launch in flight per context).  A null ctx, d_colour, d_normal, d_depth, params or d_out, a size that is not
+ * positive (or above 32768 on a side, 2^28 pixels in all), parameters outside the ranges above and a non-zero `reserved` are
+ * RT_ERR_INVALID.  rt_last_kernel_ms then reports the denoise passes from first to last. */
+rt_status rt_denoise_device(rt_ctx *ctx, int32_t width, int32_t height, const float *d_colour, const float *d_normal,
+                            const float *d_depth, const int32_t *d_object, const float *d_albedo,
+                            const rt_denoise_params *params, float *d_out, void *hip_stream);
+/* Host-buffer form: uploads the planes, filters, and returns when `out` (W*H*3 floats) is filled. */
+rt_status rt_denoise(rt_ctx *ctx, int32_t width, int32_t height, const float *colour, const float *normal, const float *depth,
+                     const int32_t *object, const float *albedo, const rt_denoise_params *params, float *out);
+
 /* ---- several GPUs of one node from one host thread ---------------------------------------------
  * What run_ray_tracer (src/dispatch.cu:127-153) does on one device, n devices do for the bands they
  * own: rank i of n_ranks renders the bands b with b % n_ranks == i (a pixel depends

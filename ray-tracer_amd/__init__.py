@@ -66,6 +66,11 @@ class rt_flat_view(C.Structure):
                 ("num_triangles", C.c_int32), ("num_nodes", C.c_int32), ("has_mesh", C.c_int32)]
 
 
+class rt_denoise_params(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_colour", C.c_float), ("sigma_depth", C.c_float), ("normal_power_log2", C.c_int32),
+                ("albedo_floor", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 # rt_hit (include/rt_amd.h) as a NumPy record: what trace_rays returns
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal", np.float32, (3,)), ("object", np.int32),
                       ("triangle", np.int32), ("u", np.float32), ("v", np.float32), ("reserved", np.int32)])
@@ -90,6 +95,7 @@ ABI_SYMBOLS = [
     "rt_frame_submit", "rt_frame_collect", "rt_frames_pending", "rt_frame_wait", "rt_frame_depth", "rt_frame_collect_host",
     "rt_trace_rays", "rt_trace_rays_device", "rt_render_aov", "rt_render_aov_device",
     "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_visibility", "rt_render_visibility_device",
+    "rt_denoise_params_default", "rt_denoise", "rt_denoise_device",
     "rt_to_rgba8_device", "rt_debug_flatten", "rt_debug_read_stats", "rt_debug_eval", "rt_debug_exhaustive", "rt_version",
 ]
 
@@ -211,6 +217,12 @@ def lib():
         L.rt_occluded_rays_device.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp]
         L.rt_render_visibility.argtypes = [vp, vp, C.POINTER(rt_camera), fp, C.c_float, vp]
         L.rt_render_visibility_device.argtypes = [vp, vp, C.POINTER(rt_camera), fp, C.c_float, vp, vp]
+    if hasattr(L, "rt_denoise"):                 # (the same: absent from libraries of older revisions)
+        i32p, dp = C.POINTER(C.c_int32), C.POINTER(rt_denoise_params)
+        L.rt_denoise_params_default.argtypes = [dp]
+        L.rt_denoise_params_default.restype = None
+        L.rt_denoise.argtypes = [vp, C.c_int32, C.c_int32, fp, fp, fp, i32p, fp, dp, fp]
+        L.rt_denoise_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, dp, vp, vp]
     L.rt_debug_flatten.argtypes = [vp, C.POINTER(rt_flat_view)]
     L.rt_debug_read_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rt_debug_eval.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32]
@@ -757,6 +769,71 @@ def render_visibility_device(ctx, scene, camera, light_pos, bias, d_visibility, 
     light = np.ascontiguousarray(light_pos, dtype=np.float32).reshape(3)
     ctx._check(lib().rt_render_visibility_device(ctx._h, scene._h, C.byref(camera.c), _fp(light)[1], float(bias), C.c_void_p(d_visibility or 0),
                                                  C.c_void_p(stream or 0)))
+
+
+class DenoiseParams:
+    """rt_denoise_params (include/rt_amd.h): the library's defaults (rt_denoise_params_default) with the given fields replaced"""
+
+    def __init__(self, iterations=None, sigma_colour=None, sigma_depth=None, normal_power_log2=None, albedo_floor=None):
+        self.c = rt_denoise_params()
+        lib().rt_denoise_params_default(C.byref(self.c))
+        for name, value in (("iterations", iterations), ("sigma_colour", sigma_colour), ("sigma_depth", sigma_depth),
+                            ("normal_power_log2", normal_power_log2), ("albedo_floor", albedo_floor)):
+            if value is not None:
+                setattr(self.c, name, value)
+
+    def as_dict(self):
+        return {n: getattr(self.c, n) for n in ("iterations", "sigma_colour", "sigma_depth", "normal_power_log2", "albedo_floor")}
+
+
+def denoise(ctx, colour, normal, depth, object=None, albedo=None, params=None):
+    """The edge-avoiding a-trous filter (rt_denoise): colour, normal [H, W, 3] and depth [H, W] float32, optionally object [H, W] int32
+    (taps across an id edge are skipped) and albedo [H, W, 3] (the colour is divided by it before the filter and multiplied after) - the
+    planes render_aov gives.  Returns the filtered [H, W, 3] float32 image; include/rt_amd.h defines it to the bit."""
+    z = np.ascontiguousarray(depth, dtype=np.float32)
+    if z.ndim != 2:
+        raise ValueError("depth must be [H, W]")
+    H, W = z.shape
+    c = np.ascontiguousarray(colour, dtype=np.float32)
+    n = np.ascontiguousarray(normal, dtype=np.float32)
+    o = None if object is None else np.ascontiguousarray(object, dtype=np.int32)
+    a = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32)
+    if c.shape != (H, W, 3) or n.shape != (H, W, 3) or (o is not None and o.shape != (H, W)) or (a is not None and a.shape != (H, W, 3)):
+        raise ValueError("the planes differ in shape")
+    params = params or DenoiseParams()
+    out = np.zeros((H, W, 3), np.float32)
+    ctx._check(lib().rt_denoise(ctx._h, W, H, _fp(c)[1], _fp(n)[1], _fp(z)[1], o.ctypes.data_as(C.POINTER(C.c_int32)) if o is not None else None,
+                                _fp(a)[1] if a is not None else None, C.byref(params.c), _fp(out)[1]))
+    return out
+
+
+def denoise_device(ctx, width, height, d_colour, d_normal, d_depth, d_object, d_albedo, d_out, params=None, stream=None):
+    """Device-buffer form (rt_denoise_device): device pointers to the planes (d_object, d_albedo may be None) and to W * H * 3 floats of
+    output, which may be d_colour; asynchronous on `stream`."""
+    params = params or DenoiseParams()
+    ctx._check(lib().rt_denoise_device(ctx._h, int(width), int(height), *[C.c_void_p(p or 0) for p in (d_colour, d_normal, d_depth, d_object, d_albedo)],
+                                       C.byref(params.c), C.c_void_p(d_out or 0), C.c_void_p(stream or 0)))
+
+
+def render_denoised(ctx, scene, camera, settings, times_ms, params=None):
+    """Scene in, picture out, all on the device: renders len(times_ms) progressive frames (render_device_batch), takes the view's first-hit
+    planes (render_aov_device; the sky colour is the settings') and filters the frame with them (denoise_device, albedo demodulated).
+    Returns (noisy, denoised), two [H, W, 3] float32 arrays."""
+    import torch
+    W, H = camera.width, camera.height
+    dev = torch.device("cuda:%d" % ctx.device)
+    frame = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+    out = torch.empty_like(frame)
+    depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    normal, albedo = torch.empty_like(frame), torch.empty_like(frame)
+    obj = torch.empty((H, W), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    render_device_batch(ctx, scene, camera, settings, list(times_ms), 0, frame.data_ptr())
+    render_aov_device(ctx, scene, camera, tuple(settings.c.sky_colour), d_depth=depth.data_ptr(), d_normal=normal.data_ptr(), d_albedo=albedo.data_ptr(),
+                      d_object=obj.data_ptr())
+    denoise_device(ctx, W, H, frame.data_ptr(), normal.data_ptr(), depth.data_ptr(), obj.data_ptr(), albedo.data_ptr(), out.data_ptr(), params)
+    ctx.synchronize()
+    return frame.cpu().numpy(), out.cpu().numpy()
 
 
 def _tile_spec(band_rows, band_first, band_stride, compact, tile_list, tile_cost, tile_peak=None):

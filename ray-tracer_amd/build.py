@@ -11,8 +11,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libraytracer_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_host.cpp")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h", "rt_internal.h", "rt_query.h", "rt_query_kernel.h", "rt_occlusion.h", "rt_occlusion_kernel.h")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_denoise_capi.cpp", "rt_host.cpp")]
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h", "rt_internal.h", "rt_query.h", "rt_query_kernel.h", "rt_occlusion.h", "rt_occlusion_kernel.h", "rt_denoise.h", "rt_denoise_kernel.h")] + [
     os.path.join(ROOT, "include", "rt_amd.h")]
 # -fno-slp-vectorize: the SLP vectorizer pairs the scalar f32 adds / multiplies of the vector math into v_pk_*_f32, which
 # are not faster on gfx950 and need register pairs: 128 instead of ~90 VGPRs and ~10 % more time (same-box A/B, round 2).
@@ -53,6 +53,7 @@ def build(force=False, verbose=False):
 
 EXAMPLE = os.path.join(HERE, "host", "example_main")
 QUERY_EXAMPLE = os.path.join(HERE, "host", "example_query")
+DENOISE_EXAMPLE = os.path.join(HERE, "host", "example_denoise")
 
 
 def _build_host_program(source, exe):
@@ -71,6 +72,11 @@ def build_example():
 def build_query_example():
     """The mirror's ray queries and first-hit planes (host/example_query.cpp): what the centre pixel sees, the depth plane as a PGM."""
     return _build_host_program("example_query.cpp", QUERY_EXAMPLE)
+
+
+def build_denoise_example():
+    """The mirror's denoiser (host/example_denoise.cpp): the reference's monkey_test_scene (scene 0) at a few samples per pixel, noisy and denoised side by side as a PNG."""
+    return _build_host_program("example_denoise.cpp", DENOISE_EXAMPLE)
 
 
 if __name__ == "__main__":

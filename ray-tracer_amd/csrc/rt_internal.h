@@ -159,6 +159,8 @@ struct rt_ctx {
     /* the host-buffer forms of the ray queries and the AOV pass (rt_query_capi.cpp): the rays on the device, and the records / planes */
     DevBuf<float> d_query_in;
     DevBuf<rt_f4> d_query_out;
+    /* rt_denoise[_device] (rt_denoise_capi.cpp): per pixel the guide record and the two colour records the levels alternate between */
+    DevBuf<rt_f4> d_denoise;
     int multi_careful = 0;                       /* RT_AMD_MULTI_CAREFUL=1: rt_render_multi_device waits on the host after every phase (diagnosis) */
 };
 

@@ -463,6 +463,9 @@ extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int,
 extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
+/* the edge-avoiding a-trous denoiser: image-space passes over planes, nothing of the traversal above (in every build) */
+#include "rt_denoise_kernel.h"
+
 /* The sequential part of a multi-frame launch (src/raytracer.cu:109-112, once per frame): the image
  * after frame n is (c_n + image * n) / (n + 1), c_n = that frame's per-pixel mean (plane n - frame_num
  * of `partial`).  In place on `frame`; its content is used only when frame_num > 0. */

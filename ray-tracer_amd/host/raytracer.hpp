@@ -404,6 +404,26 @@ public:
         check(rt_render_visibility(ctx_, scene_, &cam.c, light_pos.data(), bias, out.data()));
         return out;
     }
+    /* The edge-avoiding a-trous filter (rt_denoise) on a frame and the view's first-hit planes: colour W*H*3 floats (e.g.
+     * previous_render), the planes as render_aov gives them.  The colour is divided by the albedo before the filter and multiplied
+     * after (use_albedo), taps across an object edge are skipped (use_object).  Returns the filtered W*H*3 floats. */
+    static rt_denoise_params denoise_defaults()
+    {
+        rt_denoise_params p;
+        rt_denoise_params_default(&p);
+        return p;
+    }
+    std::vector<float> denoise(const Camera &cam, const std::vector<float> &colour, const Aov &aov, const rt_denoise_params &params = denoise_defaults(),
+                               bool use_object = true, bool use_albedo = true)
+    {
+        const size_t px = (size_t)cam.c.width * (size_t)cam.c.height;
+        if (colour.size() != px * 3 || aov.normal.size() != px * 3 || aov.depth.size() != px || aov.object.size() != px || aov.albedo.size() != px * 3)
+            throw std::invalid_argument("the frame and the planes must be of the camera's size");
+        std::vector<float> out(px * 3);
+        check(rt_denoise(ctx_, cam.c.width, cam.c.height, colour.data(), aov.normal.data(), aov.depth.data(), use_object ? aov.object.data() : nullptr,
+                         use_albedo ? aov.albedo.data() : nullptr, &params, out.data()));
+        return out;
+    }
     /* The main loop (src/main.cu:415-431) with frames in flight: submit_frame(get_time()) queues a frame and returns at once,
      * collect_frame() waits for the OLDEST submitted frame and blends it into data like render() would have.  With `depth`
      * frames submitted ahead the GPU stays full although every frame is seeded when it is submitted (rt_frame_submit):
