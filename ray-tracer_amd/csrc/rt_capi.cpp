@@ -428,8 +428,7 @@ static rt_status check_launch(rt_ctx *ctx, const rt_scene *scene, const rt_camer
 {
     if (!ctx || !scene || !cam || !rs || !have_out) return set_err(ctx, RT_ERR_INVALID, "null argument");
     if (scene->ctx != ctx) return set_err(ctx, RT_ERR_INVALID, "scene belongs to another context");
-    if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768 || (int64_t)cam->width * cam->height > (1 << 28))
-        return set_err(ctx, RT_ERR_INVALID, "bad image size (at most 32768 pixels on a side and 2^28 in all)");
+    if (rt_status st = check_image_size(ctx, cam->width, cam->height)) return st;
     if (rs->rays_per_pixel < 0 || rs->reflection_limit < 0) return set_err(ctx, RT_ERR_INVALID, "bad render settings");
     if (!t->tile_list && (t->tile_cost || t->tile_peak)) return set_err(ctx, RT_ERR_INVALID, "bad tile spec (tile_cost / tile_peak need a tile_list)");
     if (const char *bad = rt_sched::tile_spec_error(*t, (cam->width + 7) / 8, (cam->height + 7) / 8)) return set_err(ctx, RT_ERR_INVALID, bad);

@@ -1,7 +1,7 @@
 /*
  * rt_denoise_capi.cpp — the edge-avoiding a-trous denoiser of the C ABI (include/rt_amd.h): argument checks, the per-level constants
- * (binary32, on the host), the context's launch ordering and timing, the host-buffer form.  The kernels are rt_denoise_kernel.h; the
- * context is rt_capi.cpp's (rt_internal.h).  The rules are rt_query_capi.cpp's, entry for entry; there is no scene.
+ * (binary32, on the host), the host-buffer form.  The kernels are rt_denoise_kernel.h; the context is rt_capi.cpp's, and the image-size
+ * check and the launch bracket (the context's launch ordering and timing) are rt_internal.h's; there is no scene.
  */
 #include <cmath>
 #include <cstdint>
@@ -20,8 +20,7 @@ rt_status check_denoise(rt_ctx *ctx, int32_t width, int32_t height, const void *
 {
     if (!ctx) return RT_ERR_INVALID;
     if (!colour || !normal || !depth || !pr || !out) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    if (width <= 0 || height <= 0 || width > 32768 || height > 32768 || (int64_t)width * height > (1 << 28))
-        return set_err(ctx, RT_ERR_INVALID, "bad image size (at most 32768 pixels on a side and 2^28 in all)");
+    if (rt_status st = check_image_size(ctx, width, height)) return st;
     if (pr->iterations < 1 || pr->iterations > 8) return set_err(ctx, RT_ERR_INVALID, "bad denoise parameters: iterations (1 .. 8)");
     if (!(pr->sigma_colour > 0.0f) || std::isinf(pr->sigma_colour) || !(pr->sigma_depth > 0.0f) || std::isinf(pr->sigma_depth))
         return set_err(ctx, RT_ERR_INVALID, "bad denoise parameters: sigma_colour and sigma_depth must be positive and finite");
@@ -53,44 +52,37 @@ extern "C" rt_status rt_denoise_device(rt_ctx *ctx, int32_t width, int32_t heigh
     if (st != RT_OK) return st;
     hipStream_t stream = (hipStream_t)hip_stream;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    /* the context's records: guide, then the two colour buffers the levels alternate between.  A launch still running on another
-     * stream reads them until ev_stop (a regrown buffer is freed only after the device is idle: hipFree waits) */
+    /* the context's records: guide, then the two colour buffers the levels alternate between, allocated ahead of the launch bracket (on
+     * the context's device: the bracket selects it once more).  A launch still running on another stream reads them until ev_stop (a
+     * regrown buffer is freed only after the device is idle: hipFree waits) */
     const size_t px = (size_t)width * (size_t)height;
     RT_HIP(ctx, ctx->d_denoise.grow(3 * px), "allocating the denoise records");
-    if (ctx->launched && ctx->last_stream != stream) RT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_stop, 0), "ordering the launch behind the previous one");
-    for (FrameSlot &fs : ctx->pipe.slots)
-        if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
-    RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");
-    ctx->have_timing = false;
-
-    rt_denoise_args a;
-    std::memset(&a, 0, sizeof a);
-    a.width = width; a.height = height;
-    a.colour = d_colour; a.normal = d_normal; a.depth = d_depth; a.object = d_object; a.albedo = d_albedo;
-    a.albedo_floor = params->albedo_floor;
-    a.guide = ctx->d_denoise.p;
-    rt_f4 *buf[2] = {ctx->d_denoise.p + px, ctx->d_denoise.p + 2 * px};
-    a.dst = buf[0];
-    a.out = d_out;
-    a.sigma_depth = params->sigma_depth;
-    a.normal_power_log2 = params->normal_power_log2;
-    RT_HIP(ctx, rt_launch_denoise_pack(&a, stream), "launching the denoise pack kernel");
-    for (int i = 0; i < params->iterations; i++) {
-        /* sc = sigma_colour * 2^-i (exact), kc = 1 / (sc * sc): three binary32 operations, each rounded once */
-        const float sc = params->sigma_colour * std::ldexp(1.0f, -i);
-        const float sc2 = sc * sc;
-        a.kc = 1.0f / sc2;
-        a.step = 1 << i;
-        a.inv_step = std::ldexp(1.0f, -i);
-        a.src = buf[i & 1];
-        a.dst = buf[(i + 1) & 1];
-        RT_HIP(ctx, rt_launch_denoise_level(&a, i == params->iterations - 1, stream), "launching a denoise level kernel");
-    }
-    RT_HIP(ctx, hipEventRecord(ctx->ev_stop, stream), "recording stop event");
-    ctx->have_timing = true;
-    ctx->launched = true;
-    ctx->last_stream = stream;
-    return RT_OK;
+    return launch_bracket(ctx, stream, [&]() -> rt_status {
+        rt_denoise_args a;
+        std::memset(&a, 0, sizeof a);
+        a.width = width; a.height = height;
+        a.colour = d_colour; a.normal = d_normal; a.depth = d_depth; a.object = d_object; a.albedo = d_albedo;
+        a.albedo_floor = params->albedo_floor;
+        a.guide = ctx->d_denoise.p;
+        rt_f4 *buf[2] = {ctx->d_denoise.p + px, ctx->d_denoise.p + 2 * px};
+        a.dst = buf[0];
+        a.out = d_out;
+        a.sigma_depth = params->sigma_depth;
+        a.normal_power_log2 = params->normal_power_log2;
+        RT_HIP(ctx, rt_launch_denoise_pack(&a, stream), "launching the denoise pack kernel");
+        for (int i = 0; i < params->iterations; i++) {
+            /* sc = sigma_colour * 2^-i (exact), kc = 1 / (sc * sc): three binary32 operations, each rounded once */
+            const float sc = params->sigma_colour * std::ldexp(1.0f, -i);
+            const float sc2 = sc * sc;
+            a.kc = 1.0f / sc2;
+            a.step = 1 << i;
+            a.inv_step = std::ldexp(1.0f, -i);
+            a.src = buf[i & 1];
+            a.dst = buf[(i + 1) & 1];
+            RT_HIP(ctx, rt_launch_denoise_level(&a, i == params->iterations - 1, stream), "launching a denoise level kernel");
+        }
+        return RT_OK;
+    });
 }
 
 extern "C" rt_status rt_denoise(rt_ctx *ctx, int32_t width, int32_t height, const float *colour, const float *normal, const float *depth,

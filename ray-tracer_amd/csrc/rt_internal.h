@@ -1,18 +1,22 @@
 /*
  * rt_internal.h — what the translation units behind the C ABI share: the context and the committed scene (rt_ctx, rt_scene), the
- * device-buffer holder and the error helpers.  rt_capi.cpp owns their life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit);
- * rt_query_capi.cpp launches on them.  Not installed: include/rt_amd.h is the interface.
+ * device-buffer holder, the error helpers and, at the end, what the entry points beside the renderer (rt_query_capi.cpp,
+ * rt_occlusion_capi.cpp, rt_denoise_capi.cpp) have in common: the argument checks, the context's launch bracket and the ray kernels'
+ * argument block and launch.  rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed:
+ * include/rt_amd.h is the interface.
  */
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <deque>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "rt_host.h"
+#include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
 #include "rt_schedule.h"
 
 namespace rt_detail {
@@ -194,4 +198,106 @@ inline rt_status set_err(rt_ctx *ctx, rt_status code, const std::string &msg)
 {
     if (ctx) ctx->err = msg;
     return code;
+}
+
+/* ---- argument checks shared by the entry points ------------------------------------------------------------------------------- */
+inline rt_status check_scene(rt_ctx *ctx, const rt_scene *scene)
+{
+    if (!ctx || !scene) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    if (scene->ctx != ctx) return set_err(ctx, RT_ERR_INVALID, "scene belongs to another context");
+    return RT_OK;
+}
+
+/* n rays on a scene: their origins, their directions and where the answers go */
+inline rt_status check_rays(rt_ctx *ctx, const rt_scene *scene, const void *origins, const void *directions, int64_t n, const void *answers)
+{
+    rt_status st = check_scene(ctx, scene);
+    if (st != RT_OK) return st;
+    if (n < 0 || n > RT_QUERY_MAX_RAYS) return set_err(ctx, RT_ERR_INVALID, "bad ray count (0 .. 2^30)");
+    if (n > 0 && (!origins || !directions || !answers)) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    return RT_OK;
+}
+
+/* (2^28 pixels are 2^22 tiles of 8x8: RT_JOB_TILE_MASK, and 64 * tiles fits the ray kernels' 32-bit ids) */
+inline rt_status check_image_size(rt_ctx *ctx, int32_t width, int32_t height)
+{
+    if (width <= 0 || height <= 0 || width > 32768 || height > 32768 || (int64_t)width * height > (1 << 28))
+        return set_err(ctx, RT_ERR_INVALID, "bad image size (at most 32768 pixels on a side and 2^28 in all)");
+    return RT_OK;
+}
+
+/* ---- the launch bracket ------------------------------------------------------------------------------------------------------ */
+/* `work` (kernel launches and copies on `stream`, nothing that waits) in the context's launch order and between its timing events, as
+ * render_frames does it (rt_capi.cpp): one launch in flight per context, because the scratch is shared (see rt_ctx) - behind the previous
+ * launch if that ran on another stream, and behind every pipelined frame in flight.  A step that fails ends the call where it stands: after
+ * ev_start is recorded that leaves have_timing == false, and launched / last_stream as they were. */
+template <class Work>
+rt_status launch_bracket(rt_ctx *ctx, hipStream_t stream, Work work)
+{
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    if (ctx->launched && ctx->last_stream != stream) RT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_stop, 0), "ordering the launch behind the previous one");
+    for (FrameSlot &fs : ctx->pipe.slots)
+        if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
+    RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");
+    ctx->have_timing = false;
+    const rt_status st = work();
+    if (st != RT_OK) return st;
+    RT_HIP(ctx, hipEventRecord(ctx->ev_stop, stream), "recording stop event");
+    ctx->have_timing = true;
+    ctx->launched = true;
+    ctx->last_stream = stream;
+    return RT_OK;
+}
+
+/* ---- the ray kernels' argument blocks and launch (rt_query.h, rt_occlusion.h, rt_ray_kernel.h) ---------------------------- */
+/* a zeroed block (rt_query_args or rt_occlusion_args: the fields carry the same names) with the scene and the work filled in: n rays, or tile
+ * slots, handed out from the context's ticket counter */
+template <class Args>
+Args ray_args_scene(const rt_ctx *ctx, const rt_scene *scene, uint32_t n)
+{
+    Args a;
+    std::memset(&a, 0, sizeof a);
+    a.blob = scene->d_blob.p;
+    a.blob_f4 = (int32_t)scene->flat.blob.size();
+    a.off_nodes = scene->flat.off_nodes;
+    a.off_tris = scene->flat.off_tris;
+    a.off_objlds = scene->flat.off_objlds;
+    a.off_meshes = scene->flat.off_meshes;
+    a.off_objtab = scene->flat.off_objtab;
+    a.num_objects = (int32_t)scene->flat.objects.size();
+    a.num_meshes = scene->flat.num_meshes;
+    a.descend_keep = ctx->descend_keep;
+    a.n = n;
+    a.num_chunks = (n + 63u) / 64u;
+    a.counter = ctx->tile_counter;
+    return a;
+}
+
+/* ... and for a pass over a view: one slot per pixel of every 8x8 tile (at most 2^22 tiles: check_image_size), and the camera */
+template <class Args>
+Args ray_args_view(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam)
+{
+    const int tiles_x = (cam->width + 7) / 8, tiles_y = (cam->height + 7) / 8;
+    Args a = ray_args_scene<Args>(ctx, scene, (uint32_t)tiles_x * (uint32_t)tiles_y * 64u);
+    a.tiles_x = tiles_x;
+    std::memcpy(a.cam + 0, cam->cam_pos, 12);
+    std::memcpy(a.cam + 3, cam->tl_pixel_pos, 12);
+    std::memcpy(a.cam + 6, cam->delta_u, 12);
+    std::memcpy(a.cam + 9, cam->delta_v, 12);
+    a.width = cam->width;
+    a.height = cam->height;
+    return a;
+}
+
+/* One launch of a ray kernel (`launcher`: rt_launch_query or rt_launch_occlusion, with its `front`) on `stream`, in the launch bracket: the
+ * ticket counter is shared with the render launches. */
+template <class Args>
+rt_status launch_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), bool front,
+                      const char *what, hipStream_t stream)
+{
+    return launch_bracket(ctx, stream, [&]() -> rt_status {
+        RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), "clearing the ray counter");
+        RT_HIP(ctx, launcher(&a, scene->kernel.shape, front ? 1 : 0, ctx->num_cus, scene->kernel.lds_bytes, stream), what);
+        return RT_OK;
+    });
 }

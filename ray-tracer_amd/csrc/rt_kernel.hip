@@ -453,6 +453,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 /* closest-hit ray queries and the AOV pass: rt_query_kernel and its launcher (not in the development builds, whose counters the
  * shared traversal pieces would want) */
 #if !defined(RT_STATS) && !defined(RT_COSTMAP) && !defined(RT_MARK)
+#include "rt_ray_kernel.h"
 #include "rt_query_kernel.h"
 /* occlusion (any-hit) ray queries and the light-visibility plane: rt_occlusion_kernel and its launcher */
 #include "rt_occlusion_kernel.h"

@@ -1,7 +1,7 @@
 /*
  * rt_occlusion_kernel.h — occlusion (any-hit) ray queries and the light-visibility plane of a view: "is anything in the way?", one byte
  * per ray.  Included by rt_kernel.hip behind rt_query_kernel.h (it uses that file's and the render kernel's traversal pieces); the
- * launchers at the end are called from rt_occlusion_capi.cpp.
+ * launcher at the end (rt_ray_kernel.h) is called from rt_occlusion_capi.cpp.
  *
  * occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_query_kernel answers) finds a hit AND its distance
  * t <= tmax.  The ray is taken as given (direction not normalised, t and tmax in units of its length, Ray::change_direction
@@ -31,6 +31,7 @@
 #define RT_OCCLUSION_KERNEL_H
 
 #include "rt_occlusion.h"
+#include "rt_ray_kernel.h"
 
 /* lanes of a wave holding a finished ray before the traversal loop yields to store and refill them: swept over 8 / 16 / 24 / 32 with
  * tools/occlusion_probe.py (DESIGN.md §11 has the table) */
@@ -210,47 +211,15 @@ __global__ __launch_bounds__(NT, 4) void rt_occlusion_kernel(const rt_occlusion_
     }
 }
 
-/* ---- launchers (called from rt_occlusion_capi.cpp) ------------------------------------------ */
-template <int NT, bool HAS_MESH, int MODE, bool VIS>
-static hipError_t rt_occlusion_launch_one(const rt_occlusion_args *args, int num_cus, size_t lds_bytes, hipStream_t stream)
-{
-    const void *fn = (const void *)rt_occlusion_kernel<NT, HAS_MESH, MODE, VIS>;
-    /* the LDS opt-in and the resident workgroups per CU, asked once per kernel, device and LDS size, as in rt_query_launch_one */
-    static thread_local struct { int device; size_t lds; int per_cu; } seen = {-1, 0, 0};
-    int device = 0;
-    (void)hipGetDevice(&device);
-    if (seen.device != device || seen.lds != lds_bytes) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, lds_bytes) != hipSuccess || per_cu < 1) { per_cu = 1; (void)hipGetLastError(); }
-        seen = {device, lds_bytes, per_cu};
-    }
-    /* few rays: few workgroups (a wave per 64 rays); many: the persistent grid */
-    const long long waves_per_block = NT / 64;
-    const long long needed = ((long long)args->num_chunks + waves_per_block - 1) / waves_per_block;
-    long long blocks = (long long)num_cus * seen.per_cu;
-    if (blocks > needed) blocks = needed;
-    if (blocks < 1) return hipSuccess;
-    hipLaunchKernelGGL((rt_occlusion_kernel<NT, HAS_MESH, MODE, VIS>), dim3((unsigned)blocks), dim3(NT), lds_bytes, stream, *args);
-    return hipGetLastError();
-}
-
-/* built for every shape of RT_QUERY_SHAPES: a scene that renders answers occlusion queries with the placement, workgroup size and LDS size
- * its committed shape already fixed */
-typedef hipError_t (*rt_occlusion_launch_fn)(const rt_occlusion_args *args, int num_cus, size_t lds_bytes, hipStream_t stream);
-template <bool VIS, size_t... I> static constexpr std::array<rt_occlusion_launch_fn, sizeof...(I)> rt_occlusion_fns_of(std::index_sequence<I...>)
-{
-    return {{rt_occlusion_launch_one<RT_QUERY_SHAPES[I].threads, RT_QUERY_SHAPES[I].has_mesh != 0, RT_QUERY_SHAPES[I].mode, VIS>...}};
-}
-static constexpr auto rt_occlusion_table = rt_occlusion_fns_of<false>(std::make_index_sequence<std::size(RT_QUERY_SHAPES)>());
-static constexpr auto rt_visibility_table = rt_occlusion_fns_of<true>(std::make_index_sequence<std::size(RT_QUERY_SHAPES)>());
+/* ---- launcher (called from rt_occlusion_capi.cpp) ------------------------------------------- */
+struct rt_occlusion_kernels {
+    typedef rt_occlusion_args args;
+    template <int NT, bool HAS_MESH, int MODE, bool VIS> static constexpr auto kernel = &rt_occlusion_kernel<NT, HAS_MESH, MODE, VIS>;
+};
 
 extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *args, rt_shape shape, int vis, int num_cus, size_t lds_bytes, hipStream_t stream)
 {
-    const int i = rt_query_shape_index(shape);
-    if (i < 0) return hipErrorInvalidValue;
-    return (vis ? rt_visibility_table[i] : rt_occlusion_table[i])(args, num_cus, lds_bytes, stream);
+    return rt_ray_launch<rt_occlusion_kernels>(args, shape, vis, num_cus, lds_bytes, stream);
 }
 
 #endif

@@ -1,7 +1,8 @@
 /*
  * rt_query_capi.cpp — the closest-hit ray queries and the first-hit AOV pass of the C ABI (include/rt_amd.h): argument checks, the
- * context's launch ordering and timing, the host-buffer forms.  The kernels are rt_query_kernel.h; the context and the scene are
- * rt_capi.cpp's (rt_internal.h).  A translation unit of its own so that rt_capi.cpp links without the query launcher.
+ * host-buffer forms.  The kernels are rt_query_kernel.h; the context and the scene are rt_capi.cpp's, and the checks, the argument
+ * block's shared part and the launch (in the context's launch order, between its timing events) are rt_internal.h's.  A translation
+ * unit of its own so that rt_capi.cpp links without the query launcher.
  */
 #include <cstdint>
 #include <cstring>
@@ -13,72 +14,13 @@ extern "C" hipError_t rt_launch_query(const rt_query_args *args, rt_shape shape,
 
 namespace {
 
-rt_query_args scene_args(const rt_ctx *ctx, const rt_scene *scene, uint32_t n)
-{
-    rt_query_args a;
-    std::memset(&a, 0, sizeof a);
-    a.blob = scene->d_blob.p;
-    a.blob_f4 = (int32_t)scene->flat.blob.size();
-    a.off_nodes = scene->flat.off_nodes;
-    a.off_tris = scene->flat.off_tris;
-    a.off_objlds = scene->flat.off_objlds;
-    a.off_meshes = scene->flat.off_meshes;
-    a.off_objtab = scene->flat.off_objtab;
-    a.num_objects = (int32_t)scene->flat.objects.size();
-    a.num_meshes = scene->flat.num_meshes;
-    a.descend_keep = ctx->descend_keep;
-    a.tri_uv = scene->d_tri_uv.p;
-    a.tex_data = scene->d_tex.p;
-    a.n = n;
-    a.num_chunks = (n + 63u) / 64u;
-    a.counter = ctx->tile_counter;
-    return a;
-}
-
-/* One query launch on `stream`, in the context's launch order (one launch in flight per context: the ticket counter is shared with the
- * render launches) and between its timing events, as render_frames does it (rt_capi.cpp). */
-rt_status launch_query(rt_ctx *ctx, const rt_scene *scene, const rt_query_args &a, bool aov, hipStream_t stream)
-{
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    if (ctx->launched && ctx->last_stream != stream) RT_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_stop, 0), "ordering the launch behind the previous one");
-    for (FrameSlot &fs : ctx->pipe.slots)
-        if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
-    RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");
-    ctx->have_timing = false;
-    RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), "clearing the ray counter");
-    RT_HIP(ctx, rt_launch_query(&a, scene->kernel.shape, aov ? 1 : 0, ctx->num_cus, scene->kernel.lds_bytes, stream), "launching query kernel");
-    RT_HIP(ctx, hipEventRecord(ctx->ev_stop, stream), "recording stop event");
-    ctx->have_timing = true;
-    ctx->launched = true;
-    ctx->last_stream = stream;
-    return RT_OK;
-}
-
-rt_status check_scene(rt_ctx *ctx, const rt_scene *scene)
-{
-    if (!ctx || !scene) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    if (scene->ctx != ctx) return set_err(ctx, RT_ERR_INVALID, "scene belongs to another context");
-    return RT_OK;
-}
-
-rt_status check_rays(rt_ctx *ctx, const rt_scene *scene, const void *origins, const void *directions, int64_t n, const void *hits)
-{
-    rt_status st = check_scene(ctx, scene);
-    if (st != RT_OK) return st;
-    if (n < 0 || n > RT_QUERY_MAX_RAYS) return set_err(ctx, RT_ERR_INVALID, "bad ray count (0 .. 2^30)");
-    if (n > 0 && (!origins || !directions || !hits)) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    return RT_OK;
-}
-
 rt_status check_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float *sky, bool any_plane)
 {
     rt_status st = check_scene(ctx, scene);
     if (st != RT_OK) return st;
     if (!cam || !sky) return set_err(ctx, RT_ERR_INVALID, "null argument");
     if (!any_plane) return set_err(ctx, RT_ERR_INVALID, "no plane requested");
-    if (cam->width <= 0 || cam->height <= 0 || cam->width > 32768 || cam->height > 32768 || (int64_t)cam->width * cam->height > (1 << 28))
-        return set_err(ctx, RT_ERR_INVALID, "bad image size (at most 32768 pixels on a side and 2^28 in all)");
-    return RT_OK;
+    return check_image_size(ctx, cam->width, cam->height);
 }
 
 }  // namespace
@@ -90,11 +32,13 @@ extern "C" rt_status rt_trace_rays_device(rt_ctx *ctx, const rt_scene *scene, co
     if (st != RT_OK) return st;
     if (n == 0) return RT_OK;
     if ((uintptr_t)d_hits & 15u) return set_err(ctx, RT_ERR_INVALID, "d_hits must be 16-byte aligned");
-    rt_query_args a = scene_args(ctx, scene, (uint32_t)n);
+    rt_query_args a = ray_args_scene<rt_query_args>(ctx, scene, (uint32_t)n);
+    a.tri_uv = scene->d_tri_uv.p;
+    a.tex_data = scene->d_tex.p;
     a.origins = d_origins;
     a.directions = d_directions;
     a.hits = d_hits;
-    return launch_query(ctx, scene, a, false, (hipStream_t)hip_stream);
+    return launch_rays(ctx, scene, a, rt_launch_query, false, "launching query kernel", (hipStream_t)hip_stream);
 }
 
 extern "C" rt_status rt_trace_rays(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions, int64_t n, rt_hit *hits)
@@ -121,18 +65,12 @@ extern "C" rt_status rt_render_aov_device(rt_ctx *ctx, const rt_scene *scene, co
 {
     rt_status st = check_aov(ctx, scene, cam, sky_colour, d_depth || d_normal || d_albedo || d_object || d_ray);
     if (st != RT_OK) return st;
-    const int tiles_x = (cam->width + 7) / 8, tiles_y = (cam->height + 7) / 8;          /* (at most 2^22 tiles: check_aov) */
-    rt_query_args a = scene_args(ctx, scene, (uint32_t)tiles_x * (uint32_t)tiles_y * 64u);
-    a.tiles_x = tiles_x;
-    std::memcpy(a.cam + 0, cam->cam_pos, 12);
-    std::memcpy(a.cam + 3, cam->tl_pixel_pos, 12);
-    std::memcpy(a.cam + 6, cam->delta_u, 12);
-    std::memcpy(a.cam + 9, cam->delta_v, 12);
-    a.width = cam->width;
-    a.height = cam->height;
+    rt_query_args a = ray_args_view<rt_query_args>(ctx, scene, cam);
+    a.tri_uv = scene->d_tri_uv.p;
+    a.tex_data = scene->d_tex.p;
     std::memcpy(a.sky, sky_colour, 12);
     a.depth = d_depth; a.normal = d_normal; a.albedo = d_albedo; a.object = d_object; a.ray = d_ray;
-    return launch_query(ctx, scene, a, true, (hipStream_t)hip_stream);
+    return launch_rays(ctx, scene, a, rt_launch_query, true, "launching query kernel", (hipStream_t)hip_stream);
 }
 
 extern "C" rt_status rt_render_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float sky_colour[3],

@@ -1,7 +1,7 @@
 /*
  * rt_query_kernel.h — closest-hit ray queries and the first-hit AOV pass: one ray per lane through the scene the render kernel
  * stages, stopped at the first hit, with the hit written out instead of shaded.  Included by rt_kernel.hip behind rt_render_kernel
- * (it uses that file's traversal pieces); the launchers at the end are called from rt_query_capi.cpp.
+ * (it uses that file's traversal pieces); the launcher at the end (rt_ray_kernel.h) is called from rt_query_capi.cpp.
  *
  * What is found is get_ray_collision (src/raytracer.cu:24-46) under the render kernel's rules: the top-level objects in list order
  * with `t <= best_t` (rt_closest_simple, rt_pixel.h), then the meshes merged by "smaller distance, or equal distance and larger list
@@ -23,6 +23,7 @@
 #define RT_QUERY_KERNEL_H
 
 #include "rt_query.h"
+#include "rt_ray_kernel.h"
 
 #define RT_QUERY_REFILL 16      /* lanes of a wave holding a finished ray before the traversal loop yields to store and refill them (not tuned) */
 
@@ -194,49 +195,15 @@ __global__ __launch_bounds__(NT, 4) void rt_query_kernel(const rt_query_args a)
     }
 }
 
-/* ---- launchers (called from rt_query_capi.cpp) ---------------------------------------------- */
-template <int NT, bool HAS_MESH, int MODE, bool AOV>
-static hipError_t rt_query_launch_one(const rt_query_args *args, int num_cus, size_t lds_bytes, hipStream_t stream)
-{
-    const void *fn = (const void *)rt_query_kernel<NT, HAS_MESH, MODE, AOV>;
-    /* the LDS opt-in and the resident workgroups per CU, asked once per kernel, device and LDS size (a scene's calls repeat them): two runtime
-     * calls less on the path of a one-ray query.  A failed probe counts as one workgroup per CU and must not surface as a launch error. */
-    static thread_local struct { int device; size_t lds; int per_cu; } seen = {-1, 0, 0};
-    int device = 0;
-    (void)hipGetDevice(&device);
-    if (seen.device != device || seen.lds != lds_bytes) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, lds_bytes) != hipSuccess || per_cu < 1) { per_cu = 1; (void)hipGetLastError(); }
-        seen = {device, lds_bytes, per_cu};
-    }
-    const int per_cu = seen.per_cu;
-    /* few rays: few workgroups (a wave per 64 rays); many: the persistent grid */
-    const long long waves_per_block = NT / 64;
-    const long long needed = ((long long)args->num_chunks + waves_per_block - 1) / waves_per_block;
-    long long blocks = (long long)num_cus * per_cu;
-    if (blocks > needed) blocks = needed;
-    if (blocks < 1) return hipSuccess;
-    hipLaunchKernelGGL((rt_query_kernel<NT, HAS_MESH, MODE, AOV>), dim3((unsigned)blocks), dim3(NT), lds_bytes, stream, *args);
-    return hipGetLastError();
-}
-
-/* the query kernels are built for every shape of RT_QUERY_SHAPES, which is the render kernel's list: a scene that renders answers queries
- * with the placement, workgroup size and LDS size its committed shape already fixed */
-typedef hipError_t (*rt_query_launch_fn)(const rt_query_args *args, int num_cus, size_t lds_bytes, hipStream_t stream);
-template <bool AOV, size_t... I> static constexpr std::array<rt_query_launch_fn, sizeof...(I)> rt_query_fns_of(std::index_sequence<I...>)
-{
-    return {{rt_query_launch_one<RT_QUERY_SHAPES[I].threads, RT_QUERY_SHAPES[I].has_mesh != 0, RT_QUERY_SHAPES[I].mode, AOV>...}};
-}
-static constexpr auto rt_query_table = rt_query_fns_of<false>(std::make_index_sequence<std::size(RT_QUERY_SHAPES)>());
-static constexpr auto rt_aov_table = rt_query_fns_of<true>(std::make_index_sequence<std::size(RT_QUERY_SHAPES)>());
+/* ---- launcher (called from rt_query_capi.cpp) ----------------------------------------------- */
+struct rt_query_kernels {
+    typedef rt_query_args args;
+    template <int NT, bool HAS_MESH, int MODE, bool AOV> static constexpr auto kernel = &rt_query_kernel<NT, HAS_MESH, MODE, AOV>;
+};
 
 extern "C" hipError_t rt_launch_query(const rt_query_args *args, rt_shape shape, int aov, int num_cus, size_t lds_bytes, hipStream_t stream)
 {
-    const int i = rt_query_shape_index(shape);
-    if (i < 0) return hipErrorInvalidValue;
-    return (aov ? rt_aov_table[i] : rt_query_table[i])(args, num_cus, lds_bytes, stream);
+    return rt_ray_launch<rt_query_kernels>(args, shape, aov, num_cus, lds_bytes, stream);
 }
 
 #endif

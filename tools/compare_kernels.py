@@ -1,7 +1,8 @@
 """Compares the gfx950 code of two builds of the library kernel by kernel: python tools/compare_kernels.py OLD.so NEW.so [name ...]
 Unbundles each library's code object, disassembles it, and compares per function the instruction encodings (the hex words llvm-objdump
 prints; addresses and branch-target comments are dropped).  Prints which kernels whose name contains one of the given substrings (default:
-rt_render_kernel, rt_query_kernel) are identical, differ, or exist on one side only, and the register notes of the kernels only NEW has.
+rt_render_kernel, rt_query_kernel, rt_occlusion_kernel) are identical, differ, or exist on one side only, with both sides' VGPR counts for a
+kernel that differs, and the register notes of the kernels only NEW has.
 Exit status 1 if any compared kernel differs or is missing."""
 import os
 import re
@@ -47,11 +48,11 @@ def notes(co):
 
 def main():
     old, new = sys.argv[1], sys.argv[2]
-    wanted = sys.argv[3:] or ["rt_render_kernel", "rt_query_kernel"]
+    wanted = sys.argv[3:] or ["rt_render_kernel", "rt_query_kernel", "rt_occlusion_kernel"]
     with tempfile.TemporaryDirectory() as tmp:
         co_old, co_new = code_object(old, tmp, "old"), code_object(new, tmp, "new")
         e_old, e_new = encodings(co_old), encodings(co_new)
-        n_new = notes(co_new)
+        n_old, n_new = notes(co_old), notes(co_new)
     bad = 0
     for w in wanted:
         names = sorted(n for n in set(e_old) | set(e_new) if w in n)
@@ -60,7 +61,8 @@ def main():
         for n in names:
             if n not in same:
                 bad += 1
-                print("  DIFFERS or missing: %s (old %s, new %s instructions)" % (n, len(e_old.get(n, [])) or "-", len(e_new.get(n, [])) or "-"))
+                print("  DIFFERS or missing: %s (old %s, new %s instructions; old %s, new %s VGPRs)" % (
+                    n, len(e_old.get(n, [])) or "-", len(e_new.get(n, [])) or "-", n_old.get(n, {}).get("vgpr_count", "-"), n_new.get(n, {}).get("vgpr_count", "-")))
     for n in sorted(set(n_new) - set(e_old)):
         print("  new: %s %s, %d instructions" % (n, n_new[n], len(e_new.get(n, []))))
     return 1 if bad else 0
