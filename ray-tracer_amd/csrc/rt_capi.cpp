@@ -1,17 +1,19 @@
 /*
- * rt_capi.cpp — the device half of the C ABI (include/rt_amd.h): context, scene upload,
- * render launches, tile ownership over GPUs, timing.  Replaces the reference's host<->device seam
+ * rt_capi.cpp — the device half of the C ABI (include/rt_amd.h): context and scene life cycle, the
+ * tile-list cache, the view and its schedule, render launches (render_frames), their host-buffer forms,
+ * timing, the debug hooks.  Replaces the reference's host<->device seam
  * (src/dispatch.cu:104-163): where the reference allocates and frees four device buffers per
  * frame and copies the frame element-wise out of managed memory, the context here keeps
  * persistent HBM frame buffers and the device-buffer entry point takes caller-owned HBM.
- * What the launches' tile orders are is worked out in rt_schedule.h.
+ * What the launches' tile orders are is worked out in rt_schedule.h; frames in flight are in
+ * rt_pipeline_capi.cpp, tile ownership over GPUs and the multi-GPU entry points in rt_multi_capi.cpp.
  *
  * There is no CPU fallback: rt_ctx_create fails when HIP has no device.
  */
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,7 +21,6 @@
 #include <map>
 #include <mutex>
 #include <new>
-#include <queue>
 #include <set>
 #include <string>
 #include <vector>
@@ -35,10 +36,11 @@ extern "C" hipError_t rt_launch_tiles_copy(float *compact, float *frame, const u
 extern "C" hipError_t rt_launch_eval(int op, const uint32_t *in, uint32_t *out, int n, hipStream_t stream);
 extern "C" hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *out, hipStream_t stream);
 
+std::mutex rt_detail::g_ctx_mutex;
+
 namespace {
 
-/* the live contexts: a root keeps a landing area per SOURCE context (rt_ctx::stages), which has to go when the source does */
-std::mutex g_ctx_mutex;
+/* the live contexts: a root keeps a landing area per SOURCE context (rt_ctx::multi.stages), which has to go when the source does */
 std::set<rt_ctx *> g_live_ctxs;
 
 uint64_t fnv1a(const void *data, size_t bytes, uint64_t h = 1469598103934665603ull)
@@ -48,15 +50,9 @@ uint64_t fnv1a(const void *data, size_t bytes, uint64_t h = 1469598103934665603u
     return h;
 }
 
-/* A call that holds several lists at once (rt_render_multi_device: every rank's list on the root) pins what it is handed
- * from here on: pinned entries are not recycled, the cache grows instead.  unpin when the call has queued its work. */
-void pin_tile_lists(rt_ctx *ctx) { ctx->pin_floor = ctx->list_seq; }
-void unpin_tile_lists(rt_ctx *ctx) { ctx->pin_floor = ~0ull; }
-
-
 /* `list` into the entry `dl` and on its way to the device on `stream`.  A recycled entry's new upload must not overtake a
  * queued launch that still reads the old content (same stream: stream order; another stream: an event), and the pinned
- * copy is rewritten only once ITS last upload is done - which it has been since dev_list_cap lists ago, so that wait
+ * copy is rewritten only once ITS last upload is done - which it has been since `cap` lists ago, so that wait
  * returns at once.  On an error *what says which step failed. */
 hipError_t fill_dev_list(DevList &dl, bool recycled, const uint32_t *list, int n, hipStream_t stream, const char **what)
 {
@@ -86,19 +82,21 @@ hipError_t fill_dev_list(DevList &dl, bool recycled, const uint32_t *list, int n
     return e;
 }
 
+}  // namespace
+
 /* `list` (host) on ctx's GPU, for launches the caller queues on `stream` after this call.  A list seen before costs a hash
  * and a compare.  A new one takes a free entry or recycles the least recently used one: its content goes into the entry's
  * pinned buffer and is uploaded asynchronously on `stream`, behind (hipStreamWaitEvent) whatever was queued on the stream
  * the entry last served - no host synchronisation on the steady-state path, and no device-wide one ever (round 3 emptied a
  * full cache after hipDeviceSynchronize and waited for every upload).  The pointer stays valid until the entry
- * is recycled: after dev_list_cap other lists, and never while pinned.  An entry that fails is left empty (a new one is
+ * is recycled: after `cap` other lists, and never while pinned.  An entry that fails is left empty (a new one is
  * dropped). */
-rt_status device_tile_list(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t stream, const uint32_t **out)
+rt_status TileListCache::on_device(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t stream, const uint32_t **out)
 {
     *out = nullptr;
     if (n <= 0) return RT_OK;
     const uint64_t h = fnv1a(list, (size_t)n * 4);
-    for (DevList &dl : ctx->dev_lists)
+    for (DevList &dl : lists)
         if (dl.hash == h && dl.n == n && std::memcmp(dl.host, list, (size_t)n * 4) == 0) {
             if (dl.stream != stream) {
                 /* handed to another stream than the one its upload (or last use) was queued on: order the two */
@@ -106,33 +104,33 @@ rt_status device_tile_list(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t
                 RT_HIP(ctx, hipStreamWaitEvent(stream, dl.ev, 0), "ordering a tile list's use");
                 dl.stream = stream;
             }
-            dl.seq = ++ctx->list_seq;
+            dl.seq = ++seq;
             *out = dl.d.p;
             return RT_OK;
         }
     DevList *slot = nullptr;
-    if (ctx->dev_lists.size() >= ctx->dev_list_cap) {
-        for (DevList &dl : ctx->dev_lists)
-            if ((ctx->pin_floor == ~0ull || dl.seq <= ctx->pin_floor) && (!slot || dl.seq < slot->seq)) slot = &dl;
-        if (!slot) ctx->dev_list_cap = ctx->dev_lists.size() + 1;      /* everything is pinned by the running call: grow */
+    if (lists.size() >= cap) {
+        for (DevList &dl : lists)
+            if ((pin_floor == ~0ull || dl.seq <= pin_floor) && (!slot || dl.seq < slot->seq)) slot = &dl;
+        if (!slot) cap = lists.size() + 1;      /* everything is pinned by the running call: grow */
     }
     const bool recycled = slot != nullptr;
     if (!recycled) {
-        ctx->dev_lists.emplace_back();
-        slot = &ctx->dev_lists.back();
-        hipError_t e = hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&slot->ev_up, hipEventDisableTiming);
-        if (e != hipSuccess) { ctx->dev_lists.pop_back(); return hip_fail(ctx, e, "creating a tile list's event"); }
+        lists.emplace_back();
+        slot = &lists.back();
+        hipError_t e = hipEventCreateWithFlags(&slot->ev.e, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&slot->ev_up.e, hipEventDisableTiming);
+        if (e != hipSuccess) { lists.pop_back(); return hip_fail(ctx, e, "creating a tile list's event"); }
     }
     const char *what = "";
     const hipError_t e = fill_dev_list(*slot, recycled, list, n, stream, &what);
     if (e != hipSuccess) { slot->clear(); return hip_fail(ctx, e, what); }
-    slot->hash = h; slot->n = n; slot->stream = stream; slot->seq = ++ctx->list_seq;
+    slot->hash = h; slot->n = n; slot->stream = stream; slot->seq = ++seq;
     *out = slot->d.p;
     return RT_OK;
 }
 
-int batch_cap(const rt_ctx *ctx, size_t plane_floats)
+int rt_detail::batch_cap(const rt_ctx *ctx, size_t plane_floats)
 {
     const size_t plane_bytes = plane_floats * 4;
     if (plane_bytes == 0 || ctx->total_mem == 0) return RT_MAX_BATCH_FRAMES;
@@ -140,7 +138,14 @@ int batch_cap(const rt_ctx *ctx, size_t plane_floats)
     return k >= RT_MAX_BATCH_FRAMES ? RT_MAX_BATCH_FRAMES : (k < 1 ? 1 : (int)k);
 }
 
-}  // namespace
+/* an integer RT_AMD_* variable: its value if that lies in lo..hi, otherwise (or when it is not set) `def` */
+static int env_int(const char *name, int lo, int hi, int def)
+{
+    const char *e = getenv(name);
+    if (!e) return def;
+    const int v = atoi(e);
+    return v >= lo && v <= hi ? v : def;
+}
 
 extern "C" const char *rt_version(void) { return "ray-tracer_amd 0.4.1 (gfx950)"; }
 
@@ -160,17 +165,18 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete ctx; return RT_ERR_NO_DEVICE; }
     ctx->num_cus = prop.multiProcessorCount;
     ctx->total_mem = prop.totalGlobalMem;
-    if (const char *e = getenv("RT_AMD_WORK_THRESHOLD")) { int v = atoi(e); if (v >= 1 && v <= 64) ctx->work_threshold = v; }
-    if (const char *e = getenv("RT_AMD_DESCEND_KEEP")) { int v = atoi(e); if (v >= 0 && v <= 64) ctx->descend_keep = v; }
-    if (const char *e = getenv("RT_AMD_HIT_BREAK")) { int v = atoi(e); if (v >= 1 && v <= 65) ctx->hit_break = v; }
-    if (const char *e = getenv("RT_AMD_HIT_LOW")) { int v = atoi(e); if (v >= 0 && v <= 65) ctx->hit_low = v; }
-    if (const char *e = getenv("RT_AMD_MIX_BREAK")) { int v = atoi(e); if (v >= 0 && v <= 130) ctx->mix_break = v; }
-    if (const char *e = getenv("RT_AMD_SHADE_BATCH")) { int v = atoi(e); if (v >= 1 && v <= 64) ctx->shade_batch = v; }
-    if (const char *e = getenv("RT_AMD_MULTI_CAREFUL")) ctx->multi_careful = atoi(e) != 0;
-    if (const char *e = getenv("RT_AMD_READY_BREAK")) { int v = atoi(e); if (v >= 1 && v <= 65) ctx->ready_break = v; }
-    if (hipMalloc((void **)&ctx->tile_counter, 1024) != hipSuccess ||
-        hipEventCreate(&ctx->ev_start) != hipSuccess || hipEventCreate(&ctx->ev_stop) != hipSuccess) {
-        rt_ctx_destroy(ctx);
+    Knobs &k = ctx->knobs;
+    k.work_threshold = env_int("RT_AMD_WORK_THRESHOLD", 1, 64, k.work_threshold);
+    k.descend_keep = env_int("RT_AMD_DESCEND_KEEP", 0, 64, k.descend_keep);
+    k.hit_break = env_int("RT_AMD_HIT_BREAK", 1, 65, k.hit_break);
+    k.hit_low = env_int("RT_AMD_HIT_LOW", 0, 65, k.hit_low);
+    k.mix_break = env_int("RT_AMD_MIX_BREAK", 0, 130, k.mix_break);
+    k.shade_batch = env_int("RT_AMD_SHADE_BATCH", 1, 64, k.shade_batch);
+    k.ready_break = env_int("RT_AMD_READY_BREAK", 1, 65, k.ready_break);
+    ctx->multi.careful = env_int("RT_AMD_MULTI_CAREFUL", INT_MIN, INT_MAX, 0) != 0;
+    if (ctx->tile_counter.grow(256) != hipSuccess ||
+        hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
+        delete ctx;
         return RT_ERR_HIP;
     }
     {
@@ -189,27 +195,15 @@ extern "C" void rt_ctx_destroy(rt_ctx *ctx)
         std::lock_guard<std::mutex> lock(g_ctx_mutex);
         g_live_ctxs.erase(ctx);
         for (rt_ctx *r : g_live_ctxs) {
-            auto it = r->stages.find(ctx);
-            if (it == r->stages.end()) continue;
+            auto it = r->multi.stages.find(ctx);
+            if (it == r->multi.stages.end()) continue;
             (void)hipSetDevice(r->device);
             if (it->second.ev_free) (void)hipEventSynchronize(it->second.ev_free);
-            r->stages.erase(it);
+            r->multi.stages.erase(it);
         }
     }
     (void)hipSetDevice(ctx->device);
-    if (ctx->tile_counter) (void)hipFree(ctx->tile_counter);
-    for (FrameSlot &fs : ctx->pipe.slots) {
-        if (fs.stream) { (void)hipStreamSynchronize(fs.stream); (void)hipStreamDestroy(fs.stream); }
-        if (fs.counter) (void)hipFree(fs.counter);
-        if (fs.ev_done) (void)hipEventDestroy(fs.ev_done);
-        if (fs.ev_free) (void)hipEventDestroy(fs.ev_free);
-        if (fs.ev_call) (void)hipEventDestroy(fs.ev_call);
-    }
-    if (ctx->multi_stream) (void)hipStreamDestroy(ctx->multi_stream);
-    if (ctx->ev_multi) (void)hipEventDestroy(ctx->ev_multi);
-    if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-    if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-    delete ctx;                          /* (the device buffers, tile lists and staging areas go with it) */
+    delete ctx;                          /* (everything it owns goes with it, the streams first: see rt_ctx) */
 }
 
 extern "C" const char *rt_last_error(const rt_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -292,33 +286,6 @@ extern "C" int32_t rt_tile_owned_rows(const rt_tile_spec *t, int32_t height)
     return rt_sched::Layout(bands, 0, height).owned_rows();
 }
 
-/* Longest-processing-time-first ownership (see include/rt_amd.h) */
-extern "C" rt_status rt_partition_tiles(const uint32_t *cost, int32_t tiles_x, int32_t tiles_y, int32_t n_ranks, int32_t *owner)
-{
-    if (!owner || tiles_x <= 0 || tiles_y <= 0 || n_ranks <= 0 || (int64_t)tiles_x * tiles_y > (int64_t)RT_JOB_TILE_MASK + 1) return RT_ERR_INVALID;
-    const int n = tiles_x * tiles_y;
-    if (!cost) {
-        for (int ty = 0; ty < tiles_y; ty++)
-            for (int tx = 0; tx < tiles_x; tx++) owner[ty * tiles_x + tx] = (tx + ty) % n_ranks;
-        return RT_OK;
-    }
-    std::vector<uint32_t> idx((size_t)n);
-    for (int i = 0; i < n; i++) idx[(size_t)i] = (uint32_t)i;
-    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return cost[x] > cost[y]; });
-    /* (load, rank): the least loaded rank first, the lower rank on a tie */
-    typedef std::pair<uint64_t, int> LR;
-    std::priority_queue<LR, std::vector<LR>, std::greater<LR>> heap;
-    for (int r = 0; r < n_ranks; r++) heap.push(LR(0, r));
-    for (uint32_t t : idx) {
-        LR top = heap.top();
-        heap.pop();
-        owner[t] = top.second;
-        top.first += cost[t];
-        heap.push(top);
-    }
-    return RT_OK;
-}
-
 extern "C" int32_t rt_max_batch_frames(rt_ctx *ctx, int32_t width, int32_t height)
 {
     if (!ctx || width <= 0 || height <= 0) return 1;
@@ -347,8 +314,10 @@ rt_status drain_pipeline(rt_ctx *ctx, bool with_folds)
     return RT_OK;
 }
 
+}  // namespace
+
 /* d_prev and d_out of exactly `bytes` */
-rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes)
+rt_status rt_detail::ensure_frame_buffers(rt_ctx *ctx, size_t bytes)
 {
     const size_t floats = bytes / 4;
     if (ctx->d_prev.cap == floats && ctx->d_out.cap == floats) return RT_OK;
@@ -358,6 +327,8 @@ rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes)
     RT_HIP(ctx, ctx->d_out.grow(floats), "allocating frame buffer");
     return RT_OK;
 }
+
+namespace {
 
 /* `v` into `buf` (grown to fit) on `stream`; the host waits for the copy, as `v` is often a local */
 rt_status upload(rt_ctx *ctx, DevBuf<uint32_t> &buf, const std::vector<uint32_t> &v, hipStream_t stream, const char *what)
@@ -404,8 +375,8 @@ rt_status read_costs_and_refine(rt_ctx *ctx, hipStream_t stream)
 /* (c + prev * n) / (n + 1) over the pixels a launch owns, frame by frame (src/raytracer.cu:109-112): `planes` holds n_frames planes of
  * per-pixel means in the output layout L.  Compact layouts, and a full frame rendered whole: one pass over the buffer; a
  * full-layout frame of which the launch owns some bands / tiles: only those are folded (tiles: d_tile_list, the list on the device) */
-static rt_status fold(rt_ctx *ctx, const rt_sched::Layout &L, const float *planes, int n_frames, int frame_num, float *d_out, const uint32_t *d_tile_list,
-                      hipStream_t stream)
+rt_status rt_detail::fold(rt_ctx *ctx, const rt_sched::Layout &L, const float *planes, int n_frames, int frame_num, float *d_out, const uint32_t *d_tile_list,
+                          hipStream_t stream)
 {
     const long long plane = (long long)L.plane_floats();
     if (L.compact || L.whole_frame()) {
@@ -472,14 +443,15 @@ static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, cons
     a.off_objtab = scene->flat.off_objtab;
     a.num_meshes = scene->flat.num_meshes;
     a.stack_entries = scene->flat.stack_entries;
-    a.work_threshold = ctx->work_threshold;
-    a.ready_break = ctx->ready_break;
-    a.hit_break = ctx->hit_break;
-    const int mix_break = ctx->mix_break >= 0 ? ctx->mix_break : (scene->kernel.shape.threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
-    a.hit_low = ctx->hit_low > 0 && mix_break > 0 ? ctx->hit_low : ctx->hit_break;
-    a.mix_break = ctx->hit_low > 0 && mix_break > 0 ? mix_break : 1000;
-    a.shade_batch = ctx->shade_batch;
-    a.descend_keep = ctx->descend_keep;
+    a.work_threshold = ctx->knobs.work_threshold;
+    a.ready_break = ctx->knobs.ready_break;
+    a.hit_break = ctx->knobs.hit_break;
+    const Knobs &k = ctx->knobs;
+    const int mix_break = k.mix_break >= 0 ? k.mix_break : (scene->kernel.shape.threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
+    a.hit_low = k.hit_low > 0 && mix_break > 0 ? k.hit_low : k.hit_break;
+    a.mix_break = k.hit_low > 0 && mix_break > 0 ? mix_break : 1000;
+    a.shade_batch = ctx->knobs.shade_batch;
+    a.descend_keep = ctx->knobs.descend_keep;
     a.tri_uv = scene->d_tri_uv.p;
     a.tex_data = scene->d_tex.p;
     a.prev = d_prev;
@@ -489,7 +461,7 @@ static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, cons
     return a;
 }
 
-static void push_camera(std::vector<uint32_t> &key, const rt_camera *cam)
+void rt_detail::push_camera(std::vector<uint32_t> &key, const rt_camera *cam)
 {
     for (const float *v : {cam->cam_pos, cam->tl_pixel_pos, cam->delta_u, cam->delta_v})
         for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &v[i], 4); key.push_back(u); }
@@ -663,7 +635,7 @@ static rt_status prepare_view(rt_ctx *ctx, const rt_scene *scene, const rt_camer
     if (is_new && (st = new_view(ctx, scene, t, a, key, stream)) != RT_OK) return st;
     if (t->tile_list) {
         if (slot) a.tile_list = ctx->pipe.d_list.p;
-        else if ((st = device_tile_list(ctx, t->tile_list, (int)n, stream, &a.tile_list)) != RT_OK) return st;
+        else if ((st = ctx->tile_lists.on_device(ctx, t->tile_list, (int)n, stream, &a.tile_list)) != RT_OK) return st;
     }
     if (v.costs == Costs::none) {
         if (wants_pilot(v, rs) && (st = run_pilot(ctx, scene, a, plane_floats, in_place ? (size_t)a.num_frames : 1, stream)) != RT_OK) return st;
@@ -715,9 +687,9 @@ static rt_status launch(rt_ctx *ctx, const rt_scene *scene, const rt_kernel_args
  * frame; > 1, or in_place: d_out is updated in place through one plane of per-pixel means per frame).
  * slot != NULL: a pipelined frame (rt_frame_submit) - the launch runs on the slot's stream with the slot's ticket counter, its
  * pixels' means go to the slot's plane and nothing is folded here; d_prev, d_out and hip_stream are not used. */
-static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
-                               const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
-                               const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot = nullptr)
+rt_status rt_detail::render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
+                                   const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
+                                   const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot)
 {
     rt_tile_spec full{};
     full.band_rows = 8; full.band_stride = 1;
@@ -735,7 +707,7 @@ static rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_came
             if (fs.used) RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_done, 0), "ordering the launch behind the frames in flight");
 
     const rt_sched::Layout L(*t, cam->width, cam->height);
-    rt_kernel_args a = kernel_args(ctx, scene, cam, rs, times_ms, n_frames, frame_num, L, d_prev, d_out, slot ? slot->counter : ctx->tile_counter);
+    rt_kernel_args a = kernel_args(ctx, scene, cam, rs, times_ms, n_frames, frame_num, L, d_prev, d_out, slot ? slot->counter.p : ctx->tile_counter.p);
     bool collecting = false;
     if (a.num_tiles > 0 && (st = prepare_view(ctx, scene, cam, rs, t, a, L.plane_floats(), in_place, slot, stream, &collecting)) != RT_OK) return st;
     if ((st = bind_output(ctx, a, L, in_place, slot)) != RT_OK) return st;
@@ -781,130 +753,6 @@ extern "C" rt_status rt_render_device_batch(rt_ctx *ctx, const rt_scene *scene, 
     return render_frames(ctx, scene, cam, rs, times_ms, n_frames, frame_num, tiles, nullptr, d_frame, hip_stream, true);
 }
 
-/* ---- pipelined frames --------------------------------------------------------------------------------------------------- */
-static rt_status init_slot(rt_ctx *ctx, FrameSlot &fs)
-{
-    /* (each member on its own: a call that failed half-way is finished by the next one) */
-    if (!fs.stream) {
-        /* Frames only overlap if their streams sit on different hardware queues.  The runtime keeps a pool of them per stream
-         * priority (four each by default, GPU_MAX_HW_QUEUES) and the caller's own streams - the null stream, PyTorch's - already
-         * live in the normal-priority pool: a fourth frame's stream would share a queue there and run behind its neighbour
-         * (measured: 4 in flight 333 ms per frame, worse than 3; with streams of the high-priority pool 286-290).  Slots 0-3 take
-         * the high-priority pool, 4-7 the low-priority one; the priority itself is immaterial (the frames are each other's only
-         * competitors: alternating the pools over the slots measures the same at every depth). */
-        int lo = 0, hi = 0;
-        const int k = (int)(&fs - ctx->pipe.slots);
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            RT_HIP(ctx, hipStreamCreateWithPriority(&fs.stream, hipStreamNonBlocking, k < 4 ? hi : lo), "creating a pipelined frame's stream");
-        else
-            RT_HIP(ctx, hipStreamCreateWithFlags(&fs.stream, hipStreamNonBlocking), "creating a pipelined frame's stream");
-    }
-    if (!fs.counter) RT_HIP(ctx, hipMalloc((void **)&fs.counter, 1024), "allocating a pipelined frame's ticket counter");
-    if (!fs.ev_done) RT_HIP(ctx, hipEventCreateWithFlags(&fs.ev_done, hipEventDisableTiming), "creating a pipelined frame's event");
-    if (!fs.ev_free) RT_HIP(ctx, hipEventCreateWithFlags(&fs.ev_free, hipEventDisableTiming), "creating a pipelined frame's event");
-    if (!fs.ev_call) RT_HIP(ctx, hipEventCreateWithFlags(&fs.ev_call, hipEventDisableTiming), "creating a pipelined frame's event");
-    return RT_OK;
-}
-
-extern "C" rt_status rt_frame_submit(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
-                                     int32_t time_ms, const rt_tile_spec *tiles)
-{
-    if (!ctx) return RT_ERR_INVALID;
-    Pipeline &pl = ctx->pipe;
-    if (pl.pending >= pl.depth) return set_err(ctx, RT_ERR_BUSY, "as many frames as rt_frame_depth allows are in flight: collect one first");
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    /* a free slot: one that is not waiting to be collected */
-    int k = -1;
-    for (int i = 0; i < RT_PIPELINE_DEPTH && k < 0; i++) {
-        bool busy = false;
-        for (int j = 0; j < pl.pending; j++) busy = busy || pl.order[j] == i;
-        if (!busy) k = i;
-    }
-    FrameSlot &fs = pl.slots[k];
-    rt_status st = init_slot(ctx, fs);
-    if (st != RT_OK) return st;
-    /* (the slot's plane is rewritten behind the blend that read it last: that ran on the slot's stream) */
-    st = render_frames(ctx, scene, cam, rs, &time_ms, 1, 0, tiles, nullptr, nullptr, nullptr, true, &fs);
-    if (st != RT_OK) return st;
-    pl.order[pl.pending++] = k;
-    return RT_OK;
-}
-
-extern "C" rt_status rt_frame_collect(rt_ctx *ctx, int32_t frame_num, float *d_frame, void *hip_stream)
-{
-    if (!ctx) return RT_ERR_INVALID;
-    Pipeline &pl = ctx->pipe;
-    if (pl.pending <= 0) return set_err(ctx, RT_ERR_INVALID, "no frame has been submitted");
-    if (frame_num < 0) return set_err(ctx, RT_ERR_INVALID, "bad frame number");
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    FrameSlot &fs = pl.slots[pl.order[0]];
-    if (d_frame && fs.layout.num_tiles > 0) {
-        /* The blend runs on the frame's own stream, right behind its render kernel, and the caller's stream only waits for it
-         * (a kernel queued on the caller's stream may sit behind whatever shares that stream's hardware queue).  Ordered behind
-         * what the caller has queued so far (it may still be reading d_frame) and behind the previous frame's blend. */
-        hipStream_t stream = (hipStream_t)hip_stream;
-        RT_HIP(ctx, hipEventRecord(fs.ev_call, stream), "recording the collector's position");
-        RT_HIP(ctx, hipStreamWaitEvent(fs.stream, fs.ev_call, 0), "ordering the blend behind the collector's stream");
-        if (pl.last_fold >= 0 && pl.last_fold != pl.order[0])
-            RT_HIP(ctx, hipStreamWaitEvent(fs.stream, pl.slots[pl.last_fold].ev_free, 0), "ordering the blend behind the previous frame's");
-        rt_status st = fold(ctx, fs.layout, fs.plane.p, 1, frame_num, d_frame, pl.d_list.p, fs.stream);
-        if (st != RT_OK) return st;
-        RT_HIP(ctx, hipEventRecord(fs.ev_free, fs.stream), "recording a pipelined frame's blend");
-        fs.folded = true;
-        pl.last_fold = pl.order[0];
-        RT_HIP(ctx, hipStreamWaitEvent(stream, fs.ev_free, 0), "ordering the collector's stream behind the blend");
-    }
-    for (int j = 1; j < pl.pending; j++) pl.order[j - 1] = pl.order[j];
-    pl.pending--;
-    return RT_OK;
-}
-
-extern "C" int32_t rt_frames_pending(const rt_ctx *ctx) { return ctx ? ctx->pipe.pending : 0; }
-
-extern "C" rt_status rt_frame_depth(rt_ctx *ctx, int32_t depth)
-{
-    if (!ctx) return RT_ERR_INVALID;
-    if (depth < 1 || depth > RT_PIPELINE_DEPTH) return set_err(ctx, RT_ERR_INVALID, "the depth of the frame pipeline is 1..RT_PIPELINE_DEPTH");
-    if (ctx->pipe.pending > 0) return set_err(ctx, RT_ERR_BUSY, "frames are in flight: collect them before changing the depth");
-    ctx->pipe.depth = depth;
-    return RT_OK;
-}
-
-/* host-buffer form of rt_frame_collect, with rt_render's contract for previous_render and *frame_num */
-extern "C" rt_status rt_frame_collect_host(rt_ctx *ctx, int32_t *frame_num, float *previous_render)
-{
-    if (!ctx || !frame_num) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    Pipeline &pl = ctx->pipe;
-    if (pl.pending <= 0) return set_err(ctx, RT_ERR_INVALID, "no frame has been submitted");
-    if (!previous_render) return rt_frame_collect(ctx, 0, nullptr, nullptr);          /* discard */
-    if (*frame_num < 0) return set_err(ctx, RT_ERR_INVALID, "bad frame number");
-    FrameSlot &fs = pl.slots[pl.order[0]];
-    if (!fs.layout.whole_frame()) return set_err(ctx, RT_ERR_INVALID, "the host-buffer form collects whole frames (submitted without a tile spec)");
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    const size_t bytes = (size_t)fs.layout.width * (size_t)fs.layout.height * 3 * sizeof(float);
-    rt_status st = ensure_frame_buffers(ctx, bytes);
-    if (st != RT_OK) return st;
-    /* everything on the frame's own stream, behind its render kernel; the host waits for that stream only - the younger frames
-     * keep running (a hipDeviceSynchronize, as in rt_render, would wait for them too) */
-    if (*frame_num > 0) RT_HIP(ctx, hipMemcpyAsync(ctx->d_out.p, previous_render, bytes, hipMemcpyHostToDevice, fs.stream), "copying previous frame");
-    st = rt_frame_collect(ctx, *frame_num, ctx->d_out.p, fs.stream);
-    if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpyAsync(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost, fs.stream), "copying frame to host");
-    RT_HIP(ctx, hipStreamSynchronize(fs.stream), "render kernel");
-    *frame_num += 1;                                   /* src/dispatch.cu:159 */
-    return RT_OK;
-}
-
-extern "C" rt_status rt_frame_wait(rt_ctx *ctx)
-{
-    if (!ctx) return RT_ERR_INVALID;
-    const Pipeline &pl = ctx->pipe;
-    if (pl.last_fold < 0) return RT_OK;
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    RT_HIP(ctx, hipEventSynchronize(pl.slots[pl.last_fold].ev_free), "waiting for the collected frame");
-    return RT_OK;
-}
-
 extern "C" rt_status rt_tile_costs(rt_ctx *ctx, uint32_t *tile_ids, uint32_t *costs, uint32_t *peaks, int32_t capacity, int32_t *count)
 {
     if (!ctx || !count || capacity < 0 || (capacity > 0 && (!tile_ids || !costs))) return set_err(ctx, RT_ERR_INVALID, "null argument");
@@ -934,7 +782,7 @@ extern "C" rt_status rt_tiles_copy_device(rt_ctx *ctx, float *d_compact, float *
     if (!rt_sched::tiles_in_image(tile_list, num_tiles, tiles_x, tiles_y)) return set_err(ctx, RT_ERR_INVALID, "a tile index outside the image");
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     const uint32_t *d_list = nullptr;
-    rt_status st = device_tile_list(ctx, tile_list, num_tiles, (hipStream_t)hip_stream, &d_list);
+    rt_status st = ctx->tile_lists.on_device(ctx, tile_list, num_tiles, (hipStream_t)hip_stream, &d_list);
     if (st != RT_OK) return st;
     RT_HIP(ctx, rt_launch_tiles_copy(d_compact, d_frame, d_list, num_tiles, tiles_x, width, height, to_frame ? 1 : 0, (hipStream_t)hip_stream), "launching the tile copy");
     return RT_OK;
@@ -983,7 +831,7 @@ extern "C" rt_status rt_debug_read_stats(rt_ctx *ctx, unsigned long long *out48)
 {
     if (!ctx || !out48) return RT_ERR_INVALID;
     RT_HIP(ctx, hipDeviceSynchronize(), "waiting for render kernel");
-    RT_HIP(ctx, hipMemcpy(out48, ctx->tile_counter + 16, 48 * 8, hipMemcpyDeviceToHost), "reading stats");
+    RT_HIP(ctx, hipMemcpy(out48, ctx->tile_counter.p + 16, 48 * 8, hipMemcpyDeviceToHost), "reading stats");
     return RT_OK;
 }
 
@@ -996,23 +844,20 @@ extern "C" rt_status rt_last_kernel_ms(rt_ctx *ctx, float *ms)
     return RT_OK;
 }
 
+/* the host has the frame once the device is idle */
+static rt_status wait_for_device(rt_ctx *ctx)
+{
+    RT_HIP(ctx, hipDeviceSynchronize(), "render kernel");
+    return RT_OK;
+}
+
 extern "C" rt_status rt_render(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
                                int32_t time_ms, int32_t *frame_num, float *previous_render)
 {
-    if (!ctx || !cam || !frame_num || !previous_render) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    if (cam->width <= 0 || cam->height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
-    rt_status st = ensure_frame_buffers(ctx, bytes);
-    if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpy(ctx->d_prev.p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
-    st = rt_render_device(ctx, scene, cam, rs, time_ms, *frame_num, nullptr, ctx->d_prev.p, ctx->d_out.p, nullptr);
-    if (st != RT_OK) return st;
-    RT_HIP(ctx, hipDeviceSynchronize(), "render kernel");
-    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
-    *frame_num += 1;                                   /* src/dispatch.cu:159 */
-    RT_HIP(ctx, hipPeekAtLastError(), "final check after render");   /* src/dispatch.cu:161-162 */
-    return RT_OK;
+    return host_round_trip(ctx, cam, 1, frame_num, previous_render, &rt_ctx::d_prev, [&](size_t) -> rt_status {
+        const rt_status st = rt_render_device(ctx, scene, cam, rs, time_ms, *frame_num, nullptr, ctx->d_prev.p, ctx->d_out.p, nullptr);
+        return st != RT_OK ? st : wait_for_device(ctx);
+    });
 }
 
 /* the same for n_frames consecutive frames at once (seeds times_ms[i]): one multi-frame launch per
@@ -1020,25 +865,17 @@ extern "C" rt_status rt_render(rt_ctx *ctx, const rt_scene *scene, const rt_came
 extern "C" rt_status rt_render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
                                       const int32_t *times_ms, int32_t n_frames, int32_t *frame_num, float *previous_render)
 {
-    if (!ctx || !cam || !frame_num || !previous_render || !times_ms || n_frames < 1) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    if (cam->width <= 0 || cam->height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
-    rt_status st = ensure_frame_buffers(ctx, bytes);
-    if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpy(ctx->d_out.p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
-    const int32_t cap = batch_cap(ctx, bytes / 4);
-    for (int32_t done = 0; done < n_frames;) {
-        const int32_t k = n_frames - done < cap ? n_frames - done : cap;
-        st = rt_render_device_batch(ctx, scene, cam, rs, times_ms + done, k, *frame_num + done, nullptr, ctx->d_out.p, nullptr);
-        if (st != RT_OK) return st;
-        done += k;
-    }
-    RT_HIP(ctx, hipDeviceSynchronize(), "render kernel");
-    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
-    *frame_num += n_frames;
-    RT_HIP(ctx, hipPeekAtLastError(), "final check after render");
-    return RT_OK;
+    if (!times_ms || n_frames < 1) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    return host_round_trip(ctx, cam, n_frames, frame_num, previous_render, &rt_ctx::d_out, [&](size_t bytes) -> rt_status {
+        const int32_t cap = batch_cap(ctx, bytes / 4);
+        for (int32_t done = 0; done < n_frames;) {
+            const int32_t k = n_frames - done < cap ? n_frames - done : cap;
+            const rt_status st = rt_render_device_batch(ctx, scene, cam, rs, times_ms + done, k, *frame_num + done, nullptr, ctx->d_out.p, nullptr);
+            if (st != RT_OK) return st;
+            done += k;
+        }
+        return wait_for_device(ctx);
+    });
 }
 
 /* waits for the most recent launch of this context */
@@ -1052,390 +889,6 @@ extern "C" rt_status rt_ctx_synchronize(rt_ctx *ctx)
     }
     if (!ctx->launched) return RT_OK;
     RT_HIP(ctx, hipEventSynchronize(ctx->ev_stop), "waiting for render kernel");
-    return RT_OK;
-}
-
-/* =============================================================================================
- * Multi-GPU from one host thread (SURVEY.md §8(b) "rt_gather", §8(e)): every rank renders the tiles it
- * owns on its own GPU into a compact buffer; the buffers travel to the root's GPU with one peer copy per
- * rank (xGMI) and are de-interleaved there.  No collective is needed: nothing is reduced, every pixel has
- * one owner.  Ownership is either static (bands: rank i owns the bands b % n == i) or cost-balanced (tile
- * lists dealt longest-processing-time-first from the costs the view's first launch measures).
- * ============================================================================================= */
-namespace {
-
-/* A compact image of layout L and the width x height frame, both on the current device: the image into the frame (to_frame) or
- * out of it.  A list's tiles go through rt_launch_tiles_copy (d_tile_list: the list on this device); bands through one 2D copy
- * of the whole bands and one of the valid rows of a ragged last band (only those exist in the frame). */
-hipError_t exchange(const rt_sched::Layout &L, float *compact, float *frame, bool to_frame, const uint32_t *d_tile_list, hipStream_t stream)
-{
-    if (L.listed) return rt_launch_tiles_copy(compact, frame, d_tile_list, L.num_tiles, L.tiles_x, L.width, L.height, to_frame ? 1 : 0, stream);
-    const int nb = L.owned_bands(), whole = L.whole_bands();
-    const size_t chunk_bytes = L.band_floats() * 4, frame_pitch = chunk_bytes * (size_t)L.band_stride;
-    float *frame0 = frame + (size_t)L.band_first * L.band_floats();
-    hipError_t e = hipSuccess;
-    if (whole > 0) {
-        e = to_frame ? hipMemcpy2DAsync(frame0, frame_pitch, compact, chunk_bytes, chunk_bytes, (size_t)whole, hipMemcpyDeviceToDevice, stream)
-                     : hipMemcpy2DAsync(compact, chunk_bytes, frame0, frame_pitch, chunk_bytes, (size_t)whole, hipMemcpyDeviceToDevice, stream);
-        if (e != hipSuccess) return e;
-    }
-    if (whole < nb) {
-        const int b = L.band(nb - 1);
-        const size_t bytes = (size_t)L.rows_of(b) * (size_t)L.width * 12;
-        float *f = frame + (size_t)b * L.band_floats(), *c = compact + (size_t)(nb - 1) * L.band_floats();
-        e = to_frame ? hipMemcpyAsync(f, c, bytes, hipMemcpyDeviceToDevice, stream) : hipMemcpyAsync(c, f, bytes, hipMemcpyDeviceToDevice, stream);
-    }
-    return e;
-}
-
-rt_status multi_prepare(rt_ctx *ctx)
-{
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    if (!ctx->multi_stream) RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->multi_stream, hipStreamNonBlocking), "creating the rank's stream");
-    if (!ctx->ev_multi) RT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_multi, hipEventDisableTiming), "creating the rank's event");
-    return RT_OK;
-}
-
-/* device-to-device bytes between two contexts' GPUs (a plain copy when they share one), on a stream of
- * the CURRENT device */
-hipError_t copy_between(float *dst, int dst_dev, const float *src, int src_dev, size_t bytes, hipStream_t stream)
-{
-    if (bytes == 0) return hipSuccess;
-    if (dst_dev == src_dev) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
-    return hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, stream);
-}
-
-/* The root's landing area for src's compact image, at least `need` floats, ready to be written in the order of `s0`:
- * s0 has been made to wait for the last de-interleave that read it (which may have been queued on another stream
- * of the root by an earlier call).  Leaves the root's device current. */
-rt_status stage_for(rt_ctx *root, rt_ctx *src, size_t need, hipStream_t s0, Stage **out)
-{
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
-    /* rt_ctx_destroy of a source erases its entry from every live root's map under g_ctx_mutex: look the
-     * entry up under the same lock.  (std::map nodes do not move: the reference stays valid while src is alive.) */
-    Stage *sgp;
-    { std::lock_guard<std::mutex> lock(g_ctx_mutex); sgp = &root->stages[src]; }
-    Stage &sg = *sgp;
-    if (!sg.ev_free) RT_HIP(root, hipEventCreateWithFlags(&sg.ev_free, hipEventDisableTiming), "creating the staging event");
-    if (sg.d.cap < need || !sg.d.p) {
-        /* nothing may still be reading or writing the old area */
-        if (sg.used) RT_HIP(root, hipEventSynchronize(sg.ev_free), "waiting for the staging area");
-        if (src->multi_stream) { (void)hipSetDevice(src->device); (void)hipStreamSynchronize(src->multi_stream); (void)hipSetDevice(root->device); }
-        RT_HIP(root, sg.d.grow(need), "allocating the gather staging area");
-        sg.used = false;
-    }
-    if (sg.used) RT_HIP(root, hipStreamWaitEvent(s0, sg.ev_free, 0), "ordering behind the previous de-interleave");
-    *out = &sg;
-    return RT_OK;
-}
-
-int peer_access(rt_ctx *a, rt_ctx *b)
-{
-    if (a->device == b->device) return 1;
-    auto it = a->peer_ok.find(b->device);
-    if (it != a->peer_ok.end()) return it->second;
-    int ok = 1;
-    for (int dir = 0; dir < 2; dir++) {
-        const int from = dir ? b->device : a->device, to = dir ? a->device : b->device;
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, from, to) != hipSuccess || !can) { ok = 0; continue; }
-        if (hipSetDevice(from) != hipSuccess) { ok = 0; continue; }
-        const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) ok = 0;
-    }
-    (void)hipGetLastError();           /* "already enabled" must not surface as a later launch error */
-    (void)hipSetDevice(a->device);
-    a->peer_ok[b->device] = ok;
-    b->peer_ok[a->device] = ok;
-    return ok;
-}
-
-}  // namespace
-
-extern "C" int32_t rt_peer_access(rt_ctx *a, rt_ctx *b)
-{
-    if (!a || !b) return -RT_ERR_INVALID;
-    return peer_access(a, b);
-}
-
-/* The exchange step alone: the compact buffer `d_bands` of the rank described by `src_tiles`
- * (on src's GPU) lands in the full frame `d_frame` on root's GPU.  Ordered behind src's most recent
- * launch; the frame is complete in `root_stream` order. */
-extern "C" rt_status rt_gather(rt_ctx *root, float *d_frame, int32_t width, int32_t height, rt_ctx *src, const float *d_bands,
-                               const rt_tile_spec *src_tiles, void *root_stream)
-{
-    if (!root || !src || !d_frame || !d_bands || !src_tiles) return set_err(root, RT_ERR_INVALID, "null argument");
-    if (width <= 0 || height <= 0) return set_err(root, RT_ERR_INVALID, "bad image size");
-    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
-    if (const char *bad = rt_sched::tile_spec_error(*src_tiles, tiles_x, tiles_y)) return set_err(root, RT_ERR_INVALID, bad);
-    if (src_tiles->tile_list && !rt_sched::tiles_in_image(src_tiles->tile_list, src_tiles->num_tiles, tiles_x, tiles_y))
-        return set_err(root, RT_ERR_INVALID, "a tile index outside the image");
-    const rt_sched::Layout L(*src_tiles, width, height);
-    rt_status st = multi_prepare(root);
-    if (st != RT_OK) return st;
-    hipStream_t s0 = (hipStream_t)root_stream;
-    float *from = const_cast<float *>(d_bands);
-    Stage *sg = nullptr;
-    if (src->device != root->device) {
-        /* one peer copy of the whole compact buffer into the root's staging area for this source: behind src's last
-         * launch, and behind the de-interleave of the PREVIOUS gather from this source, which reads the same area on the
-         * root's stream (src may be a frame ahead of the root) */
-        if ((st = multi_prepare(src)) != RT_OK) return set_err(root, st, rt_last_error(src));
-        (void)peer_access(src, root);
-        if ((st = stage_for(root, src, L.compact_floats(), s0, &sg)) != RT_OK) return st;
-        RT_HIP(src, hipSetDevice(src->device), "selecting device");
-        if (sg->used) RT_HIP(src, hipStreamWaitEvent(src->multi_stream, sg->ev_free, 0), "ordering the copy behind the previous de-interleave");
-        if (src->launched) RT_HIP(src, hipStreamWaitEvent(src->multi_stream, src->ev_stop, 0), "ordering the gather behind the render");
-        RT_HIP(src, copy_between(sg->d.p, root->device, d_bands, src->device, L.compact_floats() * 4, src->multi_stream), "copying the rank's image to the root GPU");
-        RT_HIP(src, hipEventRecord(src->ev_multi, src->multi_stream), "recording the gather event");
-        RT_HIP(root, hipSetDevice(root->device), "selecting device");
-        RT_HIP(root, hipStreamWaitEvent(s0, src->ev_multi, 0), "ordering the de-interleave behind the copy");
-        from = sg->d.p;
-    } else {
-        RT_HIP(root, hipSetDevice(root->device), "selecting device");
-        if (src->launched) RT_HIP(root, hipStreamWaitEvent(s0, src->ev_stop, 0), "ordering the gather behind the render");
-    }
-    const uint32_t *d_list = nullptr;
-    if (L.listed && (st = device_tile_list(root, src_tiles->tile_list, L.num_tiles, s0, &d_list)) != RT_OK) return st;
-    RT_HIP(root, exchange(L, from, d_frame, true, d_list, s0), L.listed ? "de-interleaving tiles" : "de-interleaving bands");
-    if (sg) {
-        RT_HIP(root, hipEventRecord(sg->ev_free, s0), "recording the staging event");
-        sg->used = true;
-    }
-    return RT_OK;
-}
-
-namespace {
-
-/* what rank i of a multi-GPU call renders and where its image lives */
-struct RankPlan {
-    rt_ctx *c = nullptr;
-    const rt_scene *scene = nullptr;
-    rt_tile_spec spec;
-    rt_sched::Layout layout;             /* compact: the rank's bands, or its tile list */
-    const uint32_t *root_list = nullptr; /* tile lists: the rank's list on the ROOT's GPU (for the copies to and from the frame) */
-    Stage *stage = nullptr;              /* the root's landing area for the rank's image */
-};
-
-/* the arguments; then every rank's stream and event, and direct xGMI copies to and from the root where the platform allows
- * (instead of staging through the host).  Leaves the root's device current. */
-rt_status check_and_ready(rt_ctx *root, const std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
-                          int32_t n_frames, int32_t frame_num, int32_t band_rows, const float *d_frame)
-{
-    if (!cam || !rs || !times_ms || !d_frame || n_frames < 1 || frame_num < 0) return set_err(root, RT_ERR_INVALID, "null argument");
-    if (cam->width <= 0 || cam->height <= 0 || band_rows < 0 || (band_rows & 7)) return set_err(root, RT_ERR_INVALID, "bad image size or band_rows (0, or a positive multiple of 8)");
-    for (size_t i = 0; i < plan.size(); i++) {
-        if (!plan[i].c || !plan[i].scene || plan[i].scene->ctx != plan[i].c) return set_err(root, RT_ERR_INVALID, "rank without a context, or a scene committed on another context");
-        for (size_t j = 0; j < i; j++) if (plan[j].c == plan[i].c) return set_err(root, RT_ERR_INVALID, "a context may appear once (its launch scratch is not shared between ranks)");
-    }
-    rt_status st;
-    if ((st = multi_prepare(root)) != RT_OK) return st;
-    for (const RankPlan &p : plan) {
-        if ((st = multi_prepare(p.c)) != RT_OK) return set_err(root, st, rt_last_error(p.c));
-        (void)peer_access(p.c, root);
-    }
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
-    return RT_OK;
-}
-
-/* Cost-balanced ownership of the tiles, in root->multi.  A new view is dealt out interleaved, and the calls on it measure what
- * the tiles cost until one has done so.  The call after that collects every rank's figures (this waits for those launches,
- * which the caller has normally consumed already) and deals the tiles out again by cost.  All read-backs happen here,
- * before any rank is launched, so no rank's launch waits on another rank's kernel. */
-rt_status balance(rt_ctx *root, const std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs)
-{
-    MultiState &ms = root->multi;
-    const int n = (int)plan.size(), tiles_x = (cam->width + 7) / 8, tiles_y = (cam->height + 7) / 8;
-    /* (the bounce limit, and preview (< 8 samples) or real: ownership measured on the one says little about the other) */
-    std::vector<uint32_t> key;
-    push_camera(key, cam);
-    key.push_back((uint32_t)cam->width); key.push_back((uint32_t)cam->height); key.push_back((uint32_t)n);
-    key.push_back((uint32_t)rs->reflection_limit); key.push_back(rs->rays_per_pixel < 8 ? 0u : 1u);
-    for (const RankPlan &p : plan) { key.push_back(p.scene->uid); key.push_back((uint32_t)p.c->device); }
-    std::vector<int32_t> owner((size_t)tiles_x * tiles_y);
-    rt_status st;
-    if (key != ms.key || ms.lists.size() != (size_t)n) {
-        if ((st = rt_partition_tiles(nullptr, tiles_x, tiles_y, n, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
-        rt_sched::deal_tiles(owner, n, nullptr, nullptr, ms.lists, ms.costs, ms.peaks);
-        ms.key = key;
-        ms.owners = Owners::interleaved;
-    } else if (ms.owners == Owners::measured) {
-        std::vector<uint32_t> cost(owner.size(), 0u), peak(owner.size(), 0u);
-        bool have_all = true;
-        for (size_t i = 0; i < plan.size() && have_all; i++) {
-            const std::vector<uint32_t> &list = ms.lists[i];
-            if (list.empty()) continue;
-            std::vector<uint32_t> ids(list.size()), cs(list.size()), ps(list.size());
-            int32_t got = 0;
-            have_all = rt_tile_costs(plan[i].c, ids.data(), cs.data(), ps.data(), (int32_t)list.size(), &got) == RT_OK && (size_t)got == list.size() && ids == list;
-            for (size_t k = 0; k < list.size() && have_all; k++) { cost[ids[k]] = cs[k]; peak[ids[k]] = ps[k]; }
-        }
-        RT_HIP(root, hipSetDevice(root->device), "selecting device");
-        if (!have_all) { ms.owners = Owners::interleaved; return RT_OK; }    /* (a rank's context has rendered another view since: measure again) */
-        if ((st = rt_partition_tiles(cost.data(), tiles_x, tiles_y, n, owner.data())) != RT_OK) return set_err(root, st, "cannot partition the image");
-        rt_sched::deal_tiles(owner, n, cost.data(), peak.data(), ms.lists, ms.costs, ms.peaks);
-        ms.owners = Owners::balanced;
-    }
-    return RT_OK;
-}
-
-/* who renders what, each rank into a compact image (a tile list goes to the root's GPU as well) */
-rt_status plan_ranks(rt_ctx *root, std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs, int32_t band_rows, hipStream_t s0)
-{
-    const bool listed = band_rows == 0;
-    rt_status st;
-    if (listed && (st = balance(root, plan, cam, rs)) != RT_OK) return st;
-    const MultiState &ms = root->multi;
-    for (size_t i = 0; i < plan.size(); i++) {
-        RankPlan &p = plan[i];
-        std::memset(&p.spec, 0, sizeof p.spec);
-        p.spec.compact = 1;
-        if (listed) {
-            const bool costed = ms.owners == Owners::balanced && !ms.lists[i].empty();
-            static const uint32_t none = 0;      /* (an empty vector's data() may be null, which would read as "no list") */
-            p.spec.tile_list = ms.lists[i].empty() ? &none : ms.lists[i].data();
-            p.spec.num_tiles = (int32_t)ms.lists[i].size();
-            p.spec.tile_cost = costed ? ms.costs[i].data() : nullptr;
-            p.spec.tile_peak = costed ? ms.peaks[i].data() : nullptr;
-        } else {
-            p.spec.band_rows = band_rows; p.spec.band_first = (int32_t)i; p.spec.band_stride = (int32_t)plan.size();
-        }
-        p.layout = rt_sched::Layout(p.spec, cam->width, cam->height);
-        if (listed && (st = device_tile_list(root, p.spec.tile_list, p.spec.num_tiles, s0, &p.root_list)) != RT_OK) return st;
-    }
-    return RT_OK;
-}
-
-/* RT_AMD_MULTI_CAREFUL=1 (diagnosis): the host waits for every stream involved after each phase, so that no ordering between
- * devices rests on an event - if a frame is wrong or a call hangs in the asynchronous form but not in this one, the
- * fault is in the event choreography, otherwise in the copies themselves; an error names the phase it was found in.
- * bench.py's capi_multi leg falls back to it by itself (this path has never run on two physical GPUs). */
-rt_status careful(rt_ctx *root, const std::vector<RankPlan> &plan, hipStream_t s0, const char *phase)
-{
-    if (!root->multi_careful) return RT_OK;
-    for (const RankPlan &p : plan) {
-        hipError_t e = hipSetDevice(p.c->device);
-        if (e == hipSuccess) e = hipStreamSynchronize(p.c->multi_stream);
-        if (e != hipSuccess) { (void)hipSetDevice(root->device); return hip_fail(root, e, phase); }
-    }
-    hipError_t e = hipSetDevice(root->device);
-    if (e == hipSuccess) e = hipStreamSynchronize(s0);
-    if (e != hipSuccess) return hip_fail(root, e, phase);
-    return RT_OK;
-}
-
-/* The ranks' buffers, then their images travel and are rendered, in three phases.  (root->ev_multi is recorded twice: in the
- * first phase, on the caller's stream, as "the ranks may start", and in the second on rank 0's stream as "rank 0's image is
- * in the staging area"; a hipStreamWaitEvent captures the record that precedes it, and the calls are in that order.) */
-rt_status render_ranks(rt_ctx *root, std::vector<RankPlan> &plan, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
-                       int32_t n_frames, int32_t frame_num, float *d_frame, hipStream_t s0)
-{
-    /* ---- every rank's compact image on its GPU, and a landing area per rank on the root's */
-    rt_status st;
-    for (RankPlan &p : plan) {
-        const size_t floats = p.layout.compact_floats();
-        if (p.c->d_bands.cap < floats || !p.c->d_bands.p) {
-            RT_HIP(p.c, hipSetDevice(p.c->device), "selecting device");
-            RT_HIP(p.c, hipStreamSynchronize(p.c->multi_stream), "waiting for the rank's image buffer");
-            if (hipError_t e = p.c->d_bands.grow(floats)) return set_err(root, hip_fail(p.c, e, "allocating the rank's image buffer"), p.c->err);
-        }
-        if ((st = stage_for(root, p.c, floats, s0, &p.stage)) != RT_OK) return st;
-    }
-
-    /* ---- the image so far goes out to its owners, through their landing areas.  (Frame 0 ignores the buffers' content, but
-     * the landing areas may still be read by an earlier call's de-interleave: stage_for has ordered s0 behind that.) */
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
-    for (const RankPlan &p : plan)
-        if (frame_num > 0 && p.layout.compact_floats() > 0)
-            RT_HIP(root, exchange(p.layout, p.stage->d.p, d_frame, false, p.root_list, s0), p.layout.listed ? "interleaving tiles" : "interleaving bands");
-    RT_HIP(root, hipEventRecord(root->ev_multi, s0), "recording the start event");
-    if ((st = careful(root, plan, s0, "careful mode: waiting for the caller's stream before the ranks start")) != RT_OK) return st;
-    for (const RankPlan &p : plan) {
-        RT_HIP(p.c, hipSetDevice(p.c->device), "selecting device");
-        RT_HIP(p.c, hipStreamWaitEvent(p.c->multi_stream, root->ev_multi, 0), "ordering the ranks behind the caller's stream");
-        if (frame_num > 0)
-            RT_HIP(p.c, copy_between(p.c->d_bands.p, p.c->device, p.stage->d.p, root->device, p.layout.compact_floats() * 4, p.c->multi_stream), "copying the image so far to its owner");
-    }
-    if ((st = careful(root, plan, s0, "careful mode: waiting for the image so far to reach its owners (scatter-out)")) != RT_OK) return st;
-
-    /* ---- every rank renders its tiles (asynchronous launches from this one thread) and sends its image to its landing area */
-    for (const RankPlan &p : plan) {
-        const size_t floats = p.layout.compact_floats();
-        if (floats == 0) continue;
-        RT_HIP(p.c, hipSetDevice(p.c->device), "selecting device");
-        const int32_t cap = batch_cap(p.c, floats);
-        for (int32_t done = 0; done < n_frames;) {
-            const int32_t k = std::min<int32_t>(n_frames - done, cap);
-            st = rt_render_device_batch(p.c, p.scene, cam, rs, times_ms + done, k, frame_num + done, &p.spec, p.c->d_bands.p, p.c->multi_stream);
-            if (st != RT_OK) return set_err(root, st, rt_last_error(p.c));
-            done += k;
-        }
-        RT_HIP(p.c, copy_between(p.stage->d.p, root->device, p.c->d_bands.p, p.c->device, floats * 4, p.c->multi_stream), "copying the rank's image to the root GPU");
-        RT_HIP(p.c, hipEventRecord(p.c->ev_multi, p.c->multi_stream), "recording the gather event");
-    }
-    if ((st = careful(root, plan, s0, "careful mode: waiting for the ranks' kernels and their copies to the root GPU")) != RT_OK) return st;
-
-    /* ---- every rank's image into the frame, in s0's order behind its copy */
-    RT_HIP(root, hipSetDevice(root->device), "selecting device");
-    for (const RankPlan &p : plan) {
-        if (p.layout.compact_floats() == 0) continue;
-        RT_HIP(root, hipStreamWaitEvent(s0, p.c->ev_multi, 0), "ordering the de-interleave behind the copies");
-        RT_HIP(root, exchange(p.layout, p.stage->d.p, d_frame, true, p.root_list, s0), p.layout.listed ? "de-interleaving tiles" : "de-interleaving bands");
-        RT_HIP(root, hipEventRecord(p.stage->ev_free, s0), "recording the staging event");
-        p.stage->used = true;
-    }
-    return careful(root, plan, s0, "careful mode: waiting for the de-interleave into the frame");
-}
-
-}  // namespace
-
-/* n_frames consecutive progressive frames over n_ranks GPUs, accumulated in place in d_frame (a full
- * frame on ranks[0]'s GPU).  Replaces run_ray_tracer src/dispatch.cu:127-153 for a node: what one
- * device did there, n do here, each for the tiles it owns. */
-extern "C" rt_status rt_render_multi_device(const rt_rank *ranks, int32_t n_ranks, const rt_camera *cam, const rt_render_settings *rs,
-                                            const int32_t *times_ms, int32_t n_frames, int32_t frame_num, int32_t band_rows,
-                                            float *d_frame, void *hip_stream)
-{
-    if (!ranks || n_ranks < 1 || !ranks[0].ctx) return RT_ERR_INVALID;
-    rt_ctx *root = ranks[0].ctx;
-    hipStream_t s0 = (hipStream_t)hip_stream;
-    std::vector<RankPlan> plan((size_t)n_ranks);
-    for (int i = 0; i < n_ranks; i++) { plan[(size_t)i].c = ranks[i].ctx; plan[(size_t)i].scene = ranks[i].scene; }
-    rt_status st;
-    if ((st = check_and_ready(root, plan, cam, rs, times_ms, n_frames, frame_num, band_rows, d_frame)) != RT_OK) return st;
-    /* this call holds every rank's list on the root's GPU at once (the copies to and from the frame), and rank 0's launch
-     * looks its own up as well: what the cache hands out from here on is not recycled before the call has queued its work */
-    struct Pin { rt_ctx *c; explicit Pin(rt_ctx *c_) : c(c_) { pin_tile_lists(c); } ~Pin() { unpin_tile_lists(c); } } pin(root);
-    if ((st = plan_ranks(root, plan, cam, rs, band_rows, s0)) != RT_OK) return st;
-    const bool measuring = band_rows == 0 && root->multi.owners == Owners::interleaved;    /* (this call's launches measure the tiles) */
-    if ((st = render_ranks(root, plan, cam, rs, times_ms, n_frames, frame_num, d_frame, s0)) != RT_OK) return st;
-    if (measuring) root->multi.owners = Owners::measured;
-    return RT_OK;
-}
-
-/* render() src/dispatch.cu:156-163 for a node: host-buffer form of the above */
-extern "C" rt_status rt_render_multi(const rt_rank *ranks, int32_t n_ranks, const rt_camera *cam, const rt_render_settings *rs,
-                                     const int32_t *times_ms, int32_t n_frames, int32_t *frame_num, float *previous_render)
-{
-    if (!ranks || n_ranks < 1 || !ranks[0].ctx) return RT_ERR_INVALID;
-    rt_ctx *ctx = ranks[0].ctx;
-    if (!cam || !frame_num || !previous_render || !times_ms || n_frames < 1) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    if (cam->width <= 0 || cam->height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
-    rt_status st = ensure_frame_buffers(ctx, bytes);
-    if (st != RT_OK) return st;
-    RT_HIP(ctx, hipMemcpy(ctx->d_out.p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
-    st = rt_render_multi_device(ranks, n_ranks, cam, rs, times_ms, n_frames, *frame_num, 0, ctx->d_out.p, nullptr);
-    if (st != RT_OK) return st;
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    RT_HIP(ctx, hipStreamSynchronize(nullptr), "render kernels");
-    for (int i = 0; i < n_ranks; i++)
-        if ((st = rt_ctx_synchronize(ranks[i].ctx)) != RT_OK) return set_err(ctx, st, rt_last_error(ranks[i].ctx));
-    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
-    *frame_num += n_frames;
-    RT_HIP(ctx, hipPeekAtLastError(), "final check after render");
     return RT_OK;
 }
 

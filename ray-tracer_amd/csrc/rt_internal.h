@@ -1,9 +1,10 @@
 /*
- * rt_internal.h — what the translation units behind the C ABI share: the context and the committed scene (rt_ctx, rt_scene), the
- * device-buffer holder, the error helpers and, at the end, what the entry points beside the renderer (rt_query_capi.cpp,
- * rt_occlusion_capi.cpp, rt_denoise_capi.cpp) have in common: the argument checks, the context's launch bracket and the ray kernels'
- * argument block and launch.  rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed:
- * include/rt_amd.h is the interface.
+ * rt_internal.h — what the translation units behind the C ABI share: the holders that free HIP handles with their owner (DevBuf, Event,
+ * Stream), the context and its parts (rt_ctx: the tile-list cache, the view, the frame pipeline, the multi-GPU rank state, the knobs), the
+ * committed scene (rt_scene), the error helpers, the functions of rt_capi.cpp that rt_pipeline_capi.cpp and rt_multi_capi.cpp call, the
+ * host-buffer round trip and, at the end, what the entry points beside the renderer (rt_query_capi.cpp, rt_occlusion_capi.cpp,
+ * rt_denoise_capi.cpp) have in common: the argument checks, the context's launch bracket and the ray kernels' argument block and launch.
+ * rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed: include/rt_amd.h is the interface.
  */
 #pragma once
 
@@ -12,12 +13,16 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "rt_host.h"
 #include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
 #include "rt_schedule.h"
+
+/* what crosses the library's translation units without being part of its interface: not in the dynamic symbol table */
+#define RT_HIDDEN __attribute__((visibility("hidden")))
 
 namespace rt_detail {
 
@@ -41,6 +46,27 @@ template <class T> struct DevBuf {
     }
 };
 
+/* A HIP event and a HIP stream, created by whoever uses them first (null until then) and destroyed with their owner.  The stream
+ * is synchronised first: what is still queued on it may use its owner's buffers and events, so in a struct the stream goes LAST
+ * (members go in reverse order). */
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    operator hipStream_t() const { return s; }
+};
+
 /* a tile list on the device, found again by content (lists are a few KB to ~130 KB and change only with the view).
  * `host` is a pinned copy: what a hash hit is compared with (a 64-bit hash alone would render the wrong
  * tiles on a collision) and what the asynchronous upload reads.  An entry is recycled least-recently-used first; the
@@ -50,21 +76,35 @@ struct DevList {
     int n = 0;
     DevBuf<uint32_t> d;
     uint32_t *host = nullptr;            /* pinned, d.cap entries */
-    uint64_t seq = 0;                    /* rt_ctx::list_seq when last handed out (LRU order; > pin_floor: not recyclable) */
-    hipStream_t stream = nullptr;        /* the stream of the launches it was last handed out for */
-    hipEvent_t ev = nullptr;             /* scratch: "everything queued on `stream` so far" (orders a reuse on another stream) */
-    hipEvent_t ev_up = nullptr;          /* "the upload from `host` is done": the pinned copy may be rewritten */
-    ~DevList() { clear(); if (ev) (void)hipEventDestroy(ev); if (ev_up) (void)hipEventDestroy(ev_up); }
+    uint64_t seq = 0;                    /* TileListCache::seq when last handed out (LRU order; > pin_floor: not recyclable) */
+    hipStream_t stream = nullptr;        /* the stream of the launches it was last handed out for (the caller's: not owned) */
+    Event ev;                            /* scratch: "everything queued on `stream` so far" (orders a reuse on another stream) */
+    Event ev_up;                         /* "the upload from `host` is done": the pinned copy may be rewritten */
+    ~DevList() { clear(); }
     /* no content and no buffers: what every failure leaves behind */
     void clear() { d.release(); if (host) (void)hipHostFree(host); host = nullptr; n = 0; hash = 0; }
+};
+
+/* The context's tile lists on its GPU, content-addressed (rt_capi.cpp).  Errors are reported through the owning context. */
+struct TileListCache {
+    std::deque<DevList> lists;           /* (a deque: an entry stays where it is while others are added) */
+    size_t cap = 64;                     /* cached tile lists; beyond that the least recently used entry is recycled (raised when one call pins more) */
+    uint64_t seq = 0, pin_floor = ~0ull; /* entries handed out after pin_floor are held by the running call (rt_render_multi_device) */
+    RT_HIDDEN rt_status on_device(rt_ctx *ctx, const uint32_t *list, int n, hipStream_t stream, const uint32_t **out);
+    /* A call that holds several lists at once (rt_render_multi_device: every rank's list on the root) pins what it is handed
+     * while this lives: pinned entries are not recycled, the cache grows instead.  It goes when the call has queued its work. */
+    struct Pin {
+        TileListCache &c;
+        explicit Pin(TileListCache &c_) : c(c_) { c.pin_floor = c.seq; }
+        ~Pin() { c.pin_floor = ~0ull; }
+    };
 };
 
 /* the root's landing area for one source context's compact image (rt_gather, rt_render_multi_device) */
 struct Stage {
     DevBuf<float> d;
-    hipEvent_t ev_free = nullptr;        /* recorded on the root's stream after the last de-interleave that read the area */
+    Event ev_free;                       /* recorded on the root's stream after the last de-interleave that read the area */
     bool used = false;
-    ~Stage() { if (ev_free) (void)hipEventDestroy(ev_free); }
 };
 
 /* cost-balanced multi-GPU calls: a new view's interleaved deal (calls on it measure the tiles), measured, dealt by cost */
@@ -75,6 +115,18 @@ struct MultiState {
     std::vector<uint32_t> key;           /* camera, image size, number of ranks, scene ids */
     Owners owners = Owners::interleaved;
     std::vector<std::vector<uint32_t>> lists, costs, peaks;   /* per rank: its tiles (image indices), their measured costs and peak pixel costs */
+};
+
+/* a context as a rank of the multi-GPU entry points (rt_multi_capi.cpp): its compact buffer, its stream and "my image is in the
+ * root's staging area" event; on the root also the staging areas, one per source context, and the ownership of the tiles */
+struct MultiRank {
+    DevBuf<float> d_bands;
+    std::map<rt_ctx *, Stage> stages;
+    Event ev;
+    MultiState state;
+    std::map<int, int> peer_ok;          /* device -> 1 direct access both ways, 0 refused */
+    int careful = 0;                     /* RT_AMD_MULTI_CAREFUL=1: rt_render_multi_device waits on the host after every phase (diagnosis) */
+    Stream stream;
 };
 
 /* where the measured tile costs of the current view are */
@@ -98,74 +150,74 @@ struct View {
     int job_frames = 0;                  /* what the uploaded schedule was built for */
 };
 
-}  // namespace rt_detail
-using namespace rt_detail;
-
-/* One frame in flight of the pipelined per-frame entry points (rt_frame_submit / rt_frame_collect): everything a launch
- * writes that the context otherwise holds once - its stream, its ticket counter, the plane its pixels' means go to. */
-struct FrameSlot {
-    hipStream_t stream = nullptr;
-    uint32_t *counter = nullptr;        /* 1 KB like rt_ctx::tile_counter */
-    DevBuf<float> plane;
-    hipEvent_t ev_done = nullptr;       /* the frame's render kernel has finished (recorded on `stream`) */
-    hipEvent_t ev_free = nullptr;       /* the blend that read the plane has finished (recorded on `stream` too: the blend runs there) */
-    hipEvent_t ev_call = nullptr;       /* where the collector's stream stood when it asked for the frame */
-    bool used = false, folded = false;  /* ev_done / ev_free have been recorded at least once */
-    rt_sched::Layout layout;            /* the launch's output layout: how rt_frame_collect folds the plane into the caller's frame */
-};
-
-struct Pipeline {
-    FrameSlot slots[RT_PIPELINE_DEPTH];
-    int order[RT_PIPELINE_DEPTH];       /* submitted and not collected, oldest first */
-    int pending = 0;
-    int depth = RT_PIPELINE_DEFAULT_DEPTH;   /* rt_frame_depth: how many frames the caller keeps in flight */
-    int last_fold = -1;                 /* the slot whose frame was folded last (folds into one frame happen in collection order) */
-    DevBuf<uint32_t> d_list;            /* the view's tile list (listed tile specs), shared by the frames in flight */
-    std::vector<uint32_t> list_host;
-};
-
-struct rt_ctx {
-    int device = 0;
-    int num_cus = 0;
-    size_t total_mem = 0;
-    std::string err;
-    uint32_t *tile_counter = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool have_timing = false;
-    /* The launch scratch below (ticket counter, per-frame planes, tile order / costs, the two events) is
-     * per context, so launches of one context are kept in order: a launch on another stream than the
-     * previous one first waits for that one's stop event (one launch in flight per context). */
-    hipStream_t last_stream = nullptr;
-    bool launched = false;
-    /* multi-GPU entry points (rt_render_multi*): this rank's compact buffer, its stream and "my image is in the root's
-     * staging area" event; on the root also the staging areas, one per source context */
-    DevBuf<float> d_bands;
-    std::map<rt_ctx *, Stage> stages;
-    hipStream_t multi_stream = nullptr;
-    hipEvent_t ev_multi = nullptr;
-    MultiState multi;
-    std::map<int, int> peer_ok;          /* device -> 1 direct access both ways, 0 refused */
-    /* persistent frame buffers for the host-buffer entry point */
-    DevBuf<float> d_prev, d_out;
-    View view;
-    DevBuf<float> d_partial;             /* multi-frame launches: one plane of per-pixel frame means per frame; the pilot's scratch plane */
-    std::deque<DevList> dev_lists;       /* (a deque: an entry stays where it is while others are added) */
-    size_t dev_list_cap = 64;            /* cached tile lists; beyond that the least recently used entry is recycled (raised when one call pins more) */
-    uint64_t list_seq = 0, pin_floor = ~0ull;   /* entries handed out after pin_floor are held by the running call (rt_render_multi_device) */
-    /* knobs (RT_AMD_*), none changes an image */
+/* knobs (RT_AMD_*), none changes an image */
+struct Knobs {
     int work_threshold = RT_DEF_WORK_THRESHOLD;      /* lanes; RT_AMD_WORK_THRESHOLD */
     int descend_keep = RT_DEF_DESCEND_KEEP;       /* RT_AMD_DESCEND_KEEP (0..64): 0 = run every descent to its end */
     int ready_break = RT_DEF_READY_BREAK;        /* lanes; RT_AMD_READY_BREAK; 65 = never */
     int hit_break = RT_DEF_HIT_BREAK;          /* lanes; RT_AMD_HIT_BREAK */
     int hit_low = RT_DEF_HIT_LOW, mix_break = -1;                 /* RT_AMD_HIT_LOW, RT_AMD_MIX_BREAK (0 = that rule off; -1 = not set: the default of the scene's workgroup shape) */
     int shade_batch = RT_DEF_SHADE_BATCH;        /* lanes; RT_AMD_SHADE_BATCH (1..64) */
-    Pipeline pipe;
+};
+
+}  // namespace rt_detail
+using namespace rt_detail;
+
+/* One frame in flight of the pipelined per-frame entry points (rt_frame_submit / rt_frame_collect): everything a launch
+ * writes that the context otherwise holds once - its stream, its ticket counter, the plane its pixels' means go to.
+ * (The stream goes last: it is synchronised before what its work uses is released.) */
+struct FrameSlot {
+    DevBuf<uint32_t> counter;           /* 1 KB like rt_ctx::tile_counter */
+    DevBuf<float> plane;
+    Event ev_done;                      /* the frame's render kernel has finished (recorded on `stream`) */
+    Event ev_free;                      /* the blend that read the plane has finished (recorded on `stream` too: the blend runs there) */
+    Event ev_call;                      /* where the collector's stream stood when it asked for the frame */
+    bool used = false, folded = false;  /* ev_done / ev_free have been recorded at least once */
+    rt_sched::Layout layout;            /* the launch's output layout: how rt_frame_collect folds the plane into the caller's frame */
+    Stream stream;
+};
+
+struct Pipeline {
+    int order[RT_PIPELINE_DEPTH];       /* submitted and not collected, oldest first */
+    int pending = 0;
+    int depth = RT_PIPELINE_DEFAULT_DEPTH;   /* rt_frame_depth: how many frames the caller keeps in flight */
+    int last_fold = -1;                 /* the slot whose frame was folded last (folds into one frame happen in collection order) */
+    DevBuf<uint32_t> d_list;            /* the view's tile list (listed tile specs), shared by the frames in flight */
+    std::vector<uint32_t> list_host;
+    FrameSlot slots[RT_PIPELINE_DEPTH]; /* (last: their streams are synchronised before d_list goes) */
+};
+
+/* Members go in reverse order, and rt_ctx_destroy relies on it: a stream is synchronised (Stream) before any buffer or event
+ * that work queued on it may use is released.  So the two parts that own streams come last - the frames in flight read the
+ * view, the rank's stream runs launches that use everything above it - and inside each part the stream is the last member.
+ * (A frame's stream may still hold a wait for a younger slot's event that is already gone: the runtime keeps a destroyed
+ * event until the waits queued on it have passed.) */
+struct rt_ctx {
+    int device = 0;
+    int num_cus = 0;
+    size_t total_mem = 0;
+    std::string err;
+    DevBuf<uint32_t> tile_counter;      /* 1 KB: the ticket counter, and from tile_counter + 16 the 48 x u64 of a -DRT_STATS build */
+    Event ev_start, ev_stop;
+    bool have_timing = false;
+    /* The launch scratch below (ticket counter, per-frame planes, tile order / costs, the two events) is
+     * per context, so launches of one context are kept in order: a launch on another stream than the
+     * previous one first waits for that one's stop event (one launch in flight per context). */
+    hipStream_t last_stream = nullptr;
+    bool launched = false;
+    /* persistent frame buffers for the host-buffer entry point */
+    DevBuf<float> d_prev, d_out;
+    View view;
+    DevBuf<float> d_partial;             /* multi-frame launches: one plane of per-pixel frame means per frame; the pilot's scratch plane */
+    TileListCache tile_lists;
+    Knobs knobs;
     /* the host-buffer forms of the ray queries and the AOV pass (rt_query_capi.cpp): the rays on the device, and the records / planes */
     DevBuf<float> d_query_in;
     DevBuf<rt_f4> d_query_out;
     /* rt_denoise[_device] (rt_denoise_capi.cpp): per pixel the guide record and the two colour records the levels alternate between */
     DevBuf<rt_f4> d_denoise;
-    int multi_careful = 0;                       /* RT_AMD_MULTI_CAREFUL=1: rt_render_multi_device waits on the host after every phase (diagnosis) */
+    Pipeline pipe;
+    MultiRank multi;
 };
 
 
@@ -199,6 +251,44 @@ inline rt_status set_err(rt_ctx *ctx, rt_status code, const std::string &msg)
     if (ctx) ctx->err = msg;
     return code;
 }
+
+/* ---- what rt_pipeline_capi.cpp and rt_multi_capi.cpp call in rt_capi.cpp --------------------------------------------------------- */
+namespace rt_detail {
+
+/* guards the set of live contexts and every root's rt_ctx::multi.stages: rt_ctx_destroy of a source erases its entry there */
+extern RT_HIDDEN std::mutex g_ctx_mutex;
+
+RT_HIDDEN rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
+                                  const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
+                                  const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot = nullptr);
+RT_HIDDEN rt_status fold(rt_ctx *ctx, const rt_sched::Layout &L, const float *planes, int n_frames, int frame_num, float *d_out, const uint32_t *d_tile_list,
+                         hipStream_t stream);
+RT_HIDDEN rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes);
+RT_HIDDEN int batch_cap(const rt_ctx *ctx, size_t plane_floats);
+RT_HIDDEN void push_camera(std::vector<uint32_t> &key, const rt_camera *cam);
+
+/* The host-buffer forms' round trip (render() src/dispatch.cu:156-163): the caller's frame goes into the persistent buffer `into`
+ * (d_prev or d_out), `render_and_wait(bytes)` renders n_frames frames into d_out and waits for them, the frame comes back and
+ * *frame_num advances. */
+template <class Render>
+rt_status host_round_trip(rt_ctx *ctx, const rt_camera *cam, int32_t n_frames, int32_t *frame_num, float *previous_render, DevBuf<float> rt_ctx::*into,
+                          Render render_and_wait)
+{
+    if (!ctx || !cam || !frame_num || !previous_render) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    if (cam->width <= 0 || cam->height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    const size_t bytes = (size_t)cam->width * (size_t)cam->height * 3 * sizeof(float);
+    rt_status st = ensure_frame_buffers(ctx, bytes);
+    if (st != RT_OK) return st;
+    RT_HIP(ctx, hipMemcpy((ctx->*into).p, previous_render, bytes, hipMemcpyHostToDevice), "copying previous frame");
+    if ((st = render_and_wait(bytes)) != RT_OK) return st;
+    RT_HIP(ctx, hipMemcpy(previous_render, ctx->d_out.p, bytes, hipMemcpyDeviceToHost), "copying frame to host");
+    *frame_num += n_frames;                            /* src/dispatch.cu:159 */
+    RT_HIP(ctx, hipPeekAtLastError(), "final check after render");   /* src/dispatch.cu:161-162 */
+    return RT_OK;
+}
+
+}  // namespace rt_detail
 
 /* ---- argument checks shared by the entry points ------------------------------------------------------------------------------- */
 inline rt_status check_scene(rt_ctx *ctx, const rt_scene *scene)
@@ -266,10 +356,10 @@ Args ray_args_scene(const rt_ctx *ctx, const rt_scene *scene, uint32_t n)
     a.off_objtab = scene->flat.off_objtab;
     a.num_objects = (int32_t)scene->flat.objects.size();
     a.num_meshes = scene->flat.num_meshes;
-    a.descend_keep = ctx->descend_keep;
+    a.descend_keep = ctx->knobs.descend_keep;
     a.n = n;
     a.num_chunks = (n + 63u) / 64u;
-    a.counter = ctx->tile_counter;
+    a.counter = ctx->tile_counter.p;
     return a;
 }
 

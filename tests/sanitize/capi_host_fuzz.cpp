@@ -1,7 +1,7 @@
-// The GPU-free entry points of rt_capi.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; test infrastructure):
+// The GPU-free entry points of rt_capi.cpp, rt_pipeline_capi.cpp and rt_multi_capi.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; test infrastructure):
 // rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule, the output layout and
 // the kernel shape choice (rt_schedule.h) with their properties asserted, and every entry point's refusal of null / bad
-// arguments before it touches HIP.  rt_capi.cpp is compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
+// arguments before it touches HIP.  The three files are compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
 // kernel launchers (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
 #include <algorithm>
 #include <cmath>

@@ -319,6 +319,48 @@ def test_multi_device_careful_mode_renders_the_same_frames(rt, monkeypatch):
     assert eq(frames["1"], single.previous_render)
 
 
+def test_contexts_go_with_every_part_in_use(rt):
+    """rt_ctx_destroy frees what a context owns through its members' destructors, streams first.  Two contexts, each
+    with everything that is created on demand: the root has a pipelined frame still in flight (a slot's stream, counter,
+    plane and events) and one collected, and a cost-balanced rt_render_multi_device call over both has given the root a
+    staging area per rank and cached tile lists, and both their rank streams.  The source goes first (its staging area
+    on the root goes with it), then the root; a fresh context then renders the same frame.  three_sphere at 16x16: four
+    tiles, the smallest image with more than one tile per rank - what is under test is host bookkeeping."""
+    import weakref
+    import torch
+    objs, sky = rt.scenes.three_sphere()
+    W = H = 16
+    cam, rd, times = rt.Camera(W, H), rt.RenderData(1, 2, True, sky), [31, 32]
+    so = rt.SceneObjects(objs)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def batch_frame(ctx, scene):
+        out = torch.zeros((H, W, 3), device="cuda:0")
+        rt.render_device_batch(ctx, scene, cam, rd, times, 0, out.data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    root, src = rt.Context(0), rt.Context(0)
+    s_root, s_src = root.commit(so), src.commit(so)
+    want = batch_frame(root, s_root)
+    piped = torch.zeros((H, W, 3), device="cuda:0")
+    rt.frame_submit(root, s_root, cam, rd, times[0])
+    rt.frame_submit(root, s_root, cam, rd, times[1])
+    rt.frame_collect(root, 0, piped.data_ptr(), stream=st)
+    assert rt.frames_pending(root) == 1
+    multi = torch.zeros((H, W, 3), device="cuda:0")
+    rt.render_multi_device([root, src], [s_root, s_src], cam, rd, times, 0, multi.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    assert eq(multi.cpu().numpy(), want)
+    gone = [weakref.ref(src), weakref.ref(root)]
+    del s_src, src
+    assert gone[0]() is None and gone[1]() is not None
+    del s_root, root
+    assert gone[1]() is None
+    fresh = rt.Context(0)
+    assert eq(batch_frame(fresh, fresh.commit(so)), want)
+
+
 def test_preview_quality_costs_are_measured_again(rt):
     """a view's tile costs used to be measured once - a first launch at 1 sample per pixel (a preview, a profiler's warm-up)
     then fixed the schedule and the GPU ownership of every later launch.  Now figures from a launch with an eighth of the samples or

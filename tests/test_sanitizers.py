@@ -48,7 +48,7 @@ def test_a_face_naming_a_missing_vertex_is_an_error_not_a_read(rt, tmp_path):
 
 
 def test_gpu_free_entry_points_of_the_c_abi_under_asan_and_ubsan(tmp_path):
-    """rt_capi.cpp as host C++ (kernel launchers stubbed out): rt_partition_tiles on random costs and sizes, rt_tile_owned_rows, and
+    """rt_capi.cpp, rt_pipeline_capi.cpp and rt_multi_capi.cpp as host C++ (kernel launchers stubbed out): rt_partition_tiles on random costs and sizes, rt_tile_owned_rows, and
     every entry point handed null / bad arguments - refused before HIP is touched, sanitizers silent"""
     gxx = shutil.which("g++")
     rocm = "/opt/rocm"
@@ -58,6 +58,7 @@ def test_gpu_free_entry_points_of_the_c_abi_under_asan_and_ubsan(tmp_path):
     cmd = [gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
            "-I", os.path.join(rocm, "include"), "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "ray-tracer_amd", "csrc"),
            os.path.join(ROOT, "tests", "sanitize", "capi_host_fuzz.cpp"), os.path.join(ROOT, "ray-tracer_amd", "csrc", "rt_capi.cpp"),
+           os.path.join(ROOT, "ray-tracer_amd", "csrc", "rt_pipeline_capi.cpp"), os.path.join(ROOT, "ray-tracer_amd", "csrc", "rt_multi_capi.cpp"),
            os.path.join(ROOT, "ray-tracer_amd", "csrc", "rt_host.cpp"), "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
            "-Wl,-rpath," + os.path.join(rocm, "lib"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
