@@ -21,6 +21,82 @@ def test_header_and_binding_agree(rt):
     assert declared_symbols() == sorted(rt.ABI_SYMBOLS)
 
 
+def c_kind(decl, is_return=False):
+    """a C parameter declaration (or a return type) -> pointer / float / int32 / int64 / void"""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    (base,) = words if is_return else words[:-1]          # a parameter's last word is its name
+    return {"float": "float", "int32_t": "int32", "rt_status": "int32", "int64_t": "int64", "void": "void"}[base]
+
+
+def declared_prototypes():
+    """include/rt_amd.h -> [(name, return kind, [parameter kinds])] in the header's order"""
+    text = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
+    protos = []
+    for statement in text.split(";"):
+        m = re.search(r"([\w\s\*]+?)\b(rt_[a-z0-9_]+)\s*\((.*)\)\s*$", statement, flags=re.S)
+        if m:
+            ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+            params = [] if params == "void" else [p.strip() for p in params.split(",")]
+            protos.append((name, c_kind(ret, is_return=True), [c_kind(p) for p in params]))
+    return protos
+
+
+def ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_float: "float", ctypes.c_int32: "int32", ctypes.c_int64: "int64"}[t]
+
+
+def abi_module():
+    import importlib
+    return importlib.import_module("ray-tracer_amd._abi")
+
+
+def test_signature_table_agrees_with_the_header(rt):
+    """every function's return and every parameter, in number and kind - not only the names"""
+    protos = declared_prototypes()
+    table = abi_module().ABI
+    assert [p[0] for p in protos] == list(table) == rt.ABI_SYMBOLS          # the header's order, each function once
+    assert ctypes.sizeof(ctypes.c_int32) == 4 and ctypes.sizeof(ctypes.c_int64) == 8 and ctypes.sizeof(ctypes.c_float) == 4
+    for name, ret, params in protos:
+        restype, argtypes = table[name]
+        assert ctypes_kind(restype) == ret, name
+        assert len(argtypes) == len(params), name
+        assert [ctypes_kind(a) for a in argtypes] == params, name
+
+
+def test_header_parser_sees_the_kinds():
+    """the parser itself, on prototypes read by eye"""
+    protos = {p[0]: p[1:] for p in declared_prototypes()}
+    assert protos["rt_version"] == ("pointer", [])
+    assert protos["rt_material_checkerboard"] == ("void", ["pointer", "pointer", "pointer", "int32", "float"])
+    assert protos["rt_trace_rays"] == ("int32", ["pointer", "pointer", "pointer", "pointer", "int64", "pointer"])
+    assert protos["rt_frames_pending"] == ("int32", ["pointer"])
+    assert protos["rt_debug_exhaustive"] == ("int32", ["pointer", "pointer"])
+
+
+def test_applying_the_table_skips_missing_symbols(rt):
+    """a library of an older revision (loaded through RT_AMD_LIB) lacks the newer entry points: the rest is still declared"""
+    import types
+    abi = abi_module()
+    present = ["rt_render", "rt_version", "rt_obj_destroy"]
+    stand_in = types.SimpleNamespace(**{n: types.SimpleNamespace() for n in present})
+    abi.apply_abi(stand_in)
+    assert sorted(vars(stand_in)) == sorted(present)
+    for n in present:
+        assert (getattr(stand_in, n).restype, getattr(stand_in, n).argtypes) == abi.ABI[n]
+    L = rt.lib()
+    for name, (restype, argtypes) in abi.ABI.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype is restype, name
+
+
 def test_library_exports_every_declared_symbol(rt):
     L = rt.lib()
     for name in declared_symbols():
