@@ -78,6 +78,8 @@ def lib():
     L.orc_add_mesh_faces.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Material)]
     L.orc_mesh_bvh_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     L.orc_trace_one.argtypes = [C.c_void_p, f3, f3, f3]
+    L.orc_trace_one_uv.argtypes = [C.c_void_p, f3, f3, f3]
+    L.orc_mesh_bvh_dump.argtypes = [C.c_void_p, C.c_int, f3, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.orc_obj_load.restype = C.c_void_p
     L.orc_obj_load.argtypes = [C.c_char_p, C.c_int]
     L.orc_obj_free.argtypes = [C.c_void_p]
@@ -239,6 +241,28 @@ class Scene:
         if lib().orc_mesh_bvh_info(self._h, object_index, C.byref(n), hist, hist_len) != 0:
             raise ValueError("not a mesh")
         return n.value, list(hist)
+
+    def bvh_dump(self, object_index):
+        """The mesh's whole tree in array order: dict(boxes[n,6], left[n], right[n], count[n], root, list)."""
+        n, _ = self.bvh_info(object_index)
+        total = lib().orc_mesh_bvh_dump(self._h, object_index, None, None, None, None)
+        boxes = np.zeros((n, 6), np.float32)
+        links = np.zeros((n, 3), np.int32)
+        lst = np.zeros(max(total, 1), np.int32)
+        root = C.c_int()
+        ip = C.POINTER(C.c_int)
+        lib().orc_mesh_bvh_dump(self._h, object_index, boxes.ctypes.data_as(C.POINTER(C.c_float)), links.ctypes.data_as(ip),
+                                lst.ctypes.data_as(ip), C.byref(root))
+        return {"boxes": boxes, "left": links[:, 0].copy(), "right": links[:, 1].copy(), "count": links[:, 2].copy(),
+                "root": root.value, "list": lst[:total]}
+
+    def trace_one_uv(self, origin, direction):
+        """-> hit, {dist, hit point xyz, normal xyz, object index, u, v}; u, v are 0 unless the winner's material has need_uv"""
+        _, o = _f3(origin)
+        _, d = _f3(direction)
+        out = np.zeros(10, np.float32)
+        hit = lib().orc_trace_one_uv(self._h, o, d, out.ctypes.data_as(C.POINTER(C.c_float)))
+        return bool(hit), out
 
     def trace_one(self, origin, direction):
         _, o = _f3(origin)

@@ -675,6 +675,51 @@ int orc_trace_one(const orc_scene *s, const float origin[3], const float dir[3],
     return h.hits;
 }
 
+/* orc_trace_one plus the texture coordinates the winner's material asks for (need_uv): the sphere's
+ * latitude / longitude through the scene's math binding, a triangle's interpolated vertex coordinates.
+ * out = {dist, hit_point xyz, normal xyz, object index, u, v} */
+int orc_trace_one_uv(const orc_scene *s, const float origin[3], const float dir[3], float out[10])
+{
+    orc_stats st; memset(&st, 0, sizeof st);
+    ray_t ray; memset(&ray, 0, sizeof ray);
+    ray.origin = v3_from(origin);
+    ray_change_direction(&ray, v3_from(dir));
+    const object_t *ob = NULL;
+    hit_t h = scene_collision(s, &ray, &ob, &st);
+    if (h.hits && ob->type == OBJ_SPHERE && ob->mat.need_uv) {
+        if (s->math_mode == ORC_MATH_DET) sphere_uv_det(ob, &h); else sphere_uv_libm(ob, &h);
+    }
+    out[0] = h.dist;
+    out[1] = h.point.x; out[2] = h.point.y; out[3] = h.point.z;
+    out[4] = h.normal.x; out[5] = h.normal.y; out[6] = h.normal.z;
+    out[7] = h.hits ? (float)(ob - s->objs) : -1;
+    out[8] = h.u; out[9] = h.v;
+    return h.hits;
+}
+
+/* the whole tree of a mesh, nodes in array order (post-order, src/objects.cu:602-624): boxes = bl_near, tr_far;
+ * links = left, right, triangle count; list = the nodes' triangle index lists one after the other.  Returns
+ * the length of the list (call with NULL arrays first to size them), -1 if the object is no mesh. */
+int orc_mesh_bvh_dump(const orc_scene *s, int object_index, float *boxes, int *links, int *list, int *root)
+{
+    if (object_index < 0 || object_index >= s->nobjs || s->objs[object_index].type != OBJ_MESH) return -1;
+    const mesh_t *m = &s->objs[object_index].mesh;
+    int total = 0;
+    for (int i = 0; i < m->nnodes; i++) {
+        const node_t *n = &m->nodes[i];
+        if (boxes) {
+            float *b = boxes + 6 * i;
+            b[0] = n->box.bl.x; b[1] = n->box.bl.y; b[2] = n->box.bl.z;
+            b[3] = n->box.tr.x; b[4] = n->box.tr.y; b[5] = n->box.tr.z;
+        }
+        if (links) { links[3 * i] = n->left; links[3 * i + 1] = n->right; links[3 * i + 2] = n->ntris; }
+        if (list) memcpy(list + total, n->tri_idx, sizeof(int) * (size_t)n->ntris);
+        total += n->ntris;
+    }
+    if (root) *root = m->root;
+    return total;
+}
+
 /* ------------------------------------------------------------------------------------------
  * Host matrices — src/matrix.cu (float, naive triple loop, sum starts at 0)
  * ---------------------------------------------------------------------------------------- */

@@ -10,7 +10,8 @@
  * Two math bindings ("modes") of the SAME restatement:
  *   ORC_MATH_LIBM (0): log/cos/sin/tan come from the platform libm, as in the reference when
  *                      its sources are compiled for the CPU.  Used to pin the restatement
- *                      against the reference outputs recorded in SURVEY.md App. A.12 / C.2.
+ *                      against what the reference's own CPU build computes (tests/golden/ref/, made
+ *                      by oracle/ref_build.py's programs) and the outputs SURVEY.md App. A.12 / C.2 recorded.
  *   ORC_MATH_DET  (1): the same calls are bound to ray-tracer_amd/csrc/rt_math.h, the
  *                      deterministic functions the HIP kernel uses.  This is the mode the GPU
  *                      result is compared with bit for bit.
@@ -88,6 +89,14 @@ int orc_mesh_bvh_info(const orc_scene *s, int object_index, int *num_nodes, int 
 /* closest hit of one ray against the whole scene (for brute-force cross-checks):
  * returns 1 on hit; out = {dist, hit_point xyz, normal xyz, object index} */
 int orc_trace_one(const orc_scene *s, const float origin[3], const float dir[3], float out[8]);
+
+/* orc_trace_one plus the winner's texture coordinates where its material has need_uv (0, 0 elsewhere):
+ * out = {dist, hit_point xyz, normal xyz, object index, u, v} */
+int orc_trace_one_uv(const orc_scene *s, const float origin[3], const float dir[3], float out[10]);
+/* the whole tree of a mesh in array order: boxes (6 per node: bl_near, tr_far), links (3 per node: left, right,
+ * triangle count), list (the nodes' triangle index lists, concatenated).  Any array may be NULL; returns the
+ * list's length, -1 if the object is no mesh. */
+int orc_mesh_bvh_dump(const orc_scene *s, int object_index, float *boxes, int *links, int *list, int *root);
 
 /* .obj loader + transforms: reference src/obj_read.cu:8-147, src/matrix.cu */
 orc_obj *orc_obj_load(const char *path, int math_mode);   /* NULL if the file cannot be opened */

@@ -1,8 +1,9 @@
 """Pins the CPU oracle to the reference.
 
-The reference has no tests and no golden vectors and cannot be built in this
-image (CUDA + SFML).  What exists are outputs the reference itself produced when its sources
-were compiled CPU-only in this container during the survey, recorded in SURVEY.md:
+The reference has no tests and no golden vectors.  These are the pins to the
+outputs the reference itself produced when its sources were compiled CPU-only during the
+survey, recorded in SURVEY.md (tests/test_reference_pin.py holds the pins to fixtures that
+oracle/ref_build.py's committed recipe produces from the reference's sources):
   App. C.3  PCG known answers
   App. A.12 camera floats at 256x256 / 1920x1080 / 3840x2160
   §4        BVH node count and leaf-size histograms for cube.obj / low_poly_monkey.obj

@@ -1,9 +1,12 @@
 """Generates tests/golden/* from the CPU oracle (run in the build container; commit the output).
 
-The oracle is pinned to the reference first (tests/test_oracle_pin.py: in libm mode it
-reproduces the reference outputs recorded in SURVEY.md); the fixtures written here come from
-its det mode (transcendentals from rt_math.h), which is what the HIP kernel must equal bit
-for bit.  Nothing here reads /root/reference.
+The oracle is pinned to the reference first: in libm mode it equals, bit for bit, the frames,
+hit records, trees and camera floats that the reference's own programs produced
+(tests/golden/ref/, written by tools/make_reference_golden.py from oracle/ref_build.py's CPU
+build of the reference; tests/test_reference_pin.py) and the outputs SURVEY.md recorded
+(tests/test_oracle_pin.py).  The fixtures written HERE are not reference outputs: they come
+from the oracle's det mode (transcendentals from rt_math.h), which is what the HIP kernel
+must equal bit for bit.  Nothing here reads the reference.
 """
 import hashlib
 import importlib
