@@ -166,13 +166,7 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     ctx->num_cus = prop.multiProcessorCount;
     ctx->total_mem = prop.totalGlobalMem;
     Knobs &k = ctx->knobs;
-    k.work_threshold = env_int("RT_AMD_WORK_THRESHOLD", 1, 64, k.work_threshold);
-    k.descend_keep = env_int("RT_AMD_DESCEND_KEEP", 0, 64, k.descend_keep);
-    k.hit_break = env_int("RT_AMD_HIT_BREAK", 1, 65, k.hit_break);
-    k.hit_low = env_int("RT_AMD_HIT_LOW", 0, 65, k.hit_low);
-    k.mix_break = env_int("RT_AMD_MIX_BREAK", 0, 130, k.mix_break);
-    k.shade_batch = env_int("RT_AMD_SHADE_BATCH", 1, 64, k.shade_batch);
-    k.ready_break = env_int("RT_AMD_READY_BREAK", 1, 65, k.ready_break);
+    for (const rt_sched::KnobRange &r : rt_sched::KNOB_RANGES) k.*r.field = env_int(r.env, r.lo, r.hi, k.*r.field);
     ctx->multi.careful = env_int("RT_AMD_MULTI_CAREFUL", INT_MIN, INT_MAX, 0) != 0;
     if (ctx->tile_counter.grow(256) != hipSuccess ||
         hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
@@ -443,15 +437,15 @@ static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, cons
     a.off_objtab = scene->flat.off_objtab;
     a.num_meshes = scene->flat.num_meshes;
     a.stack_entries = scene->flat.stack_entries;
-    a.work_threshold = ctx->knobs.work_threshold;
-    a.ready_break = ctx->knobs.ready_break;
-    a.hit_break = ctx->knobs.hit_break;
-    const Knobs &k = ctx->knobs;
-    const int mix_break = k.mix_break >= 0 ? k.mix_break : (scene->kernel.shape.threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
-    a.hit_low = k.hit_low > 0 && mix_break > 0 ? k.hit_low : k.hit_break;
-    a.mix_break = k.hit_low > 0 && mix_break > 0 ? mix_break : 1000;
-    a.shade_batch = ctx->knobs.shade_batch;
-    a.descend_keep = ctx->knobs.descend_keep;
+    /* (the mapping keeps hit_low <= hit_break, without which the kernel's loops can stop making progress: rt_sched::kernel_knobs) */
+    const rt_sched::KernelKnobs k = rt_sched::kernel_knobs(ctx->knobs, scene->kernel.shape.threads);
+    a.work_threshold = k.work_threshold;
+    a.ready_break = k.ready_break;
+    a.hit_break = k.hit_break;
+    a.hit_low = k.hit_low;
+    a.mix_break = k.mix_break;
+    a.shade_batch = k.shade_batch;
+    a.descend_keep = k.descend_keep;
     a.tri_uv = scene->d_tri_uv.p;
     a.tex_data = scene->d_tex.p;
     a.prev = d_prev;

@@ -150,15 +150,9 @@ struct View {
     int job_frames = 0;                  /* what the uploaded schedule was built for */
 };
 
-/* knobs (RT_AMD_*), none changes an image */
-struct Knobs {
-    int work_threshold = RT_DEF_WORK_THRESHOLD;      /* lanes; RT_AMD_WORK_THRESHOLD */
-    int descend_keep = RT_DEF_DESCEND_KEEP;       /* RT_AMD_DESCEND_KEEP (0..64): 0 = run every descent to its end */
-    int ready_break = RT_DEF_READY_BREAK;        /* lanes; RT_AMD_READY_BREAK; 65 = never */
-    int hit_break = RT_DEF_HIT_BREAK;          /* lanes; RT_AMD_HIT_BREAK */
-    int hit_low = RT_DEF_HIT_LOW, mix_break = -1;                 /* RT_AMD_HIT_LOW, RT_AMD_MIX_BREAK (0 = that rule off; -1 = not set: the default of the scene's workgroup shape) */
-    int shade_batch = RT_DEF_SHADE_BATCH;        /* lanes; RT_AMD_SHADE_BATCH (1..64) */
-};
+/* knobs (RT_AMD_*), none changes an image: rt_schedule.h has them, their accepted ranges and what the kernel is handed for them
+ * (rt_sched::kernel_knobs; RT_AMD_HIT_LOW is clamped to RT_AMD_HIT_BREAK there) */
+using rt_sched::Knobs;
 
 }  // namespace rt_detail
 using namespace rt_detail;

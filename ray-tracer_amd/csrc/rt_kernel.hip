@@ -318,7 +318,11 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
          * (several hundred instructions: three Box-Muller draws, four normalisations) are shaded
          * in batches: without a mesh the lanes holding one wait until `shade_batch` of them
          * do, or nobody else can move, while the others go on generating; with a mesh the
-         * traversal loop below already yields in batches (`ready_break`). */
+         * traversal loop below already yields in batches (`ready_break`).
+         * Progress: whenever the traversal loop below leaves on a batch of hits with no cheap-work lane around, this
+         * condition has to take the batch, or the wave comes back with nothing changed.  Both conditions are restated in
+         * tests/sanitize/capi_host_fuzz.cpp (check_progress), which tries them on every wave state for every knob value the
+         * library accepts; rt_sched::kernel_knobs keeps hit_low <= hit_break for it.  Change them together. */
         if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss(p, a, f);
         {
             const int n_hit = __popcll(__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_SHADE, RT_ICMP_EQ));

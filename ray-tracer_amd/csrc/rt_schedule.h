@@ -199,7 +199,7 @@ inline void build_job_order(const std::vector<uint32_t> &order, const std::vecto
 /* The development overrides of a scene's kernel shape, as read from the environment */
 struct ShapeOverrides {
     bool threads_set = false;
-    int threads = 0;              /* RT_AMD_THREADS: the workgroup size of a mesh scene in LDS (256, 512, 768 or 1024) */
+    int threads = 0;              /* RT_AMD_THREADS: the workgroup size (256, 512, 768 or 1024) of the staged placements - the scene in LDS, the hybrid */
     bool hybrid = true;           /* RT_AMD_SCENE_MODE=0 turns the hybrid kernels off */
     int blocks_per_cu = 0;        /* RT_AMD_BLOCKS_PER_CU: replaces the probed figure when 1..8 */
 };
@@ -220,12 +220,15 @@ struct KernelShape {
  *   object list is so long that only one or two copies fit), the larger with one (fewer copies to stage).
  *   Else, for a mesh, everything before the triangles in LDS when that fits (a depth-10 tree is at most 1,023 nodes whatever
  *   the triangle count), the triangles from global memory: worth it while at least half a CU's wave slots stay filled.
- *   Else the scene in global memory (L2-resident), LDS holding only the traversal stacks. */
+ *   Else the scene in global memory (L2-resident), LDS holding only the traversal stacks.
+ *   RT_AMD_THREADS leaves the two staged placements only their shape of that size: one that does not fit, or that the placement
+ *   has no shape of (a 256-thread hybrid), passes the scene on to the next placement.  The global shapes are one per mesh flag
+ *   and ignore it. */
 template <class Probe>
 inline rt_status choose_shape(bool has_mesh, size_t blob_bytes, size_t prefix_bytes, size_t per_thread, const ShapeOverrides &o, Probe &&probe,
                               KernelShape &out, const char **err)
 {
-    if (has_mesh && o.threads_set && o.threads != 256 && o.threads != 512 && o.threads != 768 && o.threads != 1024) {
+    if (o.threads_set && o.threads != 256 && o.threads != 512 && o.threads != 768 && o.threads != 1024) {
         *err = "RT_AMD_THREADS must be 256, 512, 768 or 1024";
         return RT_ERR_INVALID;
     }
@@ -234,7 +237,7 @@ inline rt_status choose_shape(bool has_mesh, size_t blob_bytes, size_t prefix_by
         int best_waves = 0;
         for (const rt_shape &s : RT_SHAPES) {
             if (s.has_mesh != (int)has_mesh || s.mode != mode) continue;
-            if (mode == RT_SCENE_LDS && has_mesh && o.threads_set && o.threads != s.threads) continue;
+            if (o.threads_set && o.threads != s.threads) continue;       /* (a size no shape of the placement has: on to the next placement) */
             const size_t lds = scene_bytes + per_thread * (size_t)s.threads;
             if (lds > RT_LDS_LIMIT) continue;
             const int nb = blocks(s, lds);
@@ -259,6 +262,58 @@ inline rt_status choose_shape(bool has_mesh, size_t blob_bytes, size_t prefix_by
     }
     if (o.blocks_per_cu >= 1 && o.blocks_per_cu <= 8) out.blocks_per_cu = o.blocks_per_cu;
     return RT_OK;
+}
+
+/* The render kernel's scheduling knobs (RT_AMD_*) as a context holds them; none changes an image (tests/test_gpu_shapes.py renders
+ * with each control path forced) */
+struct Knobs {
+    int work_threshold = RT_DEF_WORK_THRESHOLD;      /* lanes; RT_AMD_WORK_THRESHOLD */
+    int descend_keep = RT_DEF_DESCEND_KEEP;       /* RT_AMD_DESCEND_KEEP (0..64): 0 = run every descent to its end */
+    int ready_break = RT_DEF_READY_BREAK;        /* lanes; RT_AMD_READY_BREAK; 65 = never */
+    int hit_break = RT_DEF_HIT_BREAK;          /* lanes; RT_AMD_HIT_BREAK */
+    /* RT_AMD_HIT_LOW, RT_AMD_MIX_BREAK (0 = that rule off; -1 = not set: the default of the scene's workgroup shape).  The kernel gets
+     * min(hit_low, hit_break): see kernel_knobs */
+    int hit_low = RT_DEF_HIT_LOW, mix_break = -1;
+    int shade_batch = RT_DEF_SHADE_BATCH;        /* lanes; RT_AMD_SHADE_BATCH (1..64) */
+};
+
+/* the environment variable of each knob and the values rt_ctx_create accepts for it (anything else leaves the default) */
+struct KnobRange {
+    const char *env;
+    int Knobs::*field;
+    int lo, hi;
+};
+inline constexpr KnobRange KNOB_RANGES[] = {
+    {"RT_AMD_WORK_THRESHOLD", &Knobs::work_threshold, 1, 64}, {"RT_AMD_DESCEND_KEEP", &Knobs::descend_keep, 0, 64},
+    {"RT_AMD_HIT_BREAK", &Knobs::hit_break, 1, 65},           {"RT_AMD_HIT_LOW", &Knobs::hit_low, 0, 65},
+    {"RT_AMD_MIX_BREAK", &Knobs::mix_break, 0, 130},          {"RT_AMD_SHADE_BATCH", &Knobs::shade_batch, 1, 64},
+    {"RT_AMD_READY_BREAK", &Knobs::ready_break, 1, 65},
+};
+
+/* what a launch of a `threads`-wide workgroup hands the render kernel for the knobs (rt_kernel_args' fields of the same names) */
+struct KernelKnobs {
+    int work_threshold, descend_keep, ready_break, hit_break, hit_low, mix_break, shade_batch;
+};
+
+/* The knobs as the kernel reads them.  The mix rule (hit_low, mix_break) is off when either of its knobs is 0: hit_low then equals
+ * hit_break and mix_break is out of reach.
+ * hit_low <= hit_break always, a larger RT_AMD_HIT_LOW is clamped: the traversal loop leaves with a batch of hit_break hits, and the
+ * step that shades them takes a batch only from hit_low on (or when fewer than work_threshold lanes traverse).  With hit_break <=
+ * hits < hit_low and nothing else to do the wave would leave the loop, shade nothing and come back for ever;
+ * tests/sanitize/capi_host_fuzz.cpp (check_progress) enumerates every accepted knob value and wave state for that. */
+inline KernelKnobs kernel_knobs(const Knobs &k, int threads)
+{
+    const int mix_break = k.mix_break >= 0 ? k.mix_break : (threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
+    const bool mix = k.hit_low > 0 && mix_break > 0;
+    KernelKnobs a;
+    a.work_threshold = k.work_threshold;
+    a.descend_keep = k.descend_keep;
+    a.ready_break = k.ready_break;
+    a.hit_break = k.hit_break;
+    a.hit_low = mix ? std::min(k.hit_low, k.hit_break) : k.hit_break;
+    a.mix_break = mix ? mix_break : 1000;
+    a.shade_batch = k.shade_batch;
+    return a;
 }
 
 /* rt_partition_tiles' owner table dealt out per rank: its tiles (ascending image indices) and, with cost and peak

@@ -1,7 +1,7 @@
 // The GPU-free entry points of rt_capi.cpp, rt_pipeline_capi.cpp and rt_multi_capi.cpp under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; test infrastructure):
-// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule, the output layout and
-// the kernel shape choice (rt_schedule.h) with their properties asserted, and every entry point's refusal of null / bad
-// arguments before it touches HIP.  The three files are compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
+// rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule, the output layout,
+// the kernel shape choice and the scheduling knobs' mapping (rt_schedule.h) with their properties asserted, and every entry
+// point's refusal of null / bad arguments before it touches HIP.  The three files are compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
 // kernel launchers (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
 #include <algorithm>
 #include <cmath>
@@ -276,17 +276,18 @@ template <class Rng> static bool check_shape(Rng &rng)
         return probe_of(s, lds);
     }, k, &err);
     for (size_t i = 1; i < calls.size(); i++) CHECK(calls[i - 1] < calls[i], "shape: probes out of RT_SHAPES' order");
-    const bool bad_threads = mesh && o.threads_set && o.threads != 256 && o.threads != 512 && o.threads != 768 && o.threads != 1024;
-    CHECK((st == RT_ERR_INVALID) == bad_threads, "shape: RT_AMD_THREADS refused iff invalid for a mesh scene");
+    const bool bad_threads = o.threads_set && o.threads != 256 && o.threads != 512 && o.threads != 768 && o.threads != 1024;
+    CHECK((st == RT_ERR_INVALID) == bad_threads, "shape: RT_AMD_THREADS refused iff it is none of the four sizes");
     if (bad_threads) {
         CHECK(calls.empty() && err, "shape: probed before refusing RT_AMD_THREADS");
         return true;
     }
-    /* the candidates of a mode: base LDS bytes, and whether a shape takes part */
+    /* the candidates of a mode: base LDS bytes, and whether a shape takes part (a forced size leaves the staged modes, LDS and hybrid,
+     * only their shape of that size; the global shapes are not chosen among) */
     auto base_of = [&](int mode) { return mode == RT_SCENE_LDS ? blob : mode == RT_SCENE_HYBRID ? prefix : (size_t)0; };
     auto candidate = [&](const rt_shape &s, int mode) {
         return s.has_mesh == (int)mesh && s.mode == mode && base_of(mode) + per_thread * (size_t)s.threads <= RT_LDS_LIMIT &&
-               !(mode == RT_SCENE_LDS && mesh && o.threads_set && o.threads != s.threads) && (mode != RT_SCENE_HYBRID || o.hybrid);
+               !(o.threads_set && o.threads != s.threads) && (mode != RT_SCENE_HYBRID || o.hybrid);
     };
     auto any_of_mode = [&](int mode) { for (const rt_shape &s : RT_SHAPES) if (candidate(s, mode)) return true; return false; };
     const int want_mode = any_of_mode(RT_SCENE_LDS) ? RT_SCENE_LDS : any_of_mode(RT_SCENE_HYBRID) ? RT_SCENE_HYBRID : RT_SCENE_GLOBAL;
@@ -300,6 +301,7 @@ template <class Rng> static bool check_shape(Rng &rng)
     const int ki = rt_shape_index(k.shape);
     CHECK(ki >= 0 && ki < n_shapes && k.shape.has_mesh == (int)mesh, "shape: not a built shape of the scene's mesh flag");
     CHECK(k.shape.mode == want_mode, "shape: fallback order LDS, hybrid, global");
+    CHECK(!o.threads_set || want_mode == RT_SCENE_GLOBAL || k.shape.threads == o.threads, "shape: a staged shape of another size than RT_AMD_THREADS");
     CHECK(k.lds_bytes == base_of(want_mode) + per_thread * (size_t)k.shape.threads && k.lds_bytes <= RT_LDS_LIMIT, "shape: LDS bytes");
     const bool overridden = o.blocks_per_cu >= 1 && o.blocks_per_cu <= 8;
     CHECK(k.blocks_per_cu == (overridden ? o.blocks_per_cu : blocks_of(k.shape, k.lds_bytes)), "shape: blocks per CU");
@@ -313,6 +315,132 @@ template <class Rng> static bool check_shape(Rng &rng)
         CHECK(w < waves || s.threads == k.shape.threads || (mesh ? s.threads < k.shape.threads : s.threads > k.shape.threads), "shape: tie rule");
     }
     return true;
+}
+
+/* ---- progress of the render kernel's wave loop under every accepted knob value ------------------------------------------------------
+ * rt_render_kernel (rt_kernel.hip) is a loop of rounds: finish misses, SHADE a batch of hits if the shade condition holds, fetch pixels, generate
+ * rays, enter meshes, then run traversal steps until the traversal loop's break condition holds.  The two conditions, restated here from the
+ * kernel (its comment above the shade condition points back; change them together):
+ *   n_hit lanes hold a hit to shade, n_trav == n_active lanes traverse, n_light lanes have cheap work, the rest are done. */
+static bool traversal_loop_breaks(const rt_sched::KernelKnobs &a, int n_hit, int n_active, int n_light)
+{
+    if (n_active == 0) return true;
+    return n_hit + n_light > 0 && (n_active < a.work_threshold || n_hit >= a.hit_break || n_light >= a.ready_break || (n_hit >= a.hit_low && n_hit + n_light >= a.mix_break));
+}
+static bool round_shades_mesh(const rt_sched::KernelKnobs &a, int n_hit, int n_trav) { return n_hit > 0 && (n_hit >= a.hit_low || n_trav < a.work_threshold); }
+static bool round_shades_no_mesh(const rt_sched::KernelKnobs &a, int n_hit, bool others) { return n_hit > 0 && (n_hit >= a.shade_batch || !others); }
+
+/* the mapping before rt_sched::kernel_knobs existed (rt_capi.cpp filled the kernel's arguments with this expression): kept to show that
+ * check_progress tells the two apart */
+static rt_sched::KernelKnobs mapping_without_clamp(const rt_sched::Knobs &k, int threads)
+{
+    const int mix_break = k.mix_break >= 0 ? k.mix_break : (threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK);
+    rt_sched::KernelKnobs a = rt_sched::kernel_knobs(k, threads);
+    a.hit_low = k.hit_low > 0 && mix_break > 0 ? k.hit_low : k.hit_break;
+    a.mix_break = k.hit_low > 0 && mix_break > 0 ? mix_break : 1000;
+    return a;
+}
+
+static const rt_sched::KnobRange &range_of(int rt_sched::Knobs::*field)
+{
+    for (const rt_sched::KnobRange &r : rt_sched::KNOB_RANGES) if (r.field == field) return r;
+    std::abort();
+}
+
+/* A round changes the wave's state, so the loop ends, whenever
+ *   - a lane has cheap work: a missed ray is finished on the spot (px_shade_miss) and the lane generates its next one; a lane without a pixel
+ *     takes one (px_fetch) or, the tickets used up, is done; a lane with a ray to generate generates it (px_gen); a lane between meshes
+ *     moves on to the next mesh or to its hit.  Each of these happens in the round unconditionally - no knob gates them - and moves the lane
+ *     forward in a finite sequence (meshes of the scene, bounces of a sample, samples of a pixel, pixels of the launch);
+ *   - or a traversal step runs (a traversal is finite);
+ *   - or a batch of hits is shaded.
+ * What is left are the waves WITHOUT a cheap-work lane: every lane holds a hit, traverses or is done, and nothing in the round changes that
+ * unless it shades or steps.  With a mesh: if the traversal loop breaks before its first step, the round that follows sees the same counts
+ * and must shade - "breaks" implies "shades", for every such state and every knob value rt_ctx_create accepts (rt_sched::KNOB_RANGES):
+ * work_threshold, hit_break and hit_low over their whole ranges; mix_break unset, 0, 1, both defaults and 130; 256- and 1024-thread shapes
+ * (the default mix_break differs).  ready_break is at least 1 and n_light is 0, so that term is false whatever its value; descend_keep and
+ * shade_batch are in neither condition.  Without a mesh there is no traversal loop: a wave whose lanes all hold a hit or are done has no
+ * "others", for every shade_batch.  Returns the number of (knobs, state) pairs checked, or -1 and the first counter-example on stderr. */
+template <class Mapping> static long long check_progress(Mapping mapping, const rt_sched::Knobs *only = nullptr)
+{
+    using rt_sched::Knobs;
+    const rt_sched::KnobRange &wt = range_of(&Knobs::work_threshold), &hb = range_of(&Knobs::hit_break), &hl = range_of(&Knobs::hit_low),
+                              &mb = range_of(&Knobs::mix_break), &sb = range_of(&Knobs::shade_batch), &rb = range_of(&Knobs::ready_break);
+    if (rb.lo < 1 || mb.lo > 0 || mb.hi < 130 || wt.lo < 1) { std::fprintf(stderr, "progress: the accepted ranges are not the ones this check was written for\n"); return -1; }
+    const int mixes[] = {-1, 0, 1, RT_DEF_MIX_BREAK, RT_DEF_MIX_BREAK_1024, 130};
+    long long checked = 0;
+    for (int threads : {256, 1024})
+        for (int mix : mixes)
+            for (int w = wt.lo; w <= wt.hi; w++)
+                for (int b = hb.lo; b <= hb.hi; b++)
+                    for (int l = hl.lo; l <= hl.hi; l++) {
+                        Knobs k;
+                        k.mix_break = mix; k.work_threshold = w; k.hit_break = b; k.hit_low = l;
+                        if (only && (only->mix_break != mix || only->work_threshold != w || only->hit_break != b || only->hit_low != l)) continue;
+                        const rt_sched::KernelKnobs a = mapping(k, threads);
+                        for (int n_hit = 1; n_hit <= 63; n_hit++)
+                            for (int n_active = 1; n_hit + n_active <= 64; n_active++) {
+                                checked++;
+                                if (traversal_loop_breaks(a, n_hit, n_active, 0) && !round_shades_mesh(a, n_hit, n_active)) {
+                                    std::fprintf(stderr, "progress: %d threads, RT_AMD_MIX_BREAK%s%d RT_AMD_WORK_THRESHOLD=%d RT_AMD_HIT_BREAK=%d RT_AMD_HIT_LOW=%d (kernel: hit_low %d, mix_break %d): "
+                                                 "a wave of %d hits, %d traversing, %d done leaves the traversal loop and shades nothing\n",
+                                                 threads, mix < 0 ? " unset: " : "=", mix < 0 ? a.mix_break : mix, w, b, l, a.hit_low, a.mix_break, n_hit, n_active, 64 - n_hit - n_active);
+                                    return -1;
+                                }
+                            }
+                    }
+    if (only) return checked;
+    for (int s = sb.lo; s <= sb.hi; s++) {
+        Knobs k;
+        k.shade_batch = s;
+        const rt_sched::KernelKnobs a = mapping(k, 256);
+        for (int n_hit = 1; n_hit <= 64; n_hit++) {
+            checked++;
+            if (!round_shades_no_mesh(a, n_hit, false)) { std::fprintf(stderr, "progress: no mesh, RT_AMD_SHADE_BATCH=%d: %d hits and no other lane, nothing shaded\n", s, n_hit); return -1; }
+        }
+    }
+    return checked;
+}
+
+/* kernel_knobs on every accepted value: what it promises beside progress */
+static bool check_knob_mapping()
+{
+    using rt_sched::Knobs;
+    for (int threads : {256, 512, 768, 1024})
+        for (int mix = -1; mix <= range_of(&Knobs::mix_break).hi; mix++)
+            for (int b = range_of(&Knobs::hit_break).lo; b <= range_of(&Knobs::hit_break).hi; b++)
+                for (int l = range_of(&Knobs::hit_low).lo; l <= range_of(&Knobs::hit_low).hi; l++) {
+                    Knobs k;
+                    k.mix_break = mix; k.hit_break = b; k.hit_low = l;
+                    const rt_sched::KernelKnobs a = rt_sched::kernel_knobs(k, threads);
+                    const int mb = mix >= 0 ? mix : threads == 1024 ? RT_DEF_MIX_BREAK_1024 : RT_DEF_MIX_BREAK;
+                    const bool on = l > 0 && mb > 0;
+                    CHECK(a.hit_low <= a.hit_break && a.hit_break == b, "knobs: hit_low above hit_break");
+                    CHECK(a.hit_low == (on ? std::min(l, b) : b) && a.mix_break == (on ? mb : 1000), "knobs: the mix rule");
+                    CHECK(a.work_threshold == k.work_threshold && a.ready_break == k.ready_break && a.descend_keep == k.descend_keep && a.shade_batch == k.shade_batch, "knobs: passed through");
+                }
+    const Knobs def;
+    const rt_sched::KernelKnobs d = rt_sched::kernel_knobs(def, 256), e = rt_sched::kernel_knobs(def, 1024);
+    CHECK(d.hit_low == RT_DEF_HIT_LOW && d.mix_break == RT_DEF_MIX_BREAK && e.mix_break == RT_DEF_MIX_BREAK_1024 && d.hit_break == RT_DEF_HIT_BREAK, "knobs: the defaults");
+    return true;
+}
+
+/* `progress`: the whole enumeration on the library's mapping.  `progress-without-clamp`: the same on the mapping before the clamp, which must
+ * produce a counter-example (first the enumeration's, then the one RT_AMD_HIT_BREAK=8 alone gives): exit status 0 iff it does. */
+static int progress_main(const char *mode)
+{
+    if (!std::strcmp(mode, "progress")) {
+        const long long n = check_progress(rt_sched::kernel_knobs);
+        if (n < 0 || !check_knob_mapping()) return 1;
+        std::printf("capi host fuzz: progress holds for %lld (knobs, wave state) pairs\n", n);
+        return 0;
+    }
+    rt_sched::Knobs eight;
+    eight.hit_break = 8;
+    const bool found = check_progress(mapping_without_clamp) < 0 && check_progress(mapping_without_clamp, &eight) < 0;
+    const bool clean = check_progress(rt_sched::kernel_knobs, &eight) > 0;
+    std::printf("capi host fuzz: without the clamp %s; with it RT_AMD_HIT_BREAK=8 %s\n", found ? "counter-examples found" : "NO counter-example", clean ? "makes progress" : "FAILS");
+    return found && clean ? 0 : 1;
 }
 
 /* rt_partition_tiles' owner table dealt out: a partition of the image's tiles, with each tile's cost and peak */
@@ -337,6 +465,8 @@ static bool check_deal(const std::vector<int32_t> &owner, int n_ranks, const std
 
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !std::strncmp(argv[1], "progress", 8)) return progress_main(argv[1]);
+    if (!check_knob_mapping()) return 1;
     std::mt19937_64 rng((unsigned long long)(argc > 1 ? std::atoll(argv[1]) : 1));
     const int cases = argc > 2 ? std::atoi(argv[2]) : 1000;
     auto irand = [&](long long lo, long long hi) { return (long long)std::uniform_int_distribution<long long>(lo, hi)(rng); };

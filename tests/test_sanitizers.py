@@ -67,6 +67,19 @@ def test_gpu_free_entry_points_of_the_c_abi_under_asan_and_ubsan(tmp_path):
     for seed in (1, 2):
         r = subprocess.run([exe, str(seed), "3000"], capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode == 0 and "sanitizers silent" in r.stdout, (seed, (r.stderr or r.stdout)[-3000:])
+    # The wave loop's progress under every accepted knob value (check_progress in the program).  It has teeth: on the knob mapping without
+    # the hit_low <= hit_break clamp it finds a wave that spins, RT_AMD_HIT_BREAK=8 alone included ...
+    r = subprocess.run([exe, "progress-without-clamp"], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "counter-examples found" in r.stdout and "RT_AMD_HIT_BREAK=8 makes progress" in r.stdout, (r.stderr or r.stdout)[-3000:]
+    assert "RT_AMD_HIT_BREAK=8 RT_AMD_HIT_LOW=16" in r.stderr and "shades nothing" in r.stderr, r.stderr[-3000:]
+    # ... and the whole enumeration (6.6e9 states, none sampled) on the library's mapping, in a plain -O2 build of the same program: half a
+    # minute under the sanitizers, which have nothing to watch in a loop over integers
+    plain = str(tmp_path / "capi_fuzz_o2")
+    r = subprocess.run([c for c in cmd[:-2] if c not in ("-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")] + ["-O2", "-o", plain],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([plain, "progress"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "progress holds for" in r.stdout, (r.stderr or r.stdout)[-3000:]
 
 
 _ORACLE_SCRIPT = r"""
