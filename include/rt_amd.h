@@ -397,6 +397,33 @@ rt_status rt_render_visibility_device(rt_ctx *ctx, const rt_scene *scene, const 
 rt_status rt_render_visibility(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float light_pos[3], float bias,
                                uint8_t *visibility);
 
+/* The ambient-occlusion plane of a view: from every pixel's first hit, how much of the cosine-weighted hemisphere within `radius` is
+ * free.  Per pixel (px, py) of the cam->width x cam->height image, in rt_render's row-major full-frame layout:
+ *   1. rt_render_aov's primary ray (antialiasing off) and its closest hit; none: count = RT_AO_NO_SURFACE, ao = 1.0f;
+ *   2. from the hit's point P and shading normal N exactly as rt_hit reports them: o' = N * bias + P per component in two binary32
+ *      roundings (the visibility plane's step 2);
+ *   3. the renderer's per-pixel random state (src/raytracer.cu:127): state = (uint32)((py * W + px) * 3) * 3145739u +
+ *      (uint32)time_ms * 6291469u;
+ *   4. for k = 0 .. samples-1, in order, on that one stream: r = (g(), g(), g()) with g = normally_dist_num (src/utils.cu:234-239: the
+ *      angle draw first, then the radius draw; rho * cos(theta)); if dot(r, N) < 0 then r = -r; r = normalised(r); d = normalised(N + r)
+ *      - Ray::true_lambertian_reflect (src/ray.cu:157-178), with dot = (x*x' + y*y') + z*z' and normalised = a * (1.0f /
+ *      sqrtf((x*x + y*y) + z*z)), nothing fused.  The sample is free iff !occluded(o', d, radius), occluded as rt_occluded_rays defines
+ *      it; a radius >= RT_HIT_MISS_T (or +inf) means "any hit at all".  Every sample consumes exactly six draws whatever its outcome;
+ *   5. count = the number of free samples, ao = (float)count / (float)samples (one IEEE division).
+ * With samples = 1, bias = 0 and an unlimited radius the count is what rt_render gives at one sample per pixel, reflection limit 2,
+ * antialiasing off and a white sky for a scene whose materials are all white and diffuse: the first bounce ray escapes or it does not.
+ * samples outside 1 .. RT_AO_MAX_SAMPLES, a radius that is NaN or <= 0, a bias that is negative or not finite, both output pointers
+ * NULL (either alone may be), a null context, scene or camera and a scene of another context are RT_ERR_INVALID.
+ * Device-buffer form: d_count (W*H uint16) and d_ao (W*H floats) are device memory of ctx's GPU; asynchronous on hip_stream and ordered
+ * like rt_render_device (one launch in flight per context); rt_last_kernel_ms reports it. */
+#define RT_AO_NO_SURFACE 0xFFFFu
+#define RT_AO_MAX_SAMPLES 4096
+rt_status rt_render_ao_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, int32_t samples, float radius, float bias,
+                              int32_t time_ms, uint16_t *d_count, float *d_ao, void *hip_stream);
+/* Host-buffer form: returns when the planes are in host memory. */
+rt_status rt_render_ao(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, int32_t samples, float radius, float bias,
+                       int32_t time_ms, uint16_t *count, float *ao);
+
 /* ---- edge-avoiding a-trous denoiser driven by the first-hit planes ------------------------------
  * An image-space filter for a noisy low-sample frame (Dammertz et al. 2010, "Edge-avoiding A-Trous wavelet transform for fast global
  * illumination filtering"; the spatial filter of SVGF without its temporal part).  It takes plain planes in rt_render's row-major

@@ -65,6 +65,8 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal",
 HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
 VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
+AO_PLANES = ("ao", "count")
+AO_NO_SURFACE, AO_MAX_SAMPLES = 0xFFFF, 4096        # RT_AO_*: render_ao's count where the primary ray hit nothing; the most samples
 
 # Every function include/rt_amd.h declares, in its order: name -> (restype, [argtypes]).  tests/test_abi.py parses the header and
 # checks each row's parameter count and kinds.  st: rt_status; vp: an opaque handle, a device pointer, a hipStream_t, or a host
@@ -141,6 +143,8 @@ ABI = {
     "rt_occluded_rays": (st, [vp, vp, fp, fp, fp, i64, vp]),
     "rt_render_visibility_device": (st, [vp, vp, cam, fp, f32, vp, vp]),
     "rt_render_visibility": (st, [vp, vp, cam, fp, f32, vp]),
+    "rt_render_ao_device": (st, [vp, vp, cam, i32, f32, f32, i32, vp, vp, vp]),
+    "rt_render_ao": (st, [vp, vp, cam, i32, f32, f32, i32, vp, fp]),
     "rt_denoise_params_default": (None, [dnp]),
     "rt_denoise_device": (st, [vp, i32, i32, vp, vp, vp, vp, vp, dnp, vp, vp]),
     "rt_denoise": (st, [vp, i32, i32, fp, fp, fp, i32p, fp, dnp, fp]),

@@ -11,8 +11,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libraytracer_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_denoise_capi.cpp", "rt_host.cpp")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h", "rt_internal.h", "rt_query.h", "rt_ray_kernel.h", "rt_query_kernel.h", "rt_occlusion.h", "rt_occlusion_kernel.h", "rt_denoise.h", "rt_denoise_kernel.h")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_denoise_capi.cpp", "rt_host.cpp")]
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h", "rt_internal.h", "rt_query.h", "rt_ray_kernel.h", "rt_query_kernel.h", "rt_occlusion.h", "rt_occlusion_kernel.h", "rt_ao.h", "rt_ao_kernel.h", "rt_denoise.h", "rt_denoise_kernel.h")] + [
     os.path.join(ROOT, "include", "rt_amd.h")]
 # -fno-slp-vectorize: the SLP vectorizer pairs the scalar f32 adds / multiplies of the vector math into v_pk_*_f32, which
 # are not faster on gfx950 and need register pairs: 128 instead of ~90 VGPRs and ~10 % more time (same-box A/B, round 2).

@@ -461,11 +461,15 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 #include "rt_query_kernel.h"
 /* occlusion (any-hit) ray queries and the light-visibility plane: rt_occlusion_kernel and its launcher */
 #include "rt_occlusion_kernel.h"
+/* the ambient-occlusion plane: rt_ao_kernel and its launcher */
+#include "rt_ao_kernel.h"
 #else
 #include "rt_query.h"
 #include "rt_occlusion.h"
+#include "rt_ao.h"
 extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+extern "C" hipError_t rt_launch_ao(const rt_ao_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 /* the edge-avoiding a-trous denoiser: image-space passes over planes, nothing of the traversal above (in every build) */

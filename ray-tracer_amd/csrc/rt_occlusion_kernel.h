@@ -41,9 +41,10 @@
 #define M_START 6               /* (after rt_pixel.h's M_DONE) the lane holds a ray that has not met the top-level objects yet */
 #define RT_BELOW_INF_F 1073741760.0f      /* the largest binary32 below RT_INF_F (2^30 - 2^6) */
 
-/* START: a lane's ray meets the top-level objects; first exit.  Leaves the lane in MESH (with the limit clamped for the mesh walks) or, answered, in SHADE. */
-template <bool HAS_MESH>
-__device__ __forceinline__ void rt_occlusion_start(const rt_occlusion_args &a, const Lds &L, V3 o, V3 d, V3 &inv, float &tm, float &best_t, int &best_obj, int &best_prim,
+/* START: a lane's ray meets the top-level objects; first exit.  Leaves the lane in MESH (with the limit clamped for the mesh walks) or, answered, in SHADE.
+ * (Args: rt_occlusion_args, or rt_ao_args of rt_ao_kernel.h) */
+template <bool HAS_MESH, class Args>
+__device__ __forceinline__ void rt_occlusion_start(const Args &a, const Lds &L, V3 o, V3 d, V3 &inv, float &tm, float &best_t, int &best_obj, int &best_prim,
                                                    uint32_t &occ, int &next_mesh, int &mode)
 {
     if (HAS_MESH) inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);   /* src/ray.cu:198-202 */

@@ -404,6 +404,20 @@ public:
         check(rt_render_visibility(ctx_, scene_, &cam.c, light_pos.data(), bias, out.data()));
         return out;
     }
+    /* The ambient-occlusion plane of a view (rt_render_ao): per pixel `samples` cosine-weighted directions from the first hit, each free
+     * if nothing lies within `radius`; ao W*H floats (free / samples, 1 where there is no surface), count W*H (RT_AO_NO_SURFACE there) */
+    struct Ao {
+        std::vector<float> ao;
+        std::vector<uint16_t> count;
+    };
+    Ao render_ao(const Camera &cam, int32_t samples = 16, float radius = RT_HIT_MISS_T, float bias = 1e-3f, int32_t time_ms = 0)
+    {
+        const size_t px = (size_t)cam.c.width * (size_t)cam.c.height;
+        Ao a;
+        a.ao.resize(px); a.count.resize(px);
+        check(rt_render_ao(ctx_, scene_, &cam.c, samples, radius, bias, time_ms, a.count.data(), a.ao.data()));
+        return a;
+    }
     /* The edge-avoiding a-trous filter (rt_denoise) on a frame and the view's first-hit planes: colour W*H*3 floats (e.g.
      * previous_render), the planes as render_aov gives them.  The colour is divided by the albedo before the filter and multiplied
      * after (use_albedo), taps across an object edge are skipped (use_object).  Returns the filtered W*H*3 floats. */

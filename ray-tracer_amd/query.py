@@ -1,9 +1,9 @@
-"""Ray queries: closest hits and first-hit planes, occlusion (any-hit) and the light-visibility plane."""
+"""Ray queries: closest hits and first-hit planes, occlusion (any-hit), the light-visibility plane and the ambient-occlusion plane."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AOV_PLANES, HIT_DTYPE, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -86,3 +86,26 @@ def render_visibility_device(ctx, scene, camera, light_pos, bias, d_visibility, 
     """Device-buffer form (rt_render_visibility_device): a device pointer to W * H bytes; asynchronous on `stream`."""
     light = np.ascontiguousarray(light_pos, dtype=np.float32).reshape(3)
     ctx._check(lib().rt_render_visibility_device(ctx._h, scene._h, C.byref(camera.c), _fp(light)[1], float(bias), _dptr(d_visibility), _dptr(stream)))
+
+
+def render_ao(ctx, scene, camera, samples=16, radius=float("inf"), bias=1e-3, time_ms=0, planes=("ao",)):
+    """The ambient-occlusion plane of a view (rt_render_ao): per pixel the primary ray's closest hit, then `samples` cosine-weighted
+    directions of the renderer's sampler from P + N * bias on the pixel's own random stream (seeded like a frame of time_ms), each free
+    if nothing lies within `radius`.  Returns a dict with the requested ones of ao [H, W] float32 (free samples / samples; 1 where
+    there is no surface) and count [H, W] uint16 (the free samples; AO_NO_SURFACE where there is no surface)."""
+    unknown = [p for p in planes if p not in AO_PLANES]
+    if unknown:
+        raise ValueError("unknown planes: %s" % unknown)
+    W, H = camera.width, camera.height
+    out = {p: np.zeros((H, W), np.uint16 if p == "count" else np.float32) for p in AO_PLANES if p in planes}
+    count = C.c_void_p(out["count"].ctypes.data) if "count" in out else None
+    ao = out["ao"].ctypes.data_as(C.POINTER(C.c_float)) if "ao" in out else None
+    ctx._check(lib().rt_render_ao(ctx._h, scene._h, C.byref(camera.c), int(samples), float(radius), float(bias), int(time_ms), count, ao))
+    return out
+
+
+def render_ao_device(ctx, scene, camera, samples=16, radius=float("inf"), bias=1e-3, time_ms=0, d_count=None, d_ao=None, stream=None):
+    """Device-buffer form (rt_render_ao_device): device pointers to W * H uint16 counts and W * H float32 (None: not wanted, but one of
+    the two must be); asynchronous on `stream`."""
+    ctx._check(lib().rt_render_ao_device(ctx._h, scene._h, C.byref(camera.c), int(samples), float(radius), float(bias), int(time_ms),
+                                         _dptr(d_count), _dptr(d_ao), _dptr(stream)))
