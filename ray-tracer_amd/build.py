@@ -4,6 +4,7 @@ hipcc cross-compiles without a GPU; the built .so travels with the repo snapshot
 box.  -ffp-contract=off is mandatory: the reference's `a*b+c` are two roundings and a fused
 multiply-add changes hit/miss decisions (hard part 1).
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -12,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libraytracer_amd.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_denoise_capi.cpp", "rt_host.cpp")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("rt_math.h", "rt_rng.h", "rt_device_scene.h", "rt_pixel.h", "rt_host.h", "rt_schedule.h", "rt_internal.h", "rt_query.h", "rt_ray_kernel.h", "rt_query_kernel.h", "rt_occlusion.h", "rt_occlusion_kernel.h", "rt_ao.h", "rt_ao_kernel.h", "rt_denoise.h", "rt_denoise_kernel.h")] + [
-    os.path.join(ROOT, "include", "rt_amd.h")]
+# every header there is: a new one cannot be forgotten, and needs_build() then serves no stale library after an edit
+HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "rt_amd.h")]
 # -fno-slp-vectorize: the SLP vectorizer pairs the scalar f32 adds / multiplies of the vector math into v_pk_*_f32, which
 # are not faster on gfx950 and need register pairs: 128 instead of ~90 VGPRs and ~10 % more time (same-box A/B, round 2).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17",

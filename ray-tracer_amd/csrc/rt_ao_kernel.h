@@ -2,8 +2,8 @@
  * rt_ao_kernel.h — the ambient-occlusion plane of a view, fused: per pixel the AOV pass's primary ray and its closest hit, then from the
  * hit's point P and shading normal N `samples` cosine-weighted directions of the renderer's own sampler on the pixel's own random stream,
  * each an occlusion query (rt_occlusion_kernel.h) of the limit `radius` from o' = P + N * bias; the pixel is the number of free samples
- * and that number over `samples` (include/rt_amd.h has the definition to the bit).  Included by rt_kernel.hip behind
- * rt_occlusion_kernel.h, whose START and early exits it calls; the launcher at the end (rt_ray_kernel.h) is called from rt_ao_capi.cpp.
+ * and that number over `samples` (include/rt_amd.h has the definition to the bit).  It calls START and the early exits of
+ * rt_occlusion_kernel.h; the launcher at the end (rt_ray_kernel.h) is called from rt_ao_capi.cpp.
  *
  * A lane is the occlusion kernel's state machine with a pixel held across segments: FETCH (take a tile slot, form the primary ray) ->
  * START -> MESH -> WAIT (the primary segment has a NaN limit: no exit, and its meshes are merged into the closest hit) -> SHADE.  SHADE
@@ -18,8 +18,17 @@
 #ifndef RT_AO_KERNEL_H
 #define RT_AO_KERNEL_H
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
 #include "rt_ao.h"
+#include "rt_device_scene.h"
+#include "rt_intersect.h"
 #include "rt_occlusion_kernel.h"
+#include "rt_ray_kernel.h"
+#include "rt_surface.h"
+#include "rt_traverse.h"
+#include "rt_vec.h"
 
 /* lanes of a wave holding an answered segment before the traversal loop yields to count them and start their next one: swept over
  * 8 / 16 / 24 / 32 with tools/ao_probe.py (DESIGN.md §14 has the table) */

@@ -801,7 +801,7 @@ extern "C" rt_status rt_debug_eval(rt_ctx *ctx, int32_t op, const uint32_t *in, 
     return RT_OK;
 }
 
-/* test hook: the short reciprocal and square root of the device code (rt_pixel.h rt_rcp_short / rt_sqrt_short) against the
+/* test hook: the short reciprocal and square root of the device code (rt_vec.h rt_rcp_short / rt_sqrt_short) against the
  * compiler's IEEE expansions for every one of the 2^32 binary32 inputs, on the device.  out4 = {reciprocal: inputs inside its
  * range that differ, inputs inside its range; square root: likewise} */
 extern "C" hipError_t rt_launch_exhaustive(unsigned long long *out4, hipStream_t stream);

@@ -1,6 +1,6 @@
 /*
  * rt_denoise_kernel.h — the edge-avoiding a-trous wavelet filter of rt_denoise (include/rt_amd.h has the definition; the operation
- * order below IS the interface: tests/denoise_ref.py reproduces it bit for bit).  Included by rt_kernel.hip (one code object for the
+ * order below IS the interface: tests/denoise_ref.py reproduces it bit for bit).  Part of rt_kernel.hip's translation unit (one code object for the
  * library); the launchers at the end are called from rt_denoise_capi.cpp.
  *
  * Nothing here traverses a scene: the passes are image-space.  This is a first, untuned shape: correct to the bit, measured, not optimised.
@@ -19,7 +19,11 @@
 #ifndef RT_DENOISE_KERNEL_H
 #define RT_DENOISE_KERNEL_H
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
 #include "rt_denoise.h"
+#include "rt_device_scene.h"
 
 #define RT_DN_TILE_X 32
 #define RT_DN_TILE_Y 8

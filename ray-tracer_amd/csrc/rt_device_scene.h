@@ -1,6 +1,6 @@
 /*
  * rt_device_scene.h — the compact scene layout the HIP kernel reads, and the kernel argument
- * block.  Written by the host flattener (rt_host.cpp), read by rt_kernel.hip.
+ * block.  Written by the host flattener (rt_host.cpp), read by the kernels of rt_kernel.hip.
  *
  * The reference keeps the scene as an array of 5,328-byte `Object` unions, 216-byte triangles
  * and 3,616-byte BVH nodes with one device allocation per node (SURVEY.md §8 sizes).  Here:
@@ -36,7 +36,7 @@
 #define RT_SCENE_GLOBAL 0            /* every section from global memory; LDS holds only the traversal stacks */
 #define RT_SCENE_LDS 1               /* the whole blob staged into LDS */
 #define RT_SCENE_HYBRID 2            /* everything but the triangles in LDS, the triangles from global memory */
-/* A shape of the render kernel: rt_render_kernel<threads, has_mesh, mode>.  RT_SHAPES are the ones built (rt_kernel.hip
+/* A shape of the render kernel: rt_render_kernel<threads, has_mesh, mode>.  RT_SHAPES are the ones built (rt_render_kernel.h
  * instantiates exactly these), in the order a scene's shape is chosen from them (rt_sched::choose_shape): without a mesh
  * the smaller workgroup first, with one the larger. */
 struct rt_shape {
@@ -60,7 +60,7 @@ inline constexpr int rt_shape_index(rt_shape s)
 #define RT_FRAME_BITS 5               /* a pixel keeps the index of its frame within the launch in this many bits */
 #define RT_MAX_BATCH_FRAMES (1 << RT_FRAME_BITS)   /* frames one launch can render */
 #define RT_SMALL_WG_WAVES 5            /* workgroups of fewer than 1024 threads are compiled for this many waves per SIMD (<= 96 VGPRs) */
-/* Defaults of the render kernel's scheduling thresholds (lanes of a wave; see rt_kernel.hip; RT_AMD_* overrides them).
+/* Defaults of the render kernel's scheduling thresholds (lanes of a wave; see rt_render_kernel.h; RT_AMD_* overrides them).
  * None of them changes an image.  Values: same-box sweeps over four scenes in the multi-frame regime,
  * profiles/r02/experiments/.  (Compiling them in as immediates instead of launch arguments was measured: no difference.) */
 #define RT_DEF_WORK_THRESHOLD 4      /* traversal steps run while at least this many lanes traverse (4 against 8, round 3: -0.6 % monkey, -0.9 % cube, +-0 reference scene 0, an eighth of the image -1 %) */
@@ -202,5 +202,28 @@ typedef struct {
     uint32_t *tile_peak;           /* with tile_cost: per tile, the cost of its most expensive pixel (of any one frame) */
     unsigned long long *stats;     /* development builds only (-DRT_STATS): section counters */
 } rt_kernel_args;
+
+/* ---- the two conditions the render kernel's wave loop makes progress by, stated once -------------------------------------------------
+ * rt_render_kernel (rt_render_kernel.h) uses them on its argument block, tests/sanitize/capi_host_fuzz.cpp (check_progress) on
+ * rt_sched::KernelKnobs, which carries the same field names: it tries them on every wave state for every knob value the library accepts;
+ * rt_sched::kernel_knobs keeps hit_low <= hit_break for it.
+ *   n_hit lanes hold a hit to shade, n_active (n_trav) lanes traverse, n_light lanes have cheap work, the rest are done. */
+#if defined(__HIPCC__)
+#define RT_SCENE_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define RT_SCENE_HD inline
+#endif
+/* the traversal loop leaves (n_active > 0): lanes holding a hit wait for a batch of `hit_break`; the cheap kinds of ready lane (generate,
+ * fetch, next mesh, a miss) for one of `ready_break`; or a smaller batch of hits that, together with the cheap-work lanes, is worth the round */
+template <class K> RT_SCENE_HD bool rt_traversal_yields(const K &a, int n_hit, int n_active, int n_light)
+{
+    return n_hit + n_light > 0 && (n_active < a.work_threshold || n_hit >= a.hit_break || n_light >= a.ready_break ||
+                                   (n_hit >= a.hit_low && n_hit + n_light >= a.mix_break));
+}
+/* the round shades its batch of hits (others: some lane can generate or fetch).  A macro: as a function, in each of four forms tried (two
+ * templates over the argument block; the same taking scalars; those with `n_hit > 0 &&` left at the call; one template <bool HAS_MESH> with
+ * this expression verbatim), the render kernels' code comes out different; this expands to the expression the kernel had. */
+#define RT_ROUND_SHADES(a, has_mesh, n_hit, n_trav, others) \
+    ((n_hit) > 0 && ((has_mesh) ? ((n_hit) >= (a).hit_low || (n_trav) < (a).work_threshold) : ((n_hit) >= (a).shade_batch || !(others))))
 
 #endif

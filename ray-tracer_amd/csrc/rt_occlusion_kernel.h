@@ -1,7 +1,6 @@
 /*
  * rt_occlusion_kernel.h — occlusion (any-hit) ray queries and the light-visibility plane of a view: "is anything in the way?", one byte
- * per ray.  Included by rt_kernel.hip behind rt_query_kernel.h (it uses that file's and the render kernel's traversal pieces); the
- * launcher at the end (rt_ray_kernel.h) is called from rt_occlusion_capi.cpp.
+ * per ray.  The traversal pieces are rt_traverse.h's; the launcher at the end (rt_ray_kernel.h) is called from rt_occlusion_capi.cpp.
  *
  * occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_query_kernel answers) finds a hit AND its distance
  * t <= tmax.  The ray is taken as given (direction not normalised, t and tmax in units of its length, Ray::change_direction
@@ -25,20 +24,27 @@
  * exit) -> MESH -> WAIT (traversal macro steps, second exit) -> SHADE (store the byte; or, for a pixel whose primary ray hit, form the
  * shadow segment and go to START again) -> FETCH.  In the visibility kernel START is a state of its own, so that the kernel holds
  * rt_closest_simple once, not once per segment; a ray query does it inside FETCH (as a state it kept the ray's registers live round the loop).  Both segments use the operator's division in the sphere test (!UNIT_DIR): on a
- * unit direction it gives the short form's bits for every accepted distance (rt_pixel.h, rt_closest_simple).
+ * unit direction it gives the short form's bits for every accepted distance (rt_intersect.h, rt_closest_simple).
  */
 #ifndef RT_OCCLUSION_KERNEL_H
 #define RT_OCCLUSION_KERNEL_H
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_device_scene.h"
+#include "rt_intersect.h"
 #include "rt_occlusion.h"
 #include "rt_ray_kernel.h"
+#include "rt_surface.h"
+#include "rt_traverse.h"
+#include "rt_vec.h"
 
 /* lanes of a wave holding a finished ray before the traversal loop yields to store and refill them: swept over 8 / 16 / 24 / 32 with
  * tools/occlusion_probe.py (DESIGN.md §11 has the table) */
 #ifndef RT_OCCLUSION_REFILL
 #define RT_OCCLUSION_REFILL 16
 #endif
-#define M_START 6               /* (after rt_pixel.h's M_DONE) the lane holds a ray that has not met the top-level objects yet */
 #define RT_BELOW_INF_F 1073741760.0f      /* the largest binary32 below RT_INF_F (2^30 - 2^6) */
 
 /* START: a lane's ray meets the top-level objects; first exit.  Leaves the lane in MESH (with the limit clamped for the mesh walks) or, answered, in SHADE.

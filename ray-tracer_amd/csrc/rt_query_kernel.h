@@ -1,11 +1,11 @@
 /*
  * rt_query_kernel.h — closest-hit ray queries and the first-hit AOV pass: one ray per lane through the scene the render kernel
- * stages, stopped at the first hit, with the hit written out instead of shaded.  Included by rt_kernel.hip behind rt_render_kernel
- * (it uses that file's traversal pieces); the launcher at the end (rt_ray_kernel.h) is called from rt_query_capi.cpp.
+ * stages, stopped at the first hit, with the hit written out instead of shaded.  The traversal pieces are rt_traverse.h's, the hit's surface
+ * is rt_surface.h's; the launcher at the end (rt_ray_kernel.h) is called from rt_query_capi.cpp.
  *
  * What is found is get_ray_collision (src/raytracer.cu:24-46) under the render kernel's rules: the top-level objects in list order
- * with `t <= best_t` (rt_closest_simple, rt_pixel.h), then the meshes merged by "smaller distance, or equal distance and larger list
- * index", each walked with rt_descend / the leaf test / rt_pop of rt_kernel.hip.  The ray is taken as given: the direction is NOT
+ * with `t <= best_t` (rt_closest_simple, rt_intersect.h), then the meshes merged by "smaller distance, or equal distance and larger list
+ * index", each walked with rt_descend / the leaf test / rt_pop of rt_traverse.h.  The ray is taken as given: the direction is NOT
  * normalised (Ray::change_direction, src/ray.cu:198-202), the distance is in units of its length, the reciprocal direction is
  * 1.0f / d per component.  A NaN direction hits nothing and is answered without traversing.
  *
@@ -22,8 +22,16 @@
 #ifndef RT_QUERY_KERNEL_H
 #define RT_QUERY_KERNEL_H
 
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_device_scene.h"
+#include "rt_intersect.h"
 #include "rt_query.h"
 #include "rt_ray_kernel.h"
+#include "rt_surface.h"
+#include "rt_traverse.h"
+#include "rt_vec.h"
 
 #define RT_QUERY_REFILL 16      /* lanes of a wave holding a finished ray before the traversal loop yields to store and refill them (not tuned) */
 

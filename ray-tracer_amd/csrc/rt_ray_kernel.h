@@ -2,7 +2,7 @@
  * rt_ray_kernel.h — the launch path the ray kernels (rt_query_kernel.h: closest hit; rt_occlusion_kernel.h: any hit; rt_ao_kernel.h: the
  * ambient-occlusion plane, one front under both values of `front`) share: one launcher
  * over the kernel (the LDS opt-in, the occupancy cache, the grid sized from the ray count) and one table of its instantiations over
- * RT_SHAPES.  Included by rt_kernel.hip ahead of the kernel headers.  The grid: one wave per 64 rays up to the persistent grid (every
+ * RT_SHAPES.  The grid: one wave per 64 rays up to the persistent grid (every
  * CU filled), so a handful of rays stages the scene once, not once per CU.
  *
  * The kernels' device code (the hand-out of ray ids, the tile slots and primary rays of a view, the MESH and WORK sections) is still stated in
@@ -11,6 +11,13 @@
  */
 #ifndef RT_RAY_KERNEL_H
 #define RT_RAY_KERNEL_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <array>
+#include <iterator>
+#include <utility>
 
 #include "rt_device_scene.h"
 

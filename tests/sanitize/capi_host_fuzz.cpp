@@ -2,7 +2,7 @@
 // rt_partition_tiles (longest-processing-time-first ownership), rt_tile_owned_rows, the render schedule, the output layout,
 // the kernel shape choice and the scheduling knobs' mapping (rt_schedule.h) with their properties asserted, and every entry
 // point's refusal of null / bad arguments before it touches HIP.  The three files are compiled as host C++ against the HIP runtime's API header and linked with the runtime library; the
-// kernel launchers (rt_kernel.hip) are replaced by stubs that fail - nothing here reaches a launch.
+// kernel launchers (rt_render_kernel.h, rt_frame_kernels.h, rt_debug_kernels.h) are replaced by stubs that fail - nothing here reaches a launch.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -318,17 +318,10 @@ template <class Rng> static bool check_shape(Rng &rng)
 }
 
 /* ---- progress of the render kernel's wave loop under every accepted knob value ------------------------------------------------------
- * rt_render_kernel (rt_kernel.hip) is a loop of rounds: finish misses, SHADE a batch of hits if the shade condition holds, fetch pixels, generate
- * rays, enter meshes, then run traversal steps until the traversal loop's break condition holds.  The two conditions, restated here from the
- * kernel (its comment above the shade condition points back; change them together):
+ * rt_render_kernel (rt_render_kernel.h) is a loop of rounds: finish misses, SHADE a batch of hits if the shade condition holds, fetch pixels,
+ * generate rays, enter meshes, then run traversal steps until the traversal loop's break condition holds.  The two conditions are the kernel's
+ * own statement of them, rt_traversal_yields and RT_ROUND_SHADES of rt_device_scene.h, here on rt_sched::KernelKnobs:
  *   n_hit lanes hold a hit to shade, n_trav == n_active lanes traverse, n_light lanes have cheap work, the rest are done. */
-static bool traversal_loop_breaks(const rt_sched::KernelKnobs &a, int n_hit, int n_active, int n_light)
-{
-    if (n_active == 0) return true;
-    return n_hit + n_light > 0 && (n_active < a.work_threshold || n_hit >= a.hit_break || n_light >= a.ready_break || (n_hit >= a.hit_low && n_hit + n_light >= a.mix_break));
-}
-static bool round_shades_mesh(const rt_sched::KernelKnobs &a, int n_hit, int n_trav) { return n_hit > 0 && (n_hit >= a.hit_low || n_trav < a.work_threshold); }
-static bool round_shades_no_mesh(const rt_sched::KernelKnobs &a, int n_hit, bool others) { return n_hit > 0 && (n_hit >= a.shade_batch || !others); }
 
 /* the mapping before rt_sched::kernel_knobs existed (rt_capi.cpp filled the kernel's arguments with this expression): kept to show that
  * check_progress tells the two apart */
@@ -381,7 +374,7 @@ template <class Mapping> static long long check_progress(Mapping mapping, const 
                         for (int n_hit = 1; n_hit <= 63; n_hit++)
                             for (int n_active = 1; n_hit + n_active <= 64; n_active++) {
                                 checked++;
-                                if (traversal_loop_breaks(a, n_hit, n_active, 0) && !round_shades_mesh(a, n_hit, n_active)) {
+                                if (rt_traversal_yields(a, n_hit, n_active, 0) && !RT_ROUND_SHADES(a, true, n_hit, n_active, false)) {
                                     std::fprintf(stderr, "progress: %d threads, RT_AMD_MIX_BREAK%s%d RT_AMD_WORK_THRESHOLD=%d RT_AMD_HIT_BREAK=%d RT_AMD_HIT_LOW=%d (kernel: hit_low %d, mix_break %d): "
                                                  "a wave of %d hits, %d traversing, %d done leaves the traversal loop and shades nothing\n",
                                                  threads, mix < 0 ? " unset: " : "=", mix < 0 ? a.mix_break : mix, w, b, l, a.hit_low, a.mix_break, n_hit, n_active, 64 - n_hit - n_active);
@@ -396,7 +389,7 @@ template <class Mapping> static long long check_progress(Mapping mapping, const 
         const rt_sched::KernelKnobs a = mapping(k, 256);
         for (int n_hit = 1; n_hit <= 64; n_hit++) {
             checked++;
-            if (!round_shades_no_mesh(a, n_hit, false)) { std::fprintf(stderr, "progress: no mesh, RT_AMD_SHADE_BATCH=%d: %d hits and no other lane, nothing shaded\n", s, n_hit); return -1; }
+            if (!RT_ROUND_SHADES(a, false, n_hit, 0, false)) { std::fprintf(stderr, "progress: no mesh, RT_AMD_SHADE_BATCH=%d: %d hits and no other lane, nothing shaded\n", s, n_hit); return -1; }
         }
     }
     return checked;

@@ -76,7 +76,7 @@ def test_device_equals_host(rt, ctx, host_eval, op, name, gen):
 
 
 def test_short_reciprocal_and_square_root_are_the_ieee_ones_for_all_inputs(rt, ctx):
-    """rt_pixel.h computes 1 / x as v_rcp_f32 + one Newton step and sqrt(x) as x * v_rsq_f32 + one fma residual step whenever every
+    """rt_vec.h computes 1 / x as v_rcp_f32 + one Newton step and sqrt(x) as x * v_rsq_f32 + one fma residual step whenever every
     lane's operand is inside the range those short forms are exact on (2^-126 <= |x| <= 2^126; 2^-64 <= x < inf), and as the
     compiler's IEEE expansion otherwise.  "Exact" is checked here for EVERY binary32 input on the device: inside the ranges
     not one of the 4.2e9 (reciprocal) and 1.6e9 (square root) inputs may differ from 1.0f / x and sqrtf(x)."""

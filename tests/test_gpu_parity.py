@@ -478,7 +478,7 @@ def test_random_mixed_scenes(rt, orc, ctx, models_dir, seed):
 @pytest.mark.parametrize("aa", [False, True])
 def test_rays_with_a_zero_direction_component(rt, orc, ctx, models_dir, aa):
     """A direction component of exactly 0 makes 1/d infinite and (plane - origin) * (1/d) a NaN whenever the origin
-    lies ON a box plane.  The kernel's six-med3 slab test (rt_pixel.h box_enter_med3) is only proved equal to the
+    lies ON a box plane.  The kernel's six-med3 slab test (rt_intersect.h box_enter_med3) is only proved equal to the
     reference's min/max form (src/objects.cu:404-434, fminf/fmaxf drop a NaN operand) for products that are numbers, so
     traversals of such rays take the min/max copy of the loop.  Here: a camera at the origin whose pixel grid puts a whole
     column at x == 0 and a whole row at y == 0 (antialias off: the primary rays keep those zeros), meshes whose vertices -
@@ -506,7 +506,7 @@ def test_rays_with_a_zero_direction_component(rt, orc, ctx, models_dir, aa):
 @pytest.mark.parametrize("aa", [False, True])
 def test_extreme_operands_of_the_sphere_test(rt, orc, ctx, models_dir, aa):
     """The device computes the sphere test's near root with a short division (rt_math.h rt__div_benign) whose precondition the code
-    argues from `d` being a unit vector (rt_pixel.h).  Here the operands the argument has to cover: cameras so far away that a ray's
+    argues from `d` being a unit vector (rt_intersect.h, rt_closest_simple).  Here the operands the argument has to cover: cameras so far away that a ray's
     squared length overflows (d = 0 or NaN), spheres at astronomic distances (infinite discriminants and dividends), a ray origin
     exactly ON a sphere (dividends that cancel to ~0), radius 0 and a sphere around the camera, mixed with ordinary geometry so that
     accepted hits exist next to the rejected ones.  The oracle divides with the operator: the frames must be the same bits."""

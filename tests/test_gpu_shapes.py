@@ -232,7 +232,7 @@ def test_every_shape_has_a_case():
 
 
 # ---- the knob matrix ------------------------------------------------------------------------------------------------------------------
-# each row forces one control path of the render kernel's wave loop (rt_kernel.hip); every value is inside rt_ctx_create's ranges
+# each row forces one control path of the render kernel's wave loop (rt_render_kernel.h); every value is inside rt_ctx_create's ranges
 KNOB_ROWS = {
     "yield-whenever-ready": {"RT_AMD_WORK_THRESHOLD": "64"},                     # the traversal loop leaves whenever any lane is ready
     "never-yield": {"RT_AMD_WORK_THRESHOLD": "1", "RT_AMD_READY_BREAK": "65", "RT_AMD_HIT_BREAK": "65", "RT_AMD_HIT_LOW": "0"},   # ... only when no lane traverses

@@ -94,7 +94,7 @@ def test_dense_accuracy_against_libm(tmp_path):
 def test_short_division_equals_the_operator_where_its_call_sites_use_it(tmp_path):
     """rt_math.h rt__div_benign (reciprocal + one residual step; Markstein) against `/` on 60 million random operand pairs per class:
     a general benign class, the operands of Box-Muller's f / (2 + f), the sphere test's dividend / (2 |d|^2) from 2^-90 up.  (Below
-    ~2^-103 the residual underflows and quotients differ - the sphere test rejects such distances either way: rt_pixel.h.)"""
+    ~2^-103 the residual underflows and quotients differ - the sphere test rejects such distances either way: rt_intersect.h, rt_closest_simple.)"""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,8 +1,8 @@
 """The two forms of the slab test are the same function where the kernel uses the short one (CPU property test).
 
-rt_pixel.h box_enter is the reference's BoundingBox::ray_hits (src/objects.cu:404-434) folded with the traversal's
+rt_intersect.h box_enter is the reference's BoundingBox::ray_hits (src/objects.cu:404-434) folded with the traversal's
 `entry distance < best`; box_enter_med3 (round 4) is two chains of three v_med3_f32 - clamp 0 and `best` through the three
-slabs' intervals, enter iff the first is below the second.  rt_pixel.h argues that both make the same decision and, where
+slabs' intervals, enter iff the first is below the second.  rt_intersect.h argues that both make the same decision and, where
 the box is entered, report the same entry distance, for every ray whose slab distances are numbers (no 0 * inf: no direction
 component of exactly 0 - those rays take the min / max copy of the loop).  Here both forms are evaluated in binary32 (numpy)
 on millions of random and adversarial cases: boxes in front, behind, around the origin, flat boxes, touching slabs, origins ON
@@ -14,7 +14,7 @@ INF_F = F(1073741824.0)
 
 
 def box_enter(b, o, inv, best):
-    """(enter, tmin) as rt_pixel.h box_enter: fminf / fmaxf drop NaNs"""
+    """(enter, tmin) as rt_intersect.h box_enter: fminf / fmaxf drop NaNs"""
     tmin = np.zeros(o.shape[0], F)
     tmax = np.full(o.shape[0], INF_F, F)
     with np.errstate(all="ignore"):
