@@ -476,6 +476,94 @@ rt_status rt_denoise_device(rt_ctx *ctx, int32_t width, int32_t height, const fl
 rt_status rt_denoise(rt_ctx *ctx, int32_t width, int32_t height, const float *colour, const float *normal, const float *depth,
                      const int32_t *object, const float *albedo, const rt_denoise_params *params, float *out);
 
+/* ---- per-pixel sample budgets and the adaptive sampling loop -------------------------------------
+ * rt_render_device spends rays_per_pixel samples on every pixel; here every pixel has a sample count of its own, so that samples go
+ * where the noise is.  Three layers, each defined to the bit: all arithmetic is binary32, every operation is rounded once, nothing is
+ * fused.
+ *
+ * 1. Budget render.  d_budget (W*H uint16) and d_count (W*H uint32, or NULL) are planes in rt_render's row-major full-frame layout,
+ *    d_frame a full W*H*3 frame.  rs->rays_per_pixel is not read; reflection_limit, antialias and sky_colour apply as in
+ *    rt_render_device.  Per pixel, with n = d_budget[pixel] and m = d_count[pixel] (0 for every pixel when d_count == NULL):
+ *      n == 0: nothing of the pixel is read or written;
+ *      n >  0: c = the per-pixel mean rt_render_device computes for the pixel with rays_per_pixel = n and this time_ms: the same stream
+ *              (state = (uint32)((py * W + px) * 3) * 3145739u + (uint32)time_ms * 6291469u, src/raytracer.cu:127), its n samples summed
+ *              in order and divided by (float)n; a reflection_limit <= 0 gives (0, 0, 0), as there.
+ *              m == 0: frame = c (the old content is not read: an uninitialised frame is fine);
+ *              else    frame.k = (c.k * (float)n + frame.k * (float)m) / (float)(n + m) per channel k.
+ *              A NaN result is stored as the canonical quiet NaN 0x7FC00000.  count = m + n (not written when d_count == NULL).
+ *    So a pixel rendered with budget n from count 0 IS the pixel rt_render_device renders at rays_per_pixel = n, frame_num = 0
+ *    (tests/test_gpu_adaptive.py: equal as uint32), and a frame accumulated over calls is the sample-count-weighted mean of their means.
+ *    tiles == NULL: the whole image; a tile list with compact == 0: only the listed tiles' pixels are considered, and the tiles are
+ *    handed to the waves in list order (the caller orders them: the launch neither collects nor uses tile costs).  Bands (a tile spec
+ *    without a list), compact != 0 and tile_cost / tile_peak are RT_ERR_INVALID, as are a null ctx, scene, cam, rs, d_budget or
+ *    d_frame, a scene of another context, a negative reflection_limit, a bad image size and a list with an index outside the image or
+ *    listed twice.  A budget is at most RT_BUDGET_MAX, the plane's type.
+ *    The launch is asynchronous on hip_stream and ordered like rt_render_device; rt_last_kernel_ms reports it. */
+#define RT_BUDGET_MAX 65535
+rt_status rt_render_budget_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
+                                  int32_t time_ms, const rt_tile_spec *tiles, const uint16_t *d_budget, uint32_t *d_count,
+                                  float *d_frame, void *hip_stream);
+/* Host-buffer form: budget (W*H), count (W*H, or NULL) and frame (W*H*3) are host memory; count and frame are read, updated and
+ * written back; returns when they are. */
+rt_status rt_render_budget(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs,
+                           int32_t time_ms, const rt_tile_spec *tiles, const uint16_t *budget, uint32_t *count, float *frame);
+
+/* 2. Plan.  Image-space, no scene: the two-half-buffer stopping rule of Dammertz et al. 2010, "A hierarchical automatic stopping
+ *    condition for Monte Carlo global illumination", on the renderer's 8x8 tiles.  A and B (W*H*3 each) are two independent
+ *    accumulations of one view, count (W*H uint32) the samples in EACH of them.  Per pixel
+ *      I.k = (A.k + B.k) * 0.5f;  num = (|A.r - B.r| + |A.g - B.g|) + |A.b - B.b|;  s = (I.r + I.g) + I.b;
+ *      e = num / sqrtf(s > floor ? s : floor); a NaN e becomes 0 (a NaN pixel never converges, so it is not sampled for its own sake).
+ *    Per tile: E = (the sum of e over the tile's 64 slots, a slot outside the image counting 0.0f) / (float)(the tile's pixels inside
+ *    the image).  The sum is the xor butterfly over slot = row * 8 + column: v[i] = v[i] + v[i ^ 1], then ^ 2, ^ 4, ... ^ 32 - a
+ *    pairwise tree: neighbours, then pairs of pairs, ...
+ *    A pixel is active iff count < max_spp and (E > threshold or e > pixel_threshold); its budget is min(step_spp, max_spp - count)
+ *    if active, else 0.  Outputs: d_budget (W*H uint16), d_tile_error (one float per tile, E) and d_tile_active (one uint32 per tile,
+ *    its number of active pixels); tile ty * ceil(W / 8) + tx.  pilot_spp and max_passes are not read by the plan (checked all the
+ *    same). */
+typedef struct rt_adaptive_params {
+    int32_t pilot_spp;           /* 1 .. 65535: the samples every pixel gets in each half buffer before the first plan */
+    int32_t step_spp;            /* 1 .. 65535: an active pixel's samples per pass and half buffer */
+    int32_t max_spp;             /* pilot_spp .. 2^24: no pixel gets more per half buffer */
+    int32_t max_passes;          /* 0 .. 64: passes after the pilot (0: the pilot only) */
+    float threshold;             /* > 0 and finite: a tile whose mean error E is above it keeps all its pixels sampling */
+    float pixel_threshold;       /* > 0, +inf: off: a pixel whose own e is above it keeps sampling whatever its tile says */
+    float floor;                 /* > 0 and finite: the least brightness the error is taken relative to */
+    int32_t reserved[1];         /* 0 */
+} rt_adaptive_params;            /* 32 bytes */
+#define RT_ADAPTIVE_MAX_SPP 16777216
+#define RT_ADAPTIVE_MAX_PASSES 64
+/* The defaults: pilot_spp 8, step_spp 16, max_spp 512, max_passes 16, threshold 0.05, pixel_threshold +inf, floor 0.01.  Tuned on the
+ * CPU oracle alone (cube and monkey scenes, 128 x 128, default camera, 8 bounces, target 1024 spp; tests/test_adaptive_ref.py and
+ * DESIGN.md §16 have the figures). */
+void rt_adaptive_params_default(rt_adaptive_params *p);
+/* Asynchronous on hip_stream and ordered like rt_render_device.  A null pointer, a bad image size, parameters outside the ranges above
+ * and a non-zero `reserved` are RT_ERR_INVALID. */
+rt_status rt_adaptive_plan_device(rt_ctx *ctx, int32_t width, int32_t height, const float *d_a, const float *d_b, const uint32_t *d_count,
+                                  const rt_adaptive_params *params, uint16_t *d_budget, float *d_tile_error, uint32_t *d_tile_active,
+                                  void *hip_stream);
+
+/* 3. Driver.  The loop, on buffers of the context's own (A, B, their count planes, the budget plane, the per-tile planes: 34 bytes per
+ *    pixel, kept until the context goes):
+ *      pass 0:                  a uniform budget pilot_spp over all tiles, into A with seed time_ms, into B with seed time_ms + 1;
+ *      pass k = 1..max_passes:  plan; stop if no tile has an active pixel; the tile list is the tiles with an active pixel by
+ *                               decreasing E, ties by the lower index (the longest jobs first); budget render of the list into A with
+ *                               seed time_ms + 2k and into B with seed time_ms + 2k + 1 (seeds wrap as 32-bit integers);
+ *      end:                     d_frame = (A + B) * 0.5f, a NaN as the canonical quiet NaN; d_count (W*H uint32, or NULL) = 2 * count.
+ *    d_frame and d_count are device memory.  The call BLOCKS until they are written: it reads the per-tile planes back between passes.
+ *    Its work runs on hip_stream.  stats (or NULL) reports what was done. */
+typedef struct rt_adaptive_stats {
+    int32_t passes;              /* passes rendered after the pilot */
+    int32_t reserved;            /* 0 */
+    uint64_t total_samples;      /* over all pixels and both half buffers: the sum of d_count */
+    int32_t active_tiles[RT_ADAPTIVE_MAX_PASSES];   /* [k - 1]: the tiles pass k rendered; 0 beyond `passes` */
+} rt_adaptive_stats;             /* 272 bytes */
+rt_status rt_render_adaptive(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, int32_t time_ms,
+                             const rt_adaptive_params *params, float *d_frame, uint32_t *d_count, rt_adaptive_stats *stats,
+                             void *hip_stream);
+/* Host-buffer form: frame (W*H*3) and count (W*H, or NULL) are host memory. */
+rt_status rt_render_adaptive_host(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, int32_t time_ms,
+                                  const rt_adaptive_params *params, float *frame, uint32_t *count, rt_adaptive_stats *stats);
+
 /* ---- several GPUs of one node from one host thread ---------------------------------------------
  * What run_ray_tracer (src/dispatch.cu:127-153) does on one device, n devices do for the bands they
  * own: rank i of n_ranks renders the bands b with b % n_ranks == i (a pixel depends

@@ -59,6 +59,19 @@ class rt_denoise_params(C.Structure):
                 ("albedo_floor", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
+class rt_adaptive_params(C.Structure):
+    _fields_ = [("pilot_spp", C.c_int32), ("step_spp", C.c_int32), ("max_spp", C.c_int32), ("max_passes", C.c_int32),
+                ("threshold", C.c_float), ("pixel_threshold", C.c_float), ("floor", C.c_float), ("reserved", C.c_int32 * 1)]
+
+
+ADAPTIVE_MAX_PASSES, ADAPTIVE_MAX_SPP = 64, 1 << 24   # RT_ADAPTIVE_*
+BUDGET_MAX = 65535                                     # RT_BUDGET_MAX: the most samples one budget render gives a pixel
+
+
+class rt_adaptive_stats(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("reserved", C.c_int32), ("total_samples", C.c_uint64), ("active_tiles", C.c_int32 * ADAPTIVE_MAX_PASSES)]
+
+
 # rt_hit (include/rt_amd.h) as a NumPy record: what trace_rays returns
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal", np.float32, (3,)), ("object", np.int32),
                       ("triangle", np.int32), ("u", np.float32), ("v", np.float32), ("reserved", np.int32)])
@@ -76,6 +89,7 @@ i64, f32, vp, cstr = C.c_int64, C.c_float, C.c_void_p, C.c_char_p
 fp, i32p, u32p, u64p, vpp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)
 mat, cam, rs = C.POINTER(rt_material), C.POINTER(rt_camera), C.POINTER(rt_render_settings)
 tiles, ranks, dnp = C.POINTER(rt_tile_spec), C.POINTER(rt_rank), C.POINTER(rt_denoise_params)
+adp, ads = C.POINTER(rt_adaptive_params), C.POINTER(rt_adaptive_stats)
 ABI = {
     "rt_material_standard": (None, [mat, fp, f32]),
     "rt_material_checkerboard": (None, [mat, fp, fp, i32, f32]),
@@ -148,6 +162,12 @@ ABI = {
     "rt_denoise_params_default": (None, [dnp]),
     "rt_denoise_device": (st, [vp, i32, i32, vp, vp, vp, vp, vp, dnp, vp, vp]),
     "rt_denoise": (st, [vp, i32, i32, fp, fp, fp, i32p, fp, dnp, fp]),
+    "rt_render_budget_device": (st, [vp, vp, cam, rs, i32, tiles, vp, vp, vp, vp]),
+    "rt_render_budget": (st, [vp, vp, cam, rs, i32, tiles, vp, u32p, fp]),
+    "rt_adaptive_params_default": (None, [adp]),
+    "rt_adaptive_plan_device": (st, [vp, i32, i32, vp, vp, vp, adp, vp, vp, vp, vp]),
+    "rt_render_adaptive": (st, [vp, vp, cam, rs, i32, adp, vp, vp, ads, vp]),
+    "rt_render_adaptive_host": (st, [vp, vp, cam, rs, i32, adp, fp, u32p, ads]),
     "rt_render_multi": (st, [ranks, i32, cam, rs, i32p, i32, i32p, fp]),
     "rt_render_multi_device": (st, [ranks, i32, cam, rs, i32p, i32, i32, i32, vp, vp]),
     "rt_gather": (st, [vp, vp, i32, i32, vp, vp, tiles, vp]),

@@ -12,9 +12,11 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libraytracer_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_denoise_capi.cpp", "rt_host.cpp")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_denoise_capi.cpp", "rt_adaptive_capi.cpp", "rt_host.cpp")]
 # every header there is: a new one cannot be forgotten, and needs_build() then serves no stale library after an edit
 HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "rt_amd.h")]
+# text a header includes more than once (the wave loop both render kernels run): watched like the headers
+INCLUDED = sorted(glob.glob(os.path.join(HERE, "csrc", "*.inc")))
 # -fno-slp-vectorize: the SLP vectorizer pairs the scalar f32 adds / multiplies of the vector math into v_pk_*_f32, which
 # are not faster on gfx950 and need register pairs: 128 instead of ~90 VGPRs and ~10 % more time (same-box A/B, round 2).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17",
@@ -32,7 +34,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(p) > t for p in SOURCES + HEADERS)
+    return any(os.path.getmtime(p) > t for p in SOURCES + HEADERS + INCLUDED)
 
 
 def build_variant(name, extra_flags):
@@ -55,6 +57,7 @@ def build(force=False, verbose=False):
 EXAMPLE = os.path.join(HERE, "host", "example_main")
 QUERY_EXAMPLE = os.path.join(HERE, "host", "example_query")
 DENOISE_EXAMPLE = os.path.join(HERE, "host", "example_denoise")
+ADAPTIVE_EXAMPLE = os.path.join(HERE, "host", "example_adaptive")
 
 
 def _build_host_program(source, exe):
@@ -78,6 +81,11 @@ def build_query_example():
 def build_denoise_example():
     """The mirror's denoiser (host/example_denoise.cpp): the reference's monkey_test_scene (scene 0) at a few samples per pixel, noisy and denoised side by side as a PNG."""
     return _build_host_program("example_denoise.cpp", DENOISE_EXAMPLE)
+
+
+def build_adaptive_example():
+    """The mirror's adaptive sampling (host/example_adaptive.cpp): the monkey scene sampled to a noise target, the frame and the map of where the samples went as PNGs."""
+    return _build_host_program("example_adaptive.cpp", ADAPTIVE_EXAMPLE)
 
 
 if __name__ == "__main__":

@@ -287,7 +287,7 @@ extern "C" int32_t rt_max_batch_frames(rt_ctx *ctx, int32_t width, int32_t heigh
 }
 
 /* persistent waves: enough workgroups to fill the chip, each wave pulls 8x8 tiles */
-static int launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles)
+int rt_detail::launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles)
 {
     const int waves_per_block = scene->kernel.shape.threads / 64;
     int blocks = ctx->num_cus * scene->kernel.blocks_per_cu;
@@ -400,8 +400,8 @@ static rt_status check_launch(rt_ctx *ctx, const rt_scene *scene, const rt_camer
     return RT_OK;
 }
 
-static rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
-                                  int32_t n_frames, int32_t frame_num, const rt_sched::Layout &L, const float *d_prev, float *d_out, uint32_t *tile_counter)
+rt_kernel_args rt_detail::kernel_args(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
+                                      int32_t n_frames, int32_t frame_num, const rt_sched::Layout &L, const float *d_prev, float *d_out, uint32_t *tile_counter)
 {
     rt_kernel_args a;
     std::memset(&a, 0, sizeof a);

@@ -210,6 +210,11 @@ struct rt_ctx {
     DevBuf<rt_f4> d_query_out;
     /* rt_denoise[_device] (rt_denoise_capi.cpp): per pixel the guide record and the two colour records the levels alternate between */
     DevBuf<rt_f4> d_denoise;
+    /* rt_render_adaptive (rt_adaptive_capi.cpp): the half buffers A and B (W*H*3 each, one after the other), their count planes (W*H each),
+     * the per-tile error and active-pixel planes (one after the other), the budget plane and the pass's tile list */
+    DevBuf<float> d_adaptive_ab;
+    DevBuf<uint32_t> d_adaptive_count, d_adaptive_tiles;
+    DevBuf<uint16_t> d_adaptive_budget;
     Pipeline pipe;
     MultiRank multi;
 };
@@ -258,6 +263,11 @@ RT_HIDDEN rt_status render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_c
 RT_HIDDEN rt_status fold(rt_ctx *ctx, const rt_sched::Layout &L, const float *planes, int n_frames, int frame_num, float *d_out, const uint32_t *d_tile_list,
                          hipStream_t stream);
 RT_HIDDEN rt_status ensure_frame_buffers(rt_ctx *ctx, size_t bytes);
+/* the render kernel's argument block for a launch of layout L (tile order, tile list and outputs beyond d_out are the caller's to add),
+ * and the size of its grid: what rt_adaptive_capi.cpp launches the budget variant with */
+RT_HIDDEN rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const int32_t *times_ms,
+                                     int32_t n_frames, int32_t frame_num, const rt_sched::Layout &L, const float *d_prev, float *d_out, uint32_t *tile_counter);
+RT_HIDDEN int launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles);
 RT_HIDDEN int batch_cap(const rt_ctx *ctx, size_t plane_floats);
 RT_HIDDEN void push_camera(std::vector<uint32_t> &key, const rt_camera *cam);
 

@@ -47,6 +47,7 @@
  */
 #include "rt_ray_kernels.h"        /* closest-hit, any-hit and ambient-occlusion ray kernels (not in the development builds) */
 #include "rt_denoise_kernel.h"     /* the edge-avoiding a-trous denoiser: image-space passes, nothing of the traversal (in every build) */
+#include "rt_adaptive_kernel.h"    /* the adaptive sampling loop's image-space passes: plan, combine */
 #include "rt_frame_kernels.h"      /* blend, tile copy, RGBA8 */
 #include "rt_debug_kernels.h"      /* the math headers evaluated on the device, for the tests */
 #include "rt_render_kernel.h"      /* the render kernel and its shape table */

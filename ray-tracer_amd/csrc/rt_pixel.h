@@ -46,6 +46,18 @@ struct Frame {
     int W, H, spp, limit, tiles_per_band;
 };
 
+/* The argument block of the budget variant of the render kernel (rt_budget_kernel, rt_render_kernel.h; rt_render_budget_device in
+ * include/rt_amd.h): the render kernel's, and per pixel of the full frame how many samples it takes now and how many its value in `out`
+ * already holds.  The sections below are handed the base and, where BUDGET is set, read the rest through px_budget. */
+struct rt_budget_args : rt_kernel_args {
+    const uint16_t *budget;      /* W*H: this launch's samples per pixel; 0: the pixel is neither read nor written */
+    uint32_t *count;             /* W*H, or NULL (every pixel starts from nothing and no count is kept) */
+};
+/* (only under BUDGET, and the one user with BUDGET set is rt_budget_loop, whose parameter is an rt_budget_args: the render kernel's plain
+ * block never gets here.  Carrying that in the sections' parameter type costs the budget kernels their registers:
+ * profiles/r09/experiments/budget_loop_forms.txt) */
+__device__ __forceinline__ const rt_budget_args &px_budget(const rt_kernel_args &a) { return static_cast<const rt_budget_args &>(a); }
+
 /* wave-uniform pixel chunk: linear pixel ids [next, end) of one 8x8 tile */
 struct Chunk {
     uint32_t next, end;
@@ -94,6 +106,32 @@ __device__ __forceinline__ void tile_place(const rt_kernel_args &a, const Frame 
     }
 }
 
+/* BUDGET: a pixel's n samples are done (n is read again here rather than kept in a register across the pixel: p.sample counts DOWN from
+ * it, so the lane state is the render kernel's).  With m = the samples its value in the frame already holds, the frame becomes the mean
+ * over all n + m: c if m == 0 (the frame is not read), else (c * n + frame * m) / (n + m), every operation rounded once; the count
+ * becomes m + n.  Always a full frame (rt_render_budget_device refuses compact layouts). */
+__device__ __forceinline__ void px_finish_budget(Px &p, const rt_kernel_args &a, const Frame &f)
+{
+    const rt_budget_args &b = px_budget(a);
+    const int tile = (int)(p.id >> 6), within = (int)(p.id & 63u);
+    int tx, ty, compact_row;
+    tile_place(a, f, tile, tx, ty, compact_row);
+    const int px = tx * 8 + (within & 7), py = ty * 8 + (within >> 3);
+    const size_t pixel = (size_t)py * (size_t)f.W + (size_t)px;
+    const uint32_t n = b.budget[pixel];
+    const uint32_t m = b.count ? b.count[pixel] : 0u;
+    const float fn = (float)n;
+    V3 res = p.colour / fn;
+    float *dst = a.out + pixel * 3;
+    if (m != 0u) {
+        const V3 previous = v3(dst[0], dst[1], dst[2]);
+        res = (res * fn + previous * (float)m) / (float)(n + m);
+    }
+    dst[0] = rt_canon_nan(res.x); dst[1] = rt_canon_nan(res.y); dst[2] = rt_canon_nan(res.z);
+    if (b.count) b.count[pixel] = m + n;
+    p.mode = M_FETCH;
+}
+
 /* A pixel's samples are done: blend with the previous frame and store (src/raytracer.cu:107-112,
  * :133-135).
  *
@@ -105,8 +143,10 @@ __device__ __forceinline__ void tile_place(const rt_kernel_args &a, const Frame 
  * (plain stores, no ordering between frames needed), and a small kernel launched behind this one
  * (rt_blend_kernel) folds the planes into the frame buffer in frame order; NaN pixels are made the one
  * canonical quiet NaN there (any NaN plane value makes the blended value a NaN). */
+template <bool BUDGET = false>
 __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, const Frame &f)
 {
+    if (BUDGET) { px_finish_budget(p, a, f); return; }
     const V3 c = p.colour / (float)f.spp;
     const int tile = (int)(p.id >> 6), within = (int)(p.id & 63u);
     int tx, ty, compact_row;
@@ -147,9 +187,19 @@ __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, 
 
 /* the end of a sample (src/raytracer.cu:102-105): add it to the pixel, restart from a copy of the
  * primary ray; after the last sample the pixel is finished */
+template <bool BUDGET = false>
 __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     p.colour = p.colour + p.fin;
+    if (BUDGET) {
+        /* p.sample: the samples of the pixel's budget still to come.  (The restart lines are the render branch's below, stated twice so that
+         * the render kernel's code stays byte for byte: a change to either copy goes into both.) */
+        p.sample--;
+        p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
+        p.o = f.cam_pos; p.d = p.primary; p.bounce = 0; p.cur_n = 1.0f;
+        if (p.sample <= 0) px_finish_pixel<true>(p, a, f);
+        return;
+    }
     p.sample++;
     p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
     p.o = f.cam_pos; p.d = p.primary; p.bounce = 0; p.cur_n = 1.0f;
@@ -157,11 +207,12 @@ __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, co
 }
 
 /* ================= SHADE, a ray that hit nothing (src/raytracer.cu:76-80): sky, end of sample == */
+template <bool BUDGET = false>
 __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     p.fin = p.fin + f.sky * p.thr;
     p.mode = M_GEN;
-    px_end_sample(p, a, f);
+    px_end_sample<BUDGET>(p, a, f);
 }
 
 /* ================= SHADE: the closest hit of this bounce is known (p.best_obj >= 0) ========= */
@@ -170,7 +221,7 @@ __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, co
 /* GENERAL_FUNCTIONS: Box-Muller through rt_logf / rt_cosf instead of their forms for a draw's arguments (again the same values): the hybrid
  * kernels (nodes in LDS, triangles from L2) are 2.8 % FASTER that way on the 6,000-triangle scene and indifferent on the 50,880-triangle one
  * (profiles/r04/experiments/box_muller_on_its_domain.txt) */
-template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS>
+template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false>
 __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const Frame &f, const Lds &L)
 {
     V3 &o = p.o, &d = p.d;
@@ -287,13 +338,16 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
         p.frame_steps += (unsigned)(RT_COST_HIT * RT_MAX_BATCH_FRAMES);
     }
     p.mode = M_GEN;
-    if (p.bounce >= f.limit) px_end_sample(p, a, f);
+    if (p.bounce >= f.limit) px_end_sample<BUDGET>(p, a, f);
 }
 
 /* ================= FETCH: lanes without a pixel take the next ones =========================
  * Linear pixel ids are tile-major (64 per 8x8 tile), tiles come from a global counter; a wave
  * asks for one tile at a time and hands its ids out to whichever lanes are free.  Must be called
- * by the whole wave. */
+ * by the whole wave.  Every call with a lane in M_FETCH either hands that lane a slot it has not been handed before or, once the tiles
+ * are out, ends it (M_DONE): a lane that stays in M_FETCH (a slot outside the image; BUDGET: a pixel of budget 0) has used a slot up, so
+ * calling again until no lane is in M_FETCH ends after at most (tiles * 64) slots, whatever the budgets are. */
+template <bool BUDGET = false>
 __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args &a, const Frame &f, int lane)
 {
     const bool want = p.mode == M_FETCH;
@@ -359,6 +413,27 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
     const int px = tx * 8 + (within & 7);
     const int py = ty * 8 + (within >> 3);
     p.id = (unsigned)my_id;
+    if (BUDGET) {
+        /* the pixel's budget n; 0 (or a slot outside the image): the lane stays in M_FETCH and nothing of the pixel is touched.  The
+         * stream (the seed), the primary ray (the camera) and the restart state are the render branch's below, stated twice so that the
+         * render kernel's code stays byte for byte: a change to either copy goes into both.  p.sample counts down from n */
+        if (px >= f.W || py >= f.H) return;
+        const int n = (int)px_budget(a).budget[(size_t)py * (size_t)f.W + (size_t)px];
+        if (n == 0) return;
+        const int array_index = (py * f.W + px) * 3;
+        p.frame_steps = 0u;
+        p.rng = (uint32_t)array_index * 3145739u + a.seeds[0];
+        V3 plane_point = f.du * (float)px + f.dv * (float)py;
+        p.primary = normalised((f.tl + plane_point) - f.cam_pos);
+        p.colour = v3(0.f, 0.f, 0.f);
+        p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
+        p.o = f.cam_pos; p.d = p.primary;
+        p.bounce = 0; p.cur_n = 1.0f;
+        p.sample = n;
+        if (f.limit > 0) p.mode = M_GEN;
+        else px_finish_pixel<true>(p, a, f);                  /* a zero bounce limit traces nothing: (0,0,0) / n */
+        return;
+    }
     if (px < f.W && py < f.H) {
         /* src/raytracer.cu:123-127; Ray::set_direction_origin src/ray.cu:147-155,
          * cam_pixel_to_world src/camera.cu:24-29 */

@@ -17,6 +17,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -437,6 +438,50 @@ public:
         check(rt_denoise(ctx_, cam.c.width, cam.c.height, colour.data(), aov.normal.data(), aov.depth.data(), use_object ? aov.object.data() : nullptr,
                          use_albedo ? aov.albedo.data() : nullptr, &params, out.data()));
         return out;
+    }
+    /* Per-pixel sample budgets (rt_render_budget): pixel i takes budget[i] samples (0: it is left alone) and their mean is folded into
+     * acc->frame by sample counts, acc->count growing by the budget; an accumulation starts as Accumulation(cam).  tile_list: only these
+     * 8x8 tiles, in this order.  rd.c.rays_per_pixel is not read. */
+    struct Accumulation {
+        std::vector<float> frame;        /* W*H*3 */
+        std::vector<uint32_t> count;     /* W*H: the samples each pixel's value holds */
+        Accumulation() = default;
+        explicit Accumulation(const Camera &cam) : frame((size_t)cam.c.width * (size_t)cam.c.height * 3, 0.0f), count((size_t)cam.c.width * (size_t)cam.c.height, 0u) {}
+    };
+    void render_budget(const Camera &cam, const RenderData &rd, const std::vector<uint16_t> &budget, Accumulation *acc, int time_ms, const std::vector<uint32_t> *tile_list = nullptr)
+    {
+        const size_t px = (size_t)cam.c.width * (size_t)cam.c.height;
+        if (budget.size() != px || acc->frame.size() != px * 3 || acc->count.size() != px) throw std::invalid_argument("the budget and the accumulation must be of the camera's size");
+        rt_tile_spec ts{};
+        const uint32_t none = 0;
+        if (tile_list) {
+            ts.band_rows = 8; ts.band_stride = 1;
+            ts.tile_list = tile_list->empty() ? &none : tile_list->data();
+            ts.num_tiles = (int32_t)tile_list->size();
+        }
+        check(rt_render_budget(ctx_, scene_, &cam.c, &rd.c, time_ms, tile_list ? &ts : nullptr, budget.data(), acc->count.data(), acc->frame.data()));
+    }
+    /* The adaptive loop (rt_render_adaptive_host): a pilot, then passes that sample only where two half buffers of the view still disagree.
+     * Returns the frame, the samples every pixel got and what the loop did. */
+    static rt_adaptive_params adaptive_defaults()
+    {
+        rt_adaptive_params p;
+        rt_adaptive_params_default(&p);
+        return p;
+    }
+    struct Adaptive {
+        std::vector<float> frame;
+        std::vector<uint32_t> count;
+        rt_adaptive_stats stats;
+    };
+    Adaptive render_adaptive(const Camera &cam, const RenderData &rd, int time_ms, const rt_adaptive_params &params = adaptive_defaults())
+    {
+        const size_t px = (size_t)cam.c.width * (size_t)cam.c.height;
+        Adaptive a;
+        a.frame.resize(px * 3); a.count.resize(px);
+        std::memset(&a.stats, 0, sizeof a.stats);
+        check(rt_render_adaptive_host(ctx_, scene_, &cam.c, &rd.c, time_ms, &params, a.frame.data(), a.count.data(), &a.stats));
+        return a;
     }
     /* The main loop (src/main.cu:415-431) with frames in flight: submit_frame(get_time()) queues a frame and returns at once,
      * collect_frame() waits for the OLDEST submitted frame and blends it into data like render() would have.  With `depth`
