@@ -271,6 +271,51 @@ int32_t rt_frames_pending(const rt_ctx *ctx);
  * the cudaDeviceSynchronize of src/dispatch.cu:141 for this loop) - the younger frames keep running */
 rt_status rt_frame_wait(rt_ctx *ctx);
 
+/* ---- camera sequences: many views of a scene in one launch ---------------------------------------
+ * Everything above that keeps the GPU full renders many frames of ONE view; a caller whose camera moves (the reference's main loop with its
+ * WASD / arrow keys, src/main.cu:373-407; a turntable, a fly-through, a stereo pair, the six faces of a cube map, a light field) starts
+ * every frame cold and alone, and a launch that runs alone is as long as its longest pixel.  Here one launch renders n_views views:
+ * view i has the camera cams[i] and the seed times_ms[i] (the stream of rt_render_device: state = (uint32)((py * W + px) * 3) * 3145739u +
+ * (uint32)times_ms[i] * 6291469u, src/raytracer.cu:127), and every view's expensive tiles start at once.  All cameras share cams[0]'s
+ * width and height; whole images only (there is no tile spec).  Two modes:
+ *   accumulate == 0, separate frames: d_frames is n_views full W*H*3 frames back to back; frame i is, as uint32, what
+ *     rt_render_device(cams[i], times_ms[i], frame_num = 0, tiles = NULL, d_prev = NULL) writes - that is (c + 0 * 0) / 1 of the pixel's
+ *     mean c with a NaN stored as the canonical quiet NaN 0x7FC00000 (so a mean of -0 comes out +0).  d_frames is never read; frame_num
+ *     must be 0.
+ *   accumulate != 0, one frame: d_frames is ONE W*H*3 frame; view i is progressive frame frame_num + i, folded in order with
+ *     (c + prev * n) / (n + 1) (src/raytracer.cu:109-112): as uint32 what n_views chained calls of rt_render_device give, and with n_views
+ *     identical cameras what rt_render_device_batch gives.  The frame's content is ignored when frame_num == 0.  Cameras that differ by a
+ *     lens offset (rt_camera_lens) make this depth of field; cameras along a path, camera motion blur.
+ * Device form: n_views is 1 .. RT_VIEWS_MAX, and when accumulating at most rt_max_batch_frames (the context keeps one plane per view).
+ * Asynchronous on hip_stream and ordered like rt_render_device: one launch in flight per context, queued behind frames in flight.
+ * rt_last_kernel_ms reports it from the render kernel to the last fold.  The launch runs on a guessed schedule built from every view's own
+ * centre rays (no pilot, no cost collection) and does not touch the context's cached view: a warm view stays warm, rt_tile_costs answers as
+ * before.  RT_ERR_INVALID: a null ctx, scene, cams, times_ms, rs or d_frames; a scene of another context; n_views out of range; a
+ * negative frame_num, or a non-zero one with accumulate == 0; a negative rays_per_pixel or reflection_limit; a bad image size; a camera
+ * whose width or height differs from cams[0]'s.  A refused call touches nothing. */
+#define RT_VIEWS_MAX 32                /* = the frames of one multi-frame launch: views one launch renders */
+rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms,
+                                 int32_t n_views, const rt_render_settings *rs, int32_t accumulate, int32_t frame_num,
+                                 float *d_frames, void *hip_stream);
+/* Host-buffer form: frames is host memory (n_views frames, or one); any n_views >= 1, rendered in launches of up to the device form's
+ * limit.  When accumulating, frames is read (if *frame_num > 0) and *frame_num advances by n_views; otherwise *frame_num must be 0 and
+ * stays 0.  Returns when frames is filled.  A null frame_num is RT_ERR_INVALID too. */
+rt_status rt_render_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms,
+                          int32_t n_views, const rt_render_settings *rs, int32_t accumulate, int32_t *frame_num, float *frames);
+/* One thin-lens sample of a pinhole camera: the image plane moved out to the focus distance and the eye moved by (lens_u, lens_v) on the
+ * lens, along the camera's own axes.  focal_len is what the caller gave rt_camera_make (0.1 for rt_camera_default).  Defined in binary32,
+ * every operation rounded once, in this order, nothing fused (k over x, y, z; du = cam->delta_u, dv = cam->delta_v):
+ *     s = focus_dist / focal_len
+ *     out.delta_u.k = du.k * s;   out.delta_v.k = dv.k * s
+ *     out.tl_pixel_pos.k = (tl_pixel_pos.k - cam_pos.k) * s + cam_pos.k
+ *     eu.k = du.k * (1.0f / sqrtf((du.x*du.x + du.y*du.y) + du.z*du.z));   ev likewise from dv
+ *     out.cam_pos.k = (eu.k * lens_u + ev.k * lens_v) + cam_pos.k
+ * width and height are copied; out may be cam.  So tl_pixel_pos, delta_u and delta_v of the result do not depend on the offset: every
+ * sample's ray of pixel (px, py) passes through the same point of the focus plane, and rt_render_views with accumulate != 0 over n such
+ * cameras is a depth-of-field frame of n lens samples.  RT_ERR_INVALID (out untouched): a null pointer, a focal_len or focus_dist that is
+ * not positive and finite, an offset that is not finite, a delta_u or delta_v of length 0. */
+rt_status rt_camera_lens(const rt_camera *cam, float focal_len, float focus_dist, float lens_u, float lens_v, rt_camera *out);
+
 /* number of rows a rank owns under a band tile spec (host helper for sizing compact buffers) */
 int32_t rt_tile_owned_rows(const rt_tile_spec *tiles, int32_t height);
 

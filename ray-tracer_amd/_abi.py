@@ -66,6 +66,7 @@ class rt_adaptive_params(C.Structure):
 
 ADAPTIVE_MAX_PASSES, ADAPTIVE_MAX_SPP = 64, 1 << 24   # RT_ADAPTIVE_*
 BUDGET_MAX = 65535                                     # RT_BUDGET_MAX: the most samples one budget render gives a pixel
+VIEWS_MAX = 32                                         # RT_VIEWS_MAX: the views one launch of render_views_device renders
 
 
 class rt_adaptive_stats(C.Structure):
@@ -142,6 +143,9 @@ ABI = {
     "rt_frame_collect_host": (st, [vp, i32p, fp]),
     "rt_frames_pending": (i32, [vp]),
     "rt_frame_wait": (st, [vp]),
+    "rt_render_views_device": (st, [vp, vp, cam, i32p, i32, rs, i32, i32, vp, vp]),
+    "rt_render_views": (st, [vp, vp, cam, i32p, i32, rs, i32, i32p, fp]),
+    "rt_camera_lens": (st, [cam, f32, f32, f32, f32, cam]),
     "rt_tile_owned_rows": (i32, [tiles, i32]),
     "rt_tile_costs": (st, [vp, u32p, u32p, u32p, i32, i32p]),
     "rt_partition_tiles": (st, [u32p, i32, i32, i32, i32p]),

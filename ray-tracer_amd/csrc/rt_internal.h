@@ -150,6 +150,17 @@ struct View {
     int job_frames = 0;                  /* what the uploaded schedule was built for */
 };
 
+/* rt_render_views[_device] (rt_views_capi.cpp): what a launch reads beside the scene - the camera table (RT_VIEWS_MAX x 12 floats) and
+ * behind it the launch's schedule (rt_sched::views_job_order) - in one device buffer, written by one copy per call from `host`; ev_up:
+ * that copy has run, `host` may be rewritten.  d_frames: the host form's frames on the device. */
+struct ViewsState {
+    std::vector<uint32_t> host;
+    DevBuf<uint32_t> d_table;
+    DevBuf<float> d_frames;
+    Event ev_up;
+    bool uploaded = false;               /* ev_up has been recorded */
+};
+
 /* knobs (RT_AMD_*), none changes an image: rt_schedule.h has them, their accepted ranges and what the kernel is handed for them
  * (rt_sched::kernel_knobs; RT_AMD_HIT_LOW is clamped to RT_AMD_HIT_BREAK there) */
 using rt_sched::Knobs;
@@ -215,6 +226,7 @@ struct rt_ctx {
     DevBuf<float> d_adaptive_ab;
     DevBuf<uint32_t> d_adaptive_count, d_adaptive_tiles;
     DevBuf<uint16_t> d_adaptive_budget;
+    ViewsState views;
     Pipeline pipe;
     MultiRank multi;
 };

@@ -58,6 +58,15 @@ struct rt_budget_args : rt_kernel_args {
  * profiles/r09/experiments/budget_loop_forms.txt) */
 __device__ __forceinline__ const rt_budget_args &px_budget(const rt_kernel_args &a) { return static_cast<const rt_budget_args &>(a); }
 
+/* The argument block of the views variant of the render kernel (rt_views_kernel, rt_render_kernel.h; rt_render_views_device in
+ * include/rt_amd.h): the render kernel's, and one camera per frame of the launch.  `cam` of the base is not read: a lane takes the twelve
+ * floats of its frame's camera from the table (the index differs across the lanes of a wave, which refill from different chunks, so the
+ * table cannot be a kernel-argument array).  Only under VIEWS, and only rt_views_loop sets it: see px_budget. */
+struct rt_views_args : rt_kernel_args {
+    const float *cams;           /* num_frames x 12: cam_pos, tl_pixel_pos, delta_u, delta_v of frame k at cams + 12 * k */
+};
+__device__ __forceinline__ const rt_views_args &px_views(const rt_kernel_args &a) { return static_cast<const rt_views_args &>(a); }
+
 /* wave-uniform pixel chunk: linear pixel ids [next, end) of one 8x8 tile */
 struct Chunk {
     uint32_t next, end;
@@ -143,10 +152,23 @@ __device__ __forceinline__ void px_finish_budget(Px &p, const rt_kernel_args &a,
  * (plain stores, no ordering between frames needed), and a small kernel launched behind this one
  * (rt_blend_kernel) folds the planes into the frame buffer in frame order; NaN pixels are made the one
  * canonical quiet NaN there (any NaN plane value makes the blended value a NaN). */
-template <bool BUDGET = false>
+template <bool BUDGET = false, bool VIEWS = false>
 __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     if (BUDGET) { px_finish_budget(p, a, f); return; }
+    if (VIEWS) {
+        /* a views launch renders whole images into one plane per view and collects no costs: the mean goes to the pixel's place in its
+         * view's plane, and what becomes of the planes (the fold, or the frame-0 arithmetic of separate frames) runs behind the kernel */
+        const V3 c = p.colour / (float)f.spp;
+        const int tile = (int)(p.id >> 6), within = (int)(p.id & 63u);
+        const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+        const int px = tx * 8 + (within & 7), py = ty * 8 + (within >> 3);
+        const size_t pixel = (size_t)py * (size_t)f.W + (size_t)px;
+        float *dst = a.partial + ((size_t)(p.frame_steps & (unsigned)(RT_MAX_BATCH_FRAMES - 1)) * a.partial_plane + pixel) * 3;
+        dst[0] = c.x; dst[1] = c.y; dst[2] = c.z;
+        p.mode = M_FETCH;
+        return;
+    }
     const V3 c = p.colour / (float)f.spp;
     const int tile = (int)(p.id >> 6), within = (int)(p.id & 63u);
     int tx, ty, compact_row;
@@ -187,10 +209,20 @@ __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, 
 
 /* the end of a sample (src/raytracer.cu:102-105): add it to the pixel, restart from a copy of the
  * primary ray; after the last sample the pixel is finished */
-template <bool BUDGET = false>
+template <bool BUDGET = false, bool VIEWS = false>
 __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     p.colour = p.colour + p.fin;
+    if (VIEWS) {
+        /* the render branch's restart below with the camera position of the pixel's own view, read again from the table by the frame index
+         * in p.frame_steps rather than kept in three registers of Px (stated twice like the budget branch: a change goes into all copies) */
+        p.sample++;
+        p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
+        const float *cam = px_views(a).cams + 12u * (p.frame_steps & (unsigned)(RT_MAX_BATCH_FRAMES - 1));
+        p.o = v3(cam[0], cam[1], cam[2]); p.d = p.primary; p.bounce = 0; p.cur_n = 1.0f;
+        if (p.sample >= f.spp) px_finish_pixel<false, true>(p, a, f);
+        return;
+    }
     if (BUDGET) {
         /* p.sample: the samples of the pixel's budget still to come.  (The restart lines are the render branch's below, stated twice so that
          * the render kernel's code stays byte for byte: a change to either copy goes into both.) */
@@ -207,12 +239,12 @@ __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, co
 }
 
 /* ================= SHADE, a ray that hit nothing (src/raytracer.cu:76-80): sky, end of sample == */
-template <bool BUDGET = false>
+template <bool BUDGET = false, bool VIEWS = false>
 __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     p.fin = p.fin + f.sky * p.thr;
     p.mode = M_GEN;
-    px_end_sample<BUDGET>(p, a, f);
+    px_end_sample<BUDGET, VIEWS>(p, a, f);
 }
 
 /* ================= SHADE: the closest hit of this bounce is known (p.best_obj >= 0) ========= */
@@ -221,7 +253,7 @@ __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, co
 /* GENERAL_FUNCTIONS: Box-Muller through rt_logf / rt_cosf instead of their forms for a draw's arguments (again the same values): the hybrid
  * kernels (nodes in LDS, triangles from L2) are 2.8 % FASTER that way on the 6,000-triangle scene and indifferent on the 50,880-triangle one
  * (profiles/r04/experiments/box_muller_on_its_domain.txt) */
-template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false>
+template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false, bool VIEWS = false>
 __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const Frame &f, const Lds &L)
 {
     V3 &o = p.o, &d = p.d;
@@ -338,7 +370,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
         p.frame_steps += (unsigned)(RT_COST_HIT * RT_MAX_BATCH_FRAMES);
     }
     p.mode = M_GEN;
-    if (p.bounce >= f.limit) px_end_sample<BUDGET>(p, a, f);
+    if (p.bounce >= f.limit) px_end_sample<BUDGET, VIEWS>(p, a, f);
 }
 
 /* ================= FETCH: lanes without a pixel take the next ones =========================
@@ -347,7 +379,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
  * by the whole wave.  Every call with a lane in M_FETCH either hands that lane a slot it has not been handed before or, once the tiles
  * are out, ends it (M_DONE): a lane that stays in M_FETCH (a slot outside the image; BUDGET: a pixel of budget 0) has used a slot up, so
  * calling again until no lane is in M_FETCH ends after at most (tiles * 64) slots, whatever the budgets are. */
-template <bool BUDGET = false>
+template <bool BUDGET = false, bool VIEWS = false>
 __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args &a, const Frame &f, int lane)
 {
     const bool want = p.mode == M_FETCH;
@@ -409,7 +441,8 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
     if (my_id < 0) { p.mode = M_DONE; return; }
     const int tile = my_id >> 6, within = my_id & 63;
     int tx, ty, compact_row;
-    tile_place(a, f, tile, tx, ty, compact_row);
+    if (VIEWS) { ty = tile / a.tiles_x; tx = tile - ty * a.tiles_x; compact_row = 0; }    /* whole images only: tile t is the image's tile t */
+    else tile_place(a, f, tile, tx, ty, compact_row);
     const int px = tx * 8 + (within & 7);
     const int py = ty * 8 + (within >> 3);
     p.id = (unsigned)my_id;
@@ -432,6 +465,31 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
         p.sample = n;
         if (f.limit > 0) p.mode = M_GEN;
         else px_finish_pixel<true>(p, a, f);                  /* a zero bounce limit traces nothing: (0,0,0) / n */
+        return;
+    }
+    if (VIEWS) {
+        /* the render branch below with the camera of the pixel's own view (my_frame) from the table, stated twice like the budget branch.
+         * The table is at most 1.5 KB and every lane of the launch reads it: it stays in the L1 / L2. */
+        if (px >= f.W || py >= f.H) return;
+        const float *cam = px_views(a).cams + 12 * my_frame;
+        const int array_index = (py * f.W + px) * 3;
+        p.frame_steps = (unsigned)my_frame;
+        p.rng = (uint32_t)array_index * 3145739u + a.seeds[my_frame];
+        V3 plane_point = v3(cam[6], cam[7], cam[8]) * (float)px + v3(cam[9], cam[10], cam[11]) * (float)py;
+        const V3 cam_pos = v3(cam[0], cam[1], cam[2]);
+        p.primary = normalised((v3(cam[3], cam[4], cam[5]) + plane_point) - cam_pos);
+        p.colour = v3(0.f, 0.f, 0.f);
+        p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
+        p.o = cam_pos; p.d = p.primary;
+        p.bounce = 0; p.cur_n = 1.0f;
+        p.sample = f.limit > 0 ? 0 : f.spp;
+        if (p.sample >= f.spp) {
+            const float q = 0.0f / (float)f.spp;
+            p.colour = v3(q, q, q) * (float)f.spp;
+            px_finish_pixel<false, true>(p, a, f);
+        } else {
+            p.mode = M_GEN;
+        }
         return;
     }
     if (px < f.W && py < f.H) {

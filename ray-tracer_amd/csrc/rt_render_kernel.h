@@ -40,7 +40,9 @@
 template <int NT, bool HAS_MESH, int MODE>
 __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES : RT_SMALL_WG_WAVES + 1)) void rt_render_kernel(const rt_kernel_args a)
 #define RT_LOOP_BUDGET false
+#define RT_LOOP_VIEWS false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
 
 /* The budget variant: per-pixel sample counts (rt_render_budget_device), same shapes and launch bounds.  Its loop is a function taking the
@@ -50,13 +52,33 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 template <int NT, bool HAS_MESH, int MODE>
 __device__ __forceinline__ void rt_budget_loop(const rt_budget_args &a)
 #define RT_LOOP_BUDGET true
+#define RT_LOOP_VIEWS false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
 
 template <int NT, bool HAS_MESH, int MODE>
 __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES : RT_SMALL_WG_WAVES + 1)) void rt_budget_kernel(const rt_budget_args a)
 {
     rt_budget_loop<NT, HAS_MESH, MODE>(a);
+}
+
+/* The views variant: a camera per frame of the launch (rt_render_views_device), same shapes and launch bounds.  The wave loop is the
+ * same; what differs is in rt_pixel.h: px_fetch takes the pixel's camera from rt_views_args::cams by the frame of its chunk, the end of a
+ * sample restarts from that camera's position (read again from the table), and px_finish_pixel only stores the mean into the view's
+ * plane.  A function taking the block by reference, like the budget loop and for its reason (DESIGN.md §17 has the registers per shape). */
+template <int NT, bool HAS_MESH, int MODE>
+__device__ __forceinline__ void rt_views_loop(const rt_views_args &a)
+#define RT_LOOP_BUDGET false
+#define RT_LOOP_VIEWS true
+#include "rt_render_loop.inc"
+#undef RT_LOOP_VIEWS
+#undef RT_LOOP_BUDGET
+
+template <int NT, bool HAS_MESH, int MODE>
+__global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES : RT_SMALL_WG_WAVES + 1)) void rt_views_kernel(const rt_views_args a)
+{
+    rt_views_loop<NT, HAS_MESH, MODE>(a);
 }
 
 /* ---- launchers (called from rt_capi.cpp) -------------------------------------------------- */
@@ -83,17 +105,26 @@ static void rt_launch_budget_one(const rt_budget_args *args, int blocks, size_t 
     hipLaunchKernelGGL((rt_budget_kernel<NT, HAS_MESH, MODE>), dim3(blocks), dim3(NT), lds_bytes, stream, *args);
 }
 
+template <int NT, bool HAS_MESH, int MODE>
+static void rt_launch_views_one(const rt_views_args *args, int blocks, size_t lds_bytes, hipStream_t stream)
+{
+    (void)hipFuncSetAttribute((const void *)rt_views_kernel<NT, HAS_MESH, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL((rt_views_kernel<NT, HAS_MESH, MODE>), dim3(blocks), dim3(NT), lds_bytes, stream, *args);
+}
+
 /* the occupancy probe and the launcher of every built shape, in RT_SHAPES' order: the kernel is instantiated from that list alone */
 struct rt_shape_fns {
     int (*blocks)(size_t lds_bytes);
     void (*launch)(const rt_kernel_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
     void (*launch_budget)(const rt_budget_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
+    void (*launch_views)(const rt_views_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
 };
 template <size_t... I> static constexpr std::array<rt_shape_fns, sizeof...(I)> rt_shape_fns_of(std::index_sequence<I...>)
 {
     return {{{rt_blocks_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
               rt_launch_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
-              rt_launch_budget_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>}...}};
+              rt_launch_budget_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
+              rt_launch_views_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>}...}};
 }
 static constexpr auto rt_shape_table = rt_shape_fns_of(std::make_index_sequence<std::size(RT_SHAPES)>());
 
@@ -123,6 +154,19 @@ extern "C" hipError_t rt_launch_budget(const rt_kernel_args *args, const uint16_
     b.budget = budget;
     b.count = count;
     rt_shape_table[i].launch_budget(&b, blocks, lds_bytes, stream);
+    return hipGetLastError();
+}
+
+/* the views variant on the same shape: cams is the device table of args->num_frames x 12 camera floats; the grid is sized as for the
+ * render kernel */
+extern "C" hipError_t rt_launch_views(const rt_kernel_args *args, const float *cams, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream)
+{
+    const int i = rt_shape_index(shape);
+    if (i < 0) return hipErrorInvalidValue;
+    rt_views_args v;
+    static_cast<rt_kernel_args &>(v) = *args;
+    v.cams = cams;
+    rt_shape_table[i].launch_views(&v, blocks, lds_bytes, stream);
     return hipGetLastError();
 }
 

@@ -1,11 +1,12 @@
 /*
  * rt_render_loop.inc — the body of the render kernel: included by rt_render_kernel.h once per kernel that runs the wave loop, behind the
- * head of what runs it (template <int NT, bool HAS_MESH, int MODE> ... (ARGS a)), with RT_LOOP_BUDGET defined as false (rt_render_kernel)
- * or true (rt_budget_loop).  Text, not a function: called as a function the loop compiles to other code in all thirteen render
+ * head of what runs it (template <int NT, bool HAS_MESH, int MODE> ... (ARGS a)), with RT_LOOP_BUDGET defined as false (rt_render_kernel,
+ * rt_views_loop) or true (rt_budget_loop) and RT_LOOP_VIEWS as true (rt_views_loop: a camera per frame of the launch) or false.  Text, not a function: called as a function the loop compiles to other code in all thirteen render
  * kernels, and the render kernel's code is kept byte for byte.
  */
 {
     constexpr bool BUDGET = RT_LOOP_BUDGET;
+    constexpr bool VIEWS = RT_LOOP_VIEWS;
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
     const int lane = tid & (RT_WAVE - 1);
@@ -66,7 +67,7 @@
          * condition has to take the batch, or the wave comes back with nothing changed.  Both conditions are stated in
          * rt_device_scene.h (RT_ROUND_SHADES, rt_traversal_yields), where tests/sanitize/capi_host_fuzz.cpp (check_progress) takes
          * them from too. */
-        if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss<BUDGET>(p, a, f);
+        if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss<BUDGET, VIEWS>(p, a, f);
         {
             const int n_hit = __popcll(__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_SHADE, RT_ICMP_EQ));
             const bool others = (__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_GEN, RT_ICMP_EQ) |
@@ -75,12 +76,12 @@
             if (RT_ROUND_SHADES(a, HAS_MESH, n_hit, n_trav, others)) {
                 if (p.mode == M_SHADE) {
                     RT_STAT(ST_SHADE);
-                    px_shade<!(NT == 1024 && HAS_MESH), MODE == RT_SCENE_HYBRID, BUDGET>(p, a, f, L);
+                    px_shade<!(NT == 1024 && HAS_MESH), MODE == RT_SCENE_HYBRID, BUDGET, VIEWS>(p, a, f, L);
                 }
             }
         }
         RT_LAP(TM_SHADE);
-        px_fetch<BUDGET>(p, ch, a, f, lane);
+        px_fetch<BUDGET, VIEWS>(p, ch, a, f, lane);
         if (BUDGET) {
             /* Where budgets are sparse most slots hand their lane nothing.  A lane left in M_FETCH asks again at once instead of idling through
              * a round of the others' work: until every lane has a pixel to trace or the tiles are out (then px_fetch ends the lanes left).

@@ -110,41 +110,72 @@ inline bool view_tiles(const rt_tile_spec &t, int width, int height, std::vector
     return true;
 }
 
+/* Does the centre ray of image tile `tile` enter the root box of a mesh, enlarged by a margin?  What the guessed orders below class a
+ * tile by, before anything is measured.  cam: rt_kernel_args::cam (cam_pos, tl_pixel_pos, delta_u, delta_v).  Host float math, a
+ * heuristic only. */
+inline bool centre_ray_enters_mesh(uint32_t tile, int tiles_x, const float cam[12], const std::vector<rt_object> &objects)
+{
+    const int ty = (int)(tile / (uint32_t)tiles_x), tx = (int)(tile % (uint32_t)tiles_x);
+    const float px = tx * 8 + 4.0f, py = ty * 8 + 4.0f;
+    float d[3], o[3];
+    for (int k = 0; k < 3; k++) { o[k] = cam[k]; d[k] = cam[3 + k] + cam[6 + k] * px + cam[9 + k] * py - o[k]; }
+    bool hit = false;
+    for (size_t m = 0; m < objects.size() && !hit; m++) {
+        const rt_object &ob = objects[m];
+        if (ob.type != RT_OBJ_MESH) continue;
+        float tmin = 0.0f, tmax = 3.0e38f;
+        for (int k = 0; k < 3; k++) {
+            /* grow the box by a margin: the tile is 8 pixels wide and paths leave it */
+            const float ext = 0.15f * (ob.v[3 + k] - ob.v[k]) + 1e-3f;
+            const float inv = 1.0f / d[k];
+            float t1 = (ob.v[k] - ext - o[k]) * inv, t2 = (ob.v[3 + k] + ext - o[k]) * inv;
+            if (t1 > t2) { float s = t1; t1 = t2; t2 = s; }
+            if (t1 > tmin) tmin = t1;
+            if (t2 < tmax) tmax = t2;
+        }
+        hit = tmin <= tmax;
+    }
+    return hit;
+}
+
 /* The first guess of a view's order (ticket -> local tile), before anything is measured: tiles whose centre ray enters
  * the root box of a mesh, enlarged by a margin, first, then the others; each class scattered.  cam: rt_kernel_args::cam. */
 inline std::vector<uint32_t> guessed_order(const std::vector<uint32_t> &tiles, int tiles_x, const float cam[12], const std::vector<rt_object> &objects)
 {
-    /* Host float math, a heuristic only */
     const uint32_t n = (uint32_t)tiles.size();
     std::vector<uint32_t> heavy, light;
-    for (uint32_t i = 0; i < n; i++) {
-        const int ty = (int)(tiles[i] / (uint32_t)tiles_x), tx = (int)(tiles[i] % (uint32_t)tiles_x);
-        const float px = tx * 8 + 4.0f, py = ty * 8 + 4.0f;
-        float d[3], o[3];
-        for (int k = 0; k < 3; k++) { o[k] = cam[k]; d[k] = cam[3 + k] + cam[6 + k] * px + cam[9 + k] * py - o[k]; }
-        bool hit = false;
-        for (size_t m = 0; m < objects.size() && !hit; m++) {
-            const rt_object &ob = objects[m];
-            if (ob.type != RT_OBJ_MESH) continue;
-            float tmin = 0.0f, tmax = 3.0e38f;
-            for (int k = 0; k < 3; k++) {
-                /* grow the box by a margin: the tile is 8 pixels wide and paths leave it */
-                const float ext = 0.15f * (ob.v[3 + k] - ob.v[k]) + 1e-3f;
-                const float inv = 1.0f / d[k];
-                float t1 = (ob.v[k] - ext - o[k]) * inv, t2 = (ob.v[3 + k] + ext - o[k]) * inv;
-                if (t1 > t2) { float s = t1; t1 = t2; t2 = s; }
-                if (t1 > tmin) tmin = t1;
-                if (t2 < tmax) tmax = t2;
-            }
-            hit = tmin <= tmax;
-        }
-        (hit ? heavy : light).push_back(i);
-    }
+    for (uint32_t i = 0; i < n; i++) (centre_ray_enters_mesh(tiles[i], tiles_x, cam, objects) ? heavy : light).push_back(i);
     std::vector<uint32_t> order;
     order.reserve(n);
     append_scattered(heavy.data(), (uint32_t)heavy.size(), order);
     append_scattered(light.data(), (uint32_t)light.size(), order);
     return order;
+}
+
+/* The ticket -> (tile | view << RT_JOB_FRAME_SHIFT) table of a views launch (rt_render_views_device): n_views cameras (cams: 12 floats
+ * each, as rt_kernel_args::cam) over the n_tiles tiles of a whole image, tile t being image tile t.  Every view's tiles are classed by that
+ * view's own centre rays, each class scattered.  First the heavy jobs, round-robin over the views, so that every view's long jobs start
+ * at once; then the light ones, view by view.  Every (tile, view) pair appears exactly once.  A guess, like guessed_order: nothing of
+ * these views has been measured. */
+inline void views_job_order(uint32_t n_tiles, int tiles_x, const float *cams, uint32_t n_views, const std::vector<rt_object> &objects, std::vector<uint32_t> &jobs)
+{
+    std::vector<std::vector<uint32_t>> heavy(n_views), light(n_views);
+    std::vector<uint32_t> cls;
+    size_t longest = 0;
+    for (uint32_t v = 0; v < n_views; v++) {
+        std::vector<uint32_t> h, l;
+        for (uint32_t t = 0; t < n_tiles; t++) (centre_ray_enters_mesh(t, tiles_x, cams + 12 * (size_t)v, objects) ? h : l).push_back(t);
+        append_scattered(h.data(), (uint32_t)h.size(), heavy[v]);
+        append_scattered(l.data(), (uint32_t)l.size(), light[v]);
+        longest = std::max(longest, heavy[v].size());
+    }
+    jobs.clear();
+    jobs.reserve((size_t)n_tiles * n_views);
+    for (size_t r = 0; r < longest; r++)
+        for (uint32_t v = 0; v < n_views; v++)
+            if (r < heavy[v].size()) jobs.push_back(heavy[v][r] | (v << RT_JOB_FRAME_SHIFT));
+    for (uint32_t v = 0; v < n_views; v++)
+        for (uint32_t t : light[v]) jobs.push_back(t | (v << RT_JOB_FRAME_SHIFT));
 }
 
 /* The order once the tiles are measured: the HEAVY_TOP mesh tiles (bit 0 of cost[t]: a ray of the tile entered a mesh) of

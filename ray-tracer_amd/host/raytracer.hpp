@@ -15,6 +15,7 @@
 #ifndef RAYTRACER_AMD_HPP
 #define RAYTRACER_AMD_HPP
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -285,7 +286,27 @@ public:
     {
         rt_camera_make(width, height, pos.data(), fov, focal_len, x_rot, y_rot, z_rot, &c);
     }
+    /* one thin-lens sample of this pinhole camera (rt_camera_lens): the image plane at focus_dist, the eye moved by (u, v) on the lens;
+     * focal_len is what the camera was made with (0.1 for the default) */
+    Camera lens(float focal_len, float focus_dist, float u, float v) const
+    {
+        Camera out(*this);
+        if (rt_camera_lens(&c, focal_len, focus_dist, u, v, &out.c) != RT_OK) throw std::invalid_argument("bad lens parameters");
+        return out;
+    }
 };
+
+/* n lens samples of `cam` on a disc of radius `aperture`, by the golden-angle spiral r = aperture * sqrt((i + 0.5) / n),
+ * theta = i * 2.39996323: rendered with Renderer::render_views(..., accumulate = true) they give one depth-of-field frame */
+inline std::vector<Camera> lens_cameras(const Camera &cam, float focal_len, float focus_dist, float aperture, int n)
+{
+    std::vector<Camera> out;
+    for (int i = 0; i < n; i++) {
+        const double r = (double)aperture * std::sqrt(((double)i + 0.5) / (double)n), theta = (double)i * 2.39996323;
+        out.push_back(cam.lens(focal_len, focus_dist, (float)(r * std::cos(theta)), (float)(r * std::sin(theta))));
+    }
+    return out;
+}
 
 /* src/raytracer.cu:4-12 with the defaults of RenderSettings src/main.cu:318-330 */
 struct RenderData {
@@ -347,6 +368,30 @@ public:
         int32_t fn = data->frame_num;
         check(rt_render_frames(ctx_, scene_, &cam.c, &rd.c, t.data(), (int32_t)t.size(), &fn, data->previous_render.data()));
         data->frame_num = fn;
+    }
+    /* Many views of the scene in launches of up to RT_VIEWS_MAX (rt_render_views): view i has the camera cams[i] and the seed times_ms[i].
+     * accumulate false: returns cams.size() frames back to back, each what render() gives for its camera from frame 0.  accumulate true:
+     * `data` must be given; view i is folded into it as progressive frame data->frame_num + i, and the frame is returned as well. */
+    std::vector<float> render_views(const std::vector<Camera> &cams, const RenderData &rd, const std::vector<int> &times_ms, bool accumulate = false,
+                                    VariableRenderData *data = nullptr)
+    {
+        if (cams.empty() || cams.size() != times_ms.size()) throw std::invalid_argument("one time per camera, at least one camera");
+        if (accumulate && !data) throw std::invalid_argument("an accumulated sequence needs the frame it goes into");
+        const size_t frame = (size_t)cams[0].c.width * (size_t)cams[0].c.height * 3;
+        if (accumulate && data->previous_render.size() != frame) throw std::invalid_argument("previous_render has the wrong size");
+        std::vector<rt_camera> c;
+        for (const Camera &cam : cams) c.push_back(cam.c);
+        std::vector<int32_t> t(times_ms.begin(), times_ms.end());
+        if (accumulate) {
+            int32_t fn = data->frame_num;
+            check(rt_render_views(ctx_, scene_, c.data(), t.data(), (int32_t)c.size(), &rd.c, 1, &fn, data->previous_render.data()));
+            data->frame_num = fn;
+            return data->previous_render;
+        }
+        std::vector<float> frames(frame * cams.size());
+        int32_t fn = 0;
+        check(rt_render_views(ctx_, scene_, c.data(), t.data(), (int32_t)c.size(), &rd.c, 0, &fn, frames.data()));
+        return frames;
     }
     float last_kernel_ms()
     {

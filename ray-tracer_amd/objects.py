@@ -289,6 +289,14 @@ class Camera:
     def floats(self):
         return np.array(list(self.c.cam_pos) + list(self.c.tl_pixel_pos) + list(self.c.delta_u) + list(self.c.delta_v), np.float32)
 
+    def lens(self, focal_len, focus_dist, u, v):
+        """One thin-lens sample of this pinhole camera (rt_camera_lens): the image plane at focus_dist, the eye moved by (u, v) on the lens.
+        focal_len is what this camera was made with (0.1 by default)."""
+        out = Camera(self.width, self.height, floats=self.floats())
+        if lib().rt_camera_lens(C.byref(self.c), C.c_float(focal_len), C.c_float(focus_dist), C.c_float(u), C.c_float(v), C.byref(out.c)) != 0:
+            raise ValueError("focal_len and focus_dist must be positive and finite, the offset finite, and the camera's pixel steps not zero")
+        return out
+
 
 class RenderData:
     """reference RenderData src/raytracer.cu:4-12 (defaults of RenderSettings src/main.cu:318-330)"""
