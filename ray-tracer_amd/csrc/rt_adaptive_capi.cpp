@@ -13,10 +13,6 @@
 #include "rt_adaptive.h"
 #include "rt_internal.h"
 
-extern "C" hipError_t rt_launch_budget(const rt_kernel_args *args, const uint16_t *budget, uint32_t *count, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t rt_launch_adaptive_plan(const rt_plan_args *args, hipStream_t stream);
-extern "C" hipError_t rt_launch_adaptive_combine(const float *a, const float *b, const uint32_t *count, float *frame, uint32_t *count_out, long long n_pixels, hipStream_t stream);
-
 namespace {
 
 rt_status check_budget(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const rt_tile_spec *t, const void *budget, const void *frame)
@@ -49,8 +45,7 @@ rt_status check_params(rt_ctx *ctx, const rt_adaptive_params *p)
 rt_status launch_budget(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, int32_t time_ms, const uint32_t *d_list, int n_list,
                         const uint16_t *d_budget, uint32_t *d_count, float *d_frame, hipStream_t stream)
 {
-    rt_tile_spec spec{};
-    spec.band_rows = 8; spec.band_stride = 1;
+    rt_tile_spec spec = rt_sched::whole_image_spec();
     uint32_t placeholder = 0;
     if (d_list) { spec.tile_list = &placeholder; spec.num_tiles = n_list; }       /* (the layout reads the list's presence and length only) */
     const rt_sched::Layout L(spec, cam->width, cam->height);

@@ -4,7 +4,7 @@
  *   plan      one wave per 8x8 tile, one lane per pixel (lane = row in tile * 8 + column): the pixel's error estimate from the two
  *             half buffers, the tile's mean by an xor butterfly over the wave (a fixed pairwise tree), the pixel's next budget.
  *   combine   one lane per pixel: frame = (A + B) * 0.5f (a NaN as the canonical quiet NaN), count = 2 * count.
- * The launchers at the end are called from rt_adaptive_capi.cpp.  No LDS, no atomics.
+ * The launchers at the end are declared in rt_launch.h.  No LDS, no atomics.
  */
 #ifndef RT_ADAPTIVE_KERNEL_H
 #define RT_ADAPTIVE_KERNEL_H
@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "rt_adaptive.h"
+#include "rt_launch.h"
 #include "rt_math.h"
 
 #define RT_PLAN_WAVES 4              /* tiles per workgroup */

@@ -9,8 +9,6 @@
 #include "rt_internal.h"
 #include "rt_ao.h"
 
-extern "C" hipError_t rt_launch_ao(const rt_ao_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
-
 namespace {
 
 rt_status check_ao(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, int32_t samples, float radius, float bias, const void *count, const void *ao)

@@ -3,7 +3,7 @@
  * hit's point P and shading normal N `samples` cosine-weighted directions of the renderer's own sampler on the pixel's own random stream,
  * each an occlusion query (rt_occlusion_kernel.h) of the limit `radius` from o' = P + N * bias; the pixel is the number of free samples
  * and that number over `samples` (include/rt_amd.h has the definition to the bit).  It calls START and the early exits of
- * rt_occlusion_kernel.h; the launcher at the end (rt_ray_kernel.h) is called from rt_ao_capi.cpp.
+ * rt_occlusion_kernel.h; the launcher at the end (rt_ray_kernel.h) is declared in rt_launch.h.
  *
  * A lane is the occlusion kernel's state machine with a pixel held across segments: FETCH (take a tile slot, form the primary ray) ->
  * START -> MESH -> WAIT (the primary segment has a NaN limit: no exit, and its meshes are merged into the closest hit) -> SHADE.  SHADE
@@ -24,6 +24,7 @@
 #include "rt_ao.h"
 #include "rt_device_scene.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
 #include "rt_occlusion_kernel.h"
 #include "rt_ray_kernel.h"
 #include "rt_surface.h"
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(NT, 4) void rt_ao_kernel(const rt_ao_args a)
     }
 }
 
-/* ---- launcher (called from rt_ao_capi.cpp) -------------------------------------------------- */
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
 /* one front: both of rt_ray_launch's tables name the same thirteen kernels */
 struct rt_ao_kernels {
     typedef rt_ao_args args;

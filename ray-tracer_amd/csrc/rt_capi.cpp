@@ -27,15 +27,6 @@
 
 #include "rt_internal.h"
 
-extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
-extern "C" int rt_kernel_blocks_per_cu(rt_shape shape, size_t lds_bytes);
-extern "C" hipError_t rt_launch_blend(const float *partial, long long plane_floats, int num_frames, int frame_num, float *frame, long long n_floats, hipStream_t stream);
-extern "C" hipError_t rt_launch_blend_tiles(const float *partial, long long plane_floats, int num_frames, int frame_num, float *frame,
-                                            const uint32_t *tile_list, int n_tiles, int tiles_x, int W, int H, hipStream_t stream);
-extern "C" hipError_t rt_launch_tiles_copy(float *compact, float *frame, const uint32_t *tile_list, int n_tiles, int tiles_x, int W, int H, int to_frame, hipStream_t stream);
-extern "C" hipError_t rt_launch_eval(int op, const uint32_t *in, uint32_t *out, int n, hipStream_t stream);
-extern "C" hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *out, hipStream_t stream);
-
 std::mutex rt_detail::g_ctx_mutex;
 
 namespace {
@@ -405,10 +396,7 @@ rt_kernel_args rt_detail::kernel_args(const rt_ctx *ctx, const rt_scene *scene, 
 {
     rt_kernel_args a;
     std::memset(&a, 0, sizeof a);
-    std::memcpy(a.cam + 0, cam->cam_pos, 12);
-    std::memcpy(a.cam + 3, cam->tl_pixel_pos, 12);
-    std::memcpy(a.cam + 6, cam->delta_u, 12);
-    std::memcpy(a.cam + 9, cam->delta_v, 12);
+    camera_floats(*cam, a.cam);
     a.width = cam->width;
     a.height = cam->height;
     a.rays_per_pixel = rs->rays_per_pixel;
@@ -457,8 +445,10 @@ rt_kernel_args rt_detail::kernel_args(const rt_ctx *ctx, const rt_scene *scene, 
 
 void rt_detail::push_camera(std::vector<uint32_t> &key, const rt_camera *cam)
 {
-    for (const float *v : {cam->cam_pos, cam->tl_pixel_pos, cam->delta_u, cam->delta_v})
-        for (int i = 0; i < 3; i++) { uint32_t u; std::memcpy(&u, &v[i], 4); key.push_back(u); }
+    float f[12];
+    camera_floats(*cam, f);
+    key.resize(key.size() + 12);
+    std::memcpy(&key[key.size() - 12], f, sizeof f);
 }
 
 static std::vector<uint32_t> view_key(const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, const rt_tile_spec *t, uint32_t n)
@@ -685,8 +675,7 @@ rt_status rt_detail::render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_
                                    const int32_t *times_ms, int32_t n_frames, int32_t frame_num, const rt_tile_spec *tiles,
                                    const float *d_prev, float *d_out, void *hip_stream, bool in_place, FrameSlot *slot)
 {
-    rt_tile_spec full{};
-    full.band_rows = 8; full.band_stride = 1;
+    const rt_tile_spec full = rt_sched::whole_image_spec();
     const rt_tile_spec *t = tiles ? tiles : &full;
     rt_status st = check_launch(ctx, scene, cam, rs, t, d_out || slot);
     if (st != RT_OK) return st;
@@ -804,7 +793,6 @@ extern "C" rt_status rt_debug_eval(rt_ctx *ctx, int32_t op, const uint32_t *in, 
 /* test hook: the short reciprocal and square root of the device code (rt_vec.h rt_rcp_short / rt_sqrt_short) against the
  * compiler's IEEE expansions for every one of the 2^32 binary32 inputs, on the device.  out4 = {reciprocal: inputs inside its
  * range that differ, inputs inside its range; square root: likewise} */
-extern "C" hipError_t rt_launch_exhaustive(unsigned long long *out4, hipStream_t stream);
 extern "C" rt_status rt_debug_exhaustive(rt_ctx *ctx, unsigned long long *out4)
 {
     if (!ctx || !out4) return set_err(ctx, RT_ERR_INVALID, "bad argument");

@@ -1,6 +1,6 @@
 /*
  * rt_debug_kernels.h — the two kernels that exist for tests (rt_debug_eval, rt_debug_exhaustive): the shared math / RNG headers evaluated
- * element-wise on the device, and the short reciprocal and square root against the compiler's over all 2^32 inputs.
+ * element-wise on the device, and the short reciprocal and square root against the compiler's over all 2^32 inputs.  Their launchers are declared in rt_launch.h.
  */
 #ifndef RT_DEBUG_KERNELS_H
 #define RT_DEBUG_KERNELS_H
@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_math.h"
 #include "rt_rng.h"
 #include "rt_vec.h"

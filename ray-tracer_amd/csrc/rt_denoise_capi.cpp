@@ -10,9 +10,6 @@
 #include "rt_denoise.h"
 #include "rt_internal.h"
 
-extern "C" hipError_t rt_launch_denoise_pack(const rt_denoise_args *args, hipStream_t stream);
-extern "C" hipError_t rt_launch_denoise_level(const rt_denoise_args *args, int last, hipStream_t stream);
-
 namespace {
 
 rt_status check_denoise(rt_ctx *ctx, int32_t width, int32_t height, const void *colour, const void *normal, const void *depth, const void *albedo,

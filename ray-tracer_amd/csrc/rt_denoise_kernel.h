@@ -1,7 +1,7 @@
 /*
  * rt_denoise_kernel.h — the edge-avoiding a-trous wavelet filter of rt_denoise (include/rt_amd.h has the definition; the operation
  * order below IS the interface: tests/denoise_ref.py reproduces it bit for bit).  Part of rt_kernel.hip's translation unit (one code object for the
- * library); the launchers at the end are called from rt_denoise_capi.cpp.
+ * library); the launchers at the end are declared in rt_launch.h.
  *
  * Nothing here traverses a scene: the passes are image-space.  This is a first, untuned shape: correct to the bit, measured, not optimised.
  *   pack    one lane per pixel: reads the caller's planes (12-byte pixels), demodulates, writes two 16-byte records per pixel -
@@ -24,6 +24,7 @@
 
 #include "rt_denoise.h"
 #include "rt_device_scene.h"
+#include "rt_launch.h"
 
 #define RT_DN_TILE_X 32
 #define RT_DN_TILE_Y 8

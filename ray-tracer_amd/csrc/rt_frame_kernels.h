@@ -1,6 +1,5 @@
 /*
- * rt_frame_kernels.h — the small streaming kernels over frames and their launchers (called from rt_capi.cpp, rt_pipeline_capi.cpp and
- * rt_multi_capi.cpp): the fold of a multi-frame launch's planes into the frame buffer, whole or for a list of tiles, the tile-list exchange
+ * rt_frame_kernels.h — the small streaming kernels over frames and their launchers (declared in rt_launch.h): the fold of a multi-frame launch's planes into the frame buffer, whole or for a list of tiles, the tile-list exchange
  * copy, and float -> RGBA8.
  */
 #ifndef RT_FRAME_KERNELS_H
@@ -9,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_math.h"
 
 /* The sequential part of a multi-frame launch (src/raytracer.cu:109-112, once per frame): the image

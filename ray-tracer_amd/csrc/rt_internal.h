@@ -1,10 +1,11 @@
 /*
  * rt_internal.h — what the translation units behind the C ABI share: the holders that free HIP handles with their owner (DevBuf, Event,
  * Stream), the context and its parts (rt_ctx: the tile-list cache, the view, the frame pipeline, the multi-GPU rank state, the knobs), the
- * committed scene (rt_scene), the error helpers, the functions of rt_capi.cpp that rt_pipeline_capi.cpp and rt_multi_capi.cpp call, the
- * host-buffer round trip and, at the end, what the entry points beside the renderer (rt_query_capi.cpp, rt_occlusion_capi.cpp,
- * rt_denoise_capi.cpp) have in common: the argument checks, the context's launch bracket and the ray kernels' argument block and launch.
- * rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed: include/rt_amd.h is the interface.
+ * committed scene (rt_scene), the error helpers, the functions of rt_capi.cpp that the other translation units call, the host-buffer round
+ * trip and, at the end, what the entry points beside the renderer (rt_query_capi.cpp, rt_occlusion_capi.cpp, rt_ao_capi.cpp,
+ * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp) have in common: the argument checks, the context's launch bracket and the
+ * ray kernels' argument block and launch.  It includes rt_launch.h, the kernel launchers' declarations: no translation unit declares one
+ * itself.  rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed: include/rt_amd.h is the interface.
  */
 #pragma once
 
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "rt_host.h"
+#include "rt_launch.h"         /* the kernel launchers: the seam to rt_kernel.hip */
 #include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
 #include "rt_schedule.h"
 
@@ -263,7 +265,16 @@ inline rt_status set_err(rt_ctx *ctx, rt_status code, const std::string &msg)
     return code;
 }
 
-/* ---- what rt_pipeline_capi.cpp and rt_multi_capi.cpp call in rt_capi.cpp --------------------------------------------------------- */
+/* a camera as the kernels take it (rt_kernel_args::cam, a row of the views table): cam_pos, tl_pixel_pos, delta_u, delta_v */
+inline void camera_floats(const rt_camera &c, float out[12])
+{
+    std::memcpy(out + 0, c.cam_pos, 12);
+    std::memcpy(out + 3, c.tl_pixel_pos, 12);
+    std::memcpy(out + 6, c.delta_u, 12);
+    std::memcpy(out + 9, c.delta_v, 12);
+}
+
+/* ---- what the other translation units call in rt_capi.cpp ------------------------------------------------------------------------- */
 namespace rt_detail {
 
 /* guards the set of live contexts and every root's rt_ctx::multi.stages: rt_ctx_destroy of a source erases its entry there */
@@ -386,16 +397,13 @@ Args ray_args_view(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *ca
     const int tiles_x = (cam->width + 7) / 8, tiles_y = (cam->height + 7) / 8;
     Args a = ray_args_scene<Args>(ctx, scene, (uint32_t)tiles_x * (uint32_t)tiles_y * 64u);
     a.tiles_x = tiles_x;
-    std::memcpy(a.cam + 0, cam->cam_pos, 12);
-    std::memcpy(a.cam + 3, cam->tl_pixel_pos, 12);
-    std::memcpy(a.cam + 6, cam->delta_u, 12);
-    std::memcpy(a.cam + 9, cam->delta_v, 12);
+    camera_floats(*cam, a.cam);
     a.width = cam->width;
     a.height = cam->height;
     return a;
 }
 
-/* One launch of a ray kernel (`launcher`: rt_launch_query or rt_launch_occlusion, with its `front`) on `stream`, in the launch bracket: the
+/* One launch of a ray kernel (`launcher`: rt_launch_query, rt_launch_occlusion or rt_launch_ao, with its `front`) on `stream`, in the launch bracket: the
  * ticket counter is shared with the render launches. */
 template <class Args>
 rt_status launch_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), bool front,

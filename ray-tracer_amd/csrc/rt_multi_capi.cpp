@@ -13,8 +13,6 @@
 
 #include "rt_internal.h"
 
-extern "C" hipError_t rt_launch_tiles_copy(float *compact, float *frame, const uint32_t *tile_list, int n_tiles, int tiles_x, int W, int H, int to_frame, hipStream_t stream);
-
 /* Longest-processing-time-first ownership (see include/rt_amd.h) */
 extern "C" rt_status rt_partition_tiles(const uint32_t *cost, int32_t tiles_x, int32_t tiles_y, int32_t n_ranks, int32_t *owner)
 {

@@ -9,8 +9,6 @@
 #include "rt_internal.h"
 #include "rt_occlusion.h"
 
-extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *args, rt_shape shape, int vis, int num_cus, size_t lds_bytes, hipStream_t stream);
-
 namespace {
 
 rt_status check_visibility(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float *light_pos, const void *visibility)

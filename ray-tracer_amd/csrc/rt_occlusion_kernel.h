@@ -1,6 +1,6 @@
 /*
  * rt_occlusion_kernel.h — occlusion (any-hit) ray queries and the light-visibility plane of a view: "is anything in the way?", one byte
- * per ray.  The traversal pieces are rt_traverse.h's; the launcher at the end (rt_ray_kernel.h) is called from rt_occlusion_capi.cpp.
+ * per ray.  The traversal pieces are rt_traverse.h's; the launcher at the end (rt_ray_kernel.h) is declared in rt_launch.h.
  *
  * occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_query_kernel answers) finds a hit AND its distance
  * t <= tmax.  The ray is taken as given (direction not normalised, t and tmax in units of its length, Ray::change_direction
@@ -34,6 +34,7 @@
 
 #include "rt_device_scene.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
 #include "rt_occlusion.h"
 #include "rt_ray_kernel.h"
 #include "rt_surface.h"
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(NT, 4) void rt_occlusion_kernel(const rt_occlusion_
     }
 }
 
-/* ---- launcher (called from rt_occlusion_capi.cpp) ------------------------------------------- */
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
 struct rt_occlusion_kernels {
     typedef rt_occlusion_args args;
     template <int NT, bool HAS_MESH, int MODE, bool VIS> static constexpr auto kernel = &rt_occlusion_kernel<NT, HAS_MESH, MODE, VIS>;

@@ -10,8 +10,6 @@
 #include "rt_internal.h"
 #include "rt_query.h"
 
-extern "C" hipError_t rt_launch_query(const rt_query_args *args, rt_shape shape, int aov, int num_cus, size_t lds_bytes, hipStream_t stream);
-
 namespace {
 
 rt_status check_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float *sky, bool any_plane)

@@ -1,7 +1,7 @@
 /*
  * rt_query_kernel.h — closest-hit ray queries and the first-hit AOV pass: one ray per lane through the scene the render kernel
  * stages, stopped at the first hit, with the hit written out instead of shaded.  The traversal pieces are rt_traverse.h's, the hit's surface
- * is rt_surface.h's; the launcher at the end (rt_ray_kernel.h) is called from rt_query_capi.cpp.
+ * is rt_surface.h's; the launcher at the end (rt_ray_kernel.h) is declared in rt_launch.h.
  *
  * What is found is get_ray_collision (src/raytracer.cu:24-46) under the render kernel's rules: the top-level objects in list order
  * with `t <= best_t` (rt_closest_simple, rt_intersect.h), then the meshes merged by "smaller distance, or equal distance and larger list
@@ -27,6 +27,7 @@
 
 #include "rt_device_scene.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
 #include "rt_query.h"
 #include "rt_ray_kernel.h"
 #include "rt_surface.h"
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(NT, 4) void rt_query_kernel(const rt_query_args a)
     }
 }
 
-/* ---- launcher (called from rt_query_capi.cpp) ----------------------------------------------- */
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
 struct rt_query_kernels {
     typedef rt_query_args args;
     template <int NT, bool HAS_MESH, int MODE, bool AOV> static constexpr auto kernel = &rt_query_kernel<NT, HAS_MESH, MODE, AOV>;

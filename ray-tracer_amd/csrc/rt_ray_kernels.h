@@ -20,9 +20,7 @@
 #else
 #include <hip/hip_runtime.h>
 
-#include "rt_ao.h"
-#include "rt_occlusion.h"
-#include "rt_query.h"
+#include "rt_launch.h"
 extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t rt_launch_ao(const rt_ao_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }

@@ -1,6 +1,6 @@
 /*
  * rt_render_kernel.h — the render kernel: the wave loop over the per-pixel sections of rt_pixel.h and the traversal pieces of rt_traverse.h,
- * its instantiations over RT_SHAPES and the launchers (called from rt_capi.cpp).  rt_kernel.hip has the overview.
+ * its instantiations over RT_SHAPES and the launchers (declared in rt_launch.h).  rt_kernel.hip has the overview.
  *
  * The kernel's prologue and its MESH, leaf and merge steps are stated here in place, although rt_traverse.h has them as functions
  * (rt_stage_scene, rt_mesh_enter, rt_leaf_tris, rt_mesh_merge) for the ray kernels: calling those here changes the register allocation or
@@ -19,6 +19,7 @@
 #include "rt_device_scene.h"
 #include "rt_instrument.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
 #include "rt_pixel.h"
 #include "rt_traverse.h"
 #include "rt_vec.h"
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
     rt_views_loop<NT, HAS_MESH, MODE>(a);
 }
 
-/* ---- launchers (called from rt_capi.cpp) -------------------------------------------------- */
+/* ---- launchers (rt_launch.h) -------------------------------------------------------------- */
 template <int NT, bool HAS_MESH, int MODE>
 static int rt_blocks_one(size_t lds_bytes)
 {
@@ -91,25 +92,12 @@ static int rt_blocks_one(size_t lds_bytes)
     return n;
 }
 
-template <int NT, bool HAS_MESH, int MODE>
-static void rt_launch_one(const rt_kernel_args *args, int blocks, size_t lds_bytes, hipStream_t stream)
+/* one launch of KERNEL (rt_render_kernel, rt_budget_kernel or rt_views_kernel of one shape) with its argument block */
+template <int NT, class Args, void (*KERNEL)(Args)>
+static void rt_launch_one(const Args *args, int blocks, size_t lds_bytes, hipStream_t stream)
 {
-    (void)hipFuncSetAttribute((const void *)rt_render_kernel<NT, HAS_MESH, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL((rt_render_kernel<NT, HAS_MESH, MODE>), dim3(blocks), dim3(NT), lds_bytes, stream, *args);
-}
-
-template <int NT, bool HAS_MESH, int MODE>
-static void rt_launch_budget_one(const rt_budget_args *args, int blocks, size_t lds_bytes, hipStream_t stream)
-{
-    (void)hipFuncSetAttribute((const void *)rt_budget_kernel<NT, HAS_MESH, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL((rt_budget_kernel<NT, HAS_MESH, MODE>), dim3(blocks), dim3(NT), lds_bytes, stream, *args);
-}
-
-template <int NT, bool HAS_MESH, int MODE>
-static void rt_launch_views_one(const rt_views_args *args, int blocks, size_t lds_bytes, hipStream_t stream)
-{
-    (void)hipFuncSetAttribute((const void *)rt_views_kernel<NT, HAS_MESH, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    hipLaunchKernelGGL((rt_views_kernel<NT, HAS_MESH, MODE>), dim3(blocks), dim3(NT), lds_bytes, stream, *args);
+    (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(NT), lds_bytes, stream, *args);
 }
 
 /* the occupancy probe and the launcher of every built shape, in RT_SHAPES' order: the kernel is instantiated from that list alone */
@@ -122,9 +110,9 @@ struct rt_shape_fns {
 template <size_t... I> static constexpr std::array<rt_shape_fns, sizeof...(I)> rt_shape_fns_of(std::index_sequence<I...>)
 {
     return {{{rt_blocks_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
-              rt_launch_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
-              rt_launch_budget_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
-              rt_launch_views_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>}...}};
+              rt_launch_one<RT_SHAPES[I].threads, rt_kernel_args, rt_render_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
+              rt_launch_one<RT_SHAPES[I].threads, rt_budget_args, rt_budget_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
+              rt_launch_one<RT_SHAPES[I].threads, rt_views_args, rt_views_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>}...}};
 }
 static constexpr auto rt_shape_table = rt_shape_fns_of(std::make_index_sequence<std::size(RT_SHAPES)>());
 

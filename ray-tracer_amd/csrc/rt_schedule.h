@@ -52,6 +52,15 @@ inline const char *tile_spec_error(const rt_tile_spec &t, int tiles_x, int tiles
     return nullptr;
 }
 
+/* the spec of a launch that renders the whole image in place: every band of 8 rows, nothing listed, not compact */
+inline rt_tile_spec whole_image_spec()
+{
+    rt_tile_spec t{};
+    t.band_rows = 8;
+    t.band_stride = 1;
+    return t;
+}
+
 inline bool tiles_in_image(const uint32_t *list, int32_t n, int tiles_x, int tiles_y)
 {
     for (int32_t i = 0; i < n; i++)

@@ -13,9 +13,6 @@
 #include "rt_internal.h"
 #include "rt_views.h"
 
-extern "C" hipError_t rt_launch_views(const rt_kernel_args *args, const float *cams, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t rt_launch_blend(const float *partial, long long plane_floats, int num_frames, int frame_num, float *frame, long long n_floats, hipStream_t stream);
-
 namespace {
 
 constexpr size_t CAM_WORDS = (size_t)RT_VIEWS_MAX * 12;      /* the camera table's place at the head of ViewsState::d_table */
@@ -33,14 +30,6 @@ rt_status check_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams,
     return RT_OK;
 }
 
-void camera_floats(const rt_camera &c, float out[12])
-{
-    std::memcpy(out + 0, c.cam_pos, 12);
-    std::memcpy(out + 3, c.tl_pixel_pos, 12);
-    std::memcpy(out + 6, c.delta_u, 12);
-    std::memcpy(out + 9, c.delta_v, 12);
-}
-
 }  // namespace
 
 extern "C" rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views,
@@ -50,9 +39,7 @@ extern "C" rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, 
     if (st != RT_OK) return st;
     hipStream_t stream = (hipStream_t)hip_stream;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
-    rt_tile_spec full{};
-    full.band_rows = 8; full.band_stride = 1;
-    const rt_sched::Layout L(full, cams[0].width, cams[0].height);
+    const rt_sched::Layout L(rt_sched::whole_image_spec(), cams[0].width, cams[0].height);
     const size_t plane_floats = L.plane_floats();
     /* one plane of per-pixel means per view: the context's when they are folded into one frame, the caller's frames themselves otherwise */
     if (accumulate) RT_HIP(ctx, ctx->d_partial.grow(plane_floats * (size_t)n_views), "allocating the per-view planes");

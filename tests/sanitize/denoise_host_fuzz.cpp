@@ -13,17 +13,7 @@
 #include "rt_denoise.h"
 #include "rt_internal.h"
 
-static int g_launches = 0;
-extern "C" hipError_t rt_launch_denoise_pack(const rt_denoise_args *, hipStream_t) { g_launches++; return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_denoise_level(const rt_denoise_args *, int, hipStream_t) { g_launches++; return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_render(const rt_kernel_args *, rt_shape, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
-extern "C" int rt_kernel_blocks_per_cu(rt_shape, size_t) { return 1; }
-extern "C" hipError_t rt_launch_blend(const float *, long long, int, int, float *, long long, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_blend_tiles(const float *, long long, int, int, float *, const uint32_t *, int, int, int, int, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_tiles_copy(float *, float *, const uint32_t *, int, int, int, int, int, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_eval(int, const uint32_t *, uint32_t *, int, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_rgba8(const float *, int, uint8_t *, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_exhaustive(unsigned long long *, hipStream_t) { return hipErrorUnknown; }
+#include "launcher_stubs.h"
 
 #define CHECK(cond, what)                                                                          \
     do {                                                                                           \

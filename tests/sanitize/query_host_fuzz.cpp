@@ -11,16 +11,7 @@
 #include "rt_internal.h"
 #include "rt_query.h"
 
-static int g_launches = 0;
-extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_render(const rt_kernel_args *, rt_shape, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
-extern "C" int rt_kernel_blocks_per_cu(rt_shape, size_t) { return 1; }
-extern "C" hipError_t rt_launch_blend(const float *, long long, int, int, float *, long long, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_blend_tiles(const float *, long long, int, int, float *, const uint32_t *, int, int, int, int, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_tiles_copy(float *, float *, const uint32_t *, int, int, int, int, int, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_eval(int, const uint32_t *, uint32_t *, int, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_rgba8(const float *, int, uint8_t *, hipStream_t) { return hipErrorUnknown; }
-extern "C" hipError_t rt_launch_exhaustive(unsigned long long *, hipStream_t) { return hipErrorUnknown; }
+#include "launcher_stubs.h"
 
 #define CHECK(cond, what)                                                                        \
     do {                                                                                         \
