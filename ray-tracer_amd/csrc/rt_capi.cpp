@@ -158,6 +158,7 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     ctx->total_mem = prop.totalGlobalMem;
     Knobs &k = ctx->knobs;
     for (const rt_sched::KnobRange &r : rt_sched::KNOB_RANGES) k.*r.field = env_int(r.env, r.lo, r.hi, k.*r.field);
+    k.descend_keep_given = env_int("RT_AMD_DESCEND_KEEP", 0, 64, -1) >= 0;      /* (an explicit value replaces the per-shape default: rt_sched::render_descend_keep) */
     ctx->multi.careful = env_int("RT_AMD_MULTI_CAREFUL", INT_MIN, INT_MAX, 0) != 0;
     if (ctx->tile_counter.grow(256) != hipSuccess ||
         hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
@@ -433,7 +434,7 @@ rt_kernel_args rt_detail::kernel_args(const rt_ctx *ctx, const rt_scene *scene, 
     a.hit_low = k.hit_low;
     a.mix_break = k.mix_break;
     a.shade_batch = k.shade_batch;
-    a.descend_keep = k.descend_keep;
+    a.descend_keep = rt_sched::render_descend_keep(ctx->knobs, scene->kernel.shape);
     a.tri_uv = scene->d_tri_uv.p;
     a.tex_data = scene->d_tex.p;
     a.prev = d_prev;

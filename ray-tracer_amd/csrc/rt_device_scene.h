@@ -56,6 +56,14 @@ inline constexpr int rt_shape_index(rt_shape s)
         if (RT_SHAPES[i] == s) return i;
     return -1;
 }
+/* Which shapes of the render kernels (render, budget, views) walk with rt_descend_pop (rt_traverse.h) instead of rt_descend: the 1024-thread ones,
+ * in every scene mode.  Measured per scene against the loop before (profiles/r12/): monkey and reference scene 0 (1024 threads, scene in LDS), the
+ * 6,000-triangle soup and the 50,880-triangle surface (1024 threads, triangles from global memory) gain 5 to 8 %; the cube's 256-thread workgroups
+ * lose 2 to 4 % at every descend_keep tried and keep rt_descend, and with them the other shapes below 1024 threads, which no scene measured runs on. */
+constexpr bool rt_descend_pops(int threads, int /* mode */) { return threads == 1024; }
+static_assert(rt_descend_pops(1024, RT_SCENE_LDS) && rt_descend_pops(1024, RT_SCENE_HYBRID) && rt_descend_pops(1024, RT_SCENE_GLOBAL) &&
+              !rt_descend_pops(768, RT_SCENE_LDS) && !rt_descend_pops(512, RT_SCENE_HYBRID) && !rt_descend_pops(256, RT_SCENE_LDS),
+              "tests/test_gpu_descend_pop.py runs its scenes on 1024 threads to reach rt_descend_pop, and the cube's 256-thread shape keeps rt_descend");
 #define RT_STACK_ENTRIES RT_BVH_DEPTH /* at most one pending sibling per level below the root */
 #define RT_FRAME_BITS 5               /* a pixel keeps the index of its frame within the launch in this many bits */
 #define RT_MAX_BATCH_FRAMES (1 << RT_FRAME_BITS)   /* frames one launch can render */
@@ -74,6 +82,11 @@ inline constexpr int rt_shape_index(rt_shape s)
                                          scenes 0 / 1 / 3 within 0.3 % (the cube would lose 0.5 % with it) */
 #define RT_DEF_DESCEND_KEEP 20       /* the descend loop ends once fewer than this many 64ths of its lanes remain (24 until the end of round 4; with hit_break 32: monkey -0.5 %, reference scene 0 -8.0 %,
                                          50,880-triangle surface -1.3 %, cube -0.6 % against the defaults before) */
+#define RT_DEF_DESCEND_KEEP_POP_LDS 32 /* ... and the render kernels that pop inside the descend loop (rt_descend_pops above), scene in LDS: the loop's lanes stay through their dead ends
+                                         while the lanes that found a leaf wait, so the best fraction is higher (monkey -2.6 % against 20, reference scene 0 -1.9 %; 28 and 36 within 0.3 % of
+                                         32).  With the triangles in global memory the leaf pass is the expensive one, fuller leaf passes pay more, and 20 stays (at 32 the 6,000-triangle
+                                         soup and the 50,880-triangle surface give back 5 to 7 %): profiles/r12/forms_and_descend_keep.txt.  Defaults only: RT_AMD_DESCEND_KEEP is handed to
+                                         every kernel as given (rt_sched::render_descend_keep) */
 #define RT_DEF_SHADE_BATCH 40        /* scenes without a mesh: hits are shaded once this many lanes hold one */
 /* What a pixel is charged for (the tile costs a view's first launch collects: longest-job-first schedule, cost-balanced
  * tile ownership over GPUs): per traversal macro step, per generated bounce ray, per shaded hit.  The ratios are what was
@@ -83,7 +96,10 @@ inline constexpr int rt_shape_index(rt_shape s)
  * lives in bits 30..RT_FRAME_BITS of its frame word, 2^26 units, and at one unit per macro step that is more than any
  * pixel the host lets collect costs can reach (rt_capi.cpp: launches of rays_per_pixel * reflection_limit >= 2^16 run on
  * the previous or the guessed schedule).  Only frame 0 of a launch is charged to its tile, capped at RT_COST_PIXEL_CAP, so
- * that a tile's 32-bit sum of 64 pixels (<< 1, bit 0 = "a ray entered a mesh") cannot wrap either. */
+ * that a tile's 32-bit sum of 64 pixels (<< 1, bit 0 = "a ray entered a mesh") cannot wrap either.
+ * A macro step is one pass of a lane through the descend loop, the leaf section and the pop.  Where the descend loop pops behind a dead end
+ * (rt_descend_pop, rt_traverse.h) that pass covers the dead ends behind it too - a lane is charged RT_COST_STEP once per leaf it reaches, not once
+ * per stack entry - and nothing is charged inside the loop.  The weights were not fitted again: any weighting of this shape predicted as well. */
 #ifndef RT_COST_STEP
 #define RT_COST_STEP 1
 #endif

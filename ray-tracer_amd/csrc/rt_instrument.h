@@ -32,7 +32,9 @@ enum { TM_CTL = 0, TM_SHADE = 1, TM_FETCH = 2, TM_GEN = 3, TM_MESH = 4, TM_DESCE
 #define RT_LAP_SPLIT(slot)
 #define RT_LAP_SPLIT_LEAF(slot)
 #endif
-enum { ST_ITER = 0, ST_SHADE = 1, ST_SHADE_HIT = 2, ST_FETCH = 3, ST_GEN = 4, ST_MESH = 5, ST_MESH_START = 6, ST_WORK_ITER = 7, ST_NODE = 8, ST_LEAF_TRI = 9, ST_POP = 10, ST_DONE_MESH = 11, ST_N = 12 };
+enum { ST_ITER = 0, ST_SHADE = 1, ST_SHADE_HIT = 2, ST_FETCH = 3, ST_GEN = 4, ST_MESH = 5, ST_MESH_START = 6, ST_WORK_ITER = 7, ST_NODE = 8, ST_LEAF_TRI = 9, ST_POP = 10, ST_DONE_MESH = 11,
+       ST_POP_LOOP = 12 /* pops inside rt_descend_pop (rt_traverse.h); ST_POP counts the post-leaf ones */, ST_N = 13 };
+#define RT_STATS_TIME_BASE (2 * ST_N)   /* the counters' (wave executions, lanes) pairs come first, then TM_N lap times, the summed wave lifetimes and the wave count: tools/stats_run.py reads them by position */
 
 /* -DRT_COSTMAP (tools/costmap.py): the frame holds per-pixel step counts and clock ticks instead of colours (Px, rt_pixel.h) */
 #ifdef RT_COSTMAP
@@ -60,9 +62,9 @@ enum { ST_ITER = 0, ST_SHADE = 1, ST_SHADE_HIT = 2, ST_FETCH = 3, ST_GEN = 4, ST
     }                                                                                                         \
     RT_LAP(TM_CTL);                                                                                           \
     if (lane == 0) {                                                                                          \
-        for (int i = 0; i < TM_N; i++) atomicAdd(&a.stats[24 + i], st_time[i]);                               \
-        atomicAdd(&a.stats[24 + TM_N], wall_clock64() - st_wall0);      /* summed wave lifetimes, 100 MHz ticks */ \
-        atomicAdd(&a.stats[24 + TM_N + 1], 1ull);                        /* waves */                          \
+        for (int i = 0; i < TM_N; i++) atomicAdd(&a.stats[RT_STATS_TIME_BASE + i], st_time[i]);                               \
+        atomicAdd(&a.stats[RT_STATS_TIME_BASE + TM_N], wall_clock64() - st_wall0);      /* summed wave lifetimes, 100 MHz ticks */ \
+        atomicAdd(&a.stats[RT_STATS_TIME_BASE + TM_N + 1], 1ull);                        /* waves */                          \
     }                                                                                                         \
 } while (0)
 #else

@@ -105,6 +105,7 @@ __device__ __forceinline__ bool tri_test(const v4f *tris, int idx, V3 o, V3 d, f
 /* The same test for the traversal's leaf loop, with the outcome as a lane mask (compares written straight to SGPR pairs and
  * combined there): which lanes' rays hit AND are closer than `best`.  (__ballot of a bool built from several compares costs a
  * v_cndmask and a v_cmp to rebuild the mask.) */
+#define RT_FCMP_OEQ 1
 #define RT_FCMP_OGT 2
 #define RT_FCMP_OGE 3
 #define RT_FCMP_OLT 4

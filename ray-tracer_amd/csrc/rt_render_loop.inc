@@ -154,9 +154,16 @@
                      * traversal state is `cur` (+ the stack): an internal node to descend from,
                      * or a leaf whose triangles are tested and after which the stack is popped;
                      * "no child entered" is the empty leaf. */
-                    if (!(cur & RT_REF_LEAF)) {
-                        /* two copies of the loop: the six-med3 slab test where no traversing ray of the wave has a direction
-                         * component of exactly zero (always, in practice), the reference's min / max form otherwise */
+                    /* two copies of the loop: the six-med3 slab test where no traversing ray of the wave has a direction
+                     * component of exactly zero (always, in practice), the reference's min / max form otherwise */
+                    if (rt_descend_pops(NT, MODE)) {
+                        /* the loop pops behind a dead end and goes on (rt_descend_pop, rt_traverse.h): what it hands the leaf section
+                         * is a leaf with triangles, a finished mesh, or what the descend_keep rule sent out early */
+                        if (rt_descend_pop_enters(cur, sp)) {
+                            if (__builtin_amdgcn_uicmp(w_zero_dir, 0u, RT_ICMP_NE) == 0ull) rt_descend_pop<NT, true>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
+                            else rt_descend_pop<NT, false>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
+                        }
+                    } else if (!(cur & RT_REF_LEAF)) {
                         if (__builtin_amdgcn_uicmp(w_zero_dir, 0u, RT_ICMP_NE) == 0ull) rt_descend<NT, true>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
                         else rt_descend<NT, false>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
                     }

@@ -309,6 +309,7 @@ inline rt_status choose_shape(bool has_mesh, size_t blob_bytes, size_t prefix_by
 struct Knobs {
     int work_threshold = RT_DEF_WORK_THRESHOLD;      /* lanes; RT_AMD_WORK_THRESHOLD */
     int descend_keep = RT_DEF_DESCEND_KEEP;       /* RT_AMD_DESCEND_KEEP (0..64): 0 = run every descent to its end */
+    bool descend_keep_given = false;              /* RT_AMD_DESCEND_KEEP was set to an accepted value: every kernel gets it as it is (render_descend_keep) */
     int ready_break = RT_DEF_READY_BREAK;        /* lanes; RT_AMD_READY_BREAK; 65 = never */
     int hit_break = RT_DEF_HIT_BREAK;          /* lanes; RT_AMD_HIT_BREAK */
     /* RT_AMD_HIT_LOW, RT_AMD_MIX_BREAK (0 = that rule off; -1 = not set: the default of the scene's workgroup shape).  The kernel gets
@@ -354,6 +355,15 @@ inline KernelKnobs kernel_knobs(const Knobs &k, int threads)
     a.mix_break = mix ? mix_break : 1000;
     a.shade_batch = k.shade_batch;
     return a;
+}
+
+/* The descend_keep a render, budget or views launch of `shape` runs with: RT_AMD_DESCEND_KEEP as given, whatever the shape (63 means 63/64);
+ * without it the default of the shape's descend loop - RT_DEF_DESCEND_KEEP_POP_LDS where the loop pops inside (rt_descend_pops) and the scene is
+ * in LDS, RT_DEF_DESCEND_KEEP (k.descend_keep) everywhere else.  The ray kernels take k.descend_keep: their loop is rt_descend. */
+inline int render_descend_keep(const Knobs &k, const rt_shape &shape)
+{
+    if (k.descend_keep_given) return k.descend_keep;
+    return shape.has_mesh && shape.mode == RT_SCENE_LDS && rt_descend_pops(shape.threads, shape.mode) ? RT_DEF_DESCEND_KEEP_POP_LDS : k.descend_keep;
 }
 
 /* rt_partition_tiles' owner table dealt out per rank: its tiles (ascending image indices) and, with cost and peak

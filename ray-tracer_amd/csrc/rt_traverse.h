@@ -21,6 +21,7 @@ enum { M_FETCH = 0, M_GEN = 1, M_MESH = 2, M_WAIT = 3, M_SHADE = 4, M_DONE = 5, 
 /* LLVM integer-compare predicates for __builtin_amdgcn_uicmp / sicmp (lane mask of a compare, straight into an SGPR pair) */
 #define RT_ICMP_EQ 32
 #define RT_ICMP_NE 33
+#define RT_ICMP_SGT 38
 #define RT_ICMP_SGE 39
 
 /* The descend loop of a traversal macro step: from an internal node down to a leaf (or to "no child entered").
@@ -65,6 +66,97 @@ __device__ __forceinline__ void rt_descend(uint32_t &cur, int &sp, uint2 *my_sta
              * to the compiler as the loop's exit condition (inverse ballot: no instruction).  The compiler's own rendering of
              * "leaf || count < n_keep" took 16 scalar instructions and 3 branches per node step (round 3), then, with the count
              * passed through a VGPR, 9 + 3 vector ones (-2 %, profiles/r04/experiments/keep_rule_single_exit.txt). */
+            unsigned long long stop, internal;
+            int cnt;
+            asm volatile("v_cmp_gt_i32_e64 %0, 0, %3\n\t"
+                         "s_andn2_b64 %1, exec, %0\n\t"
+                         "s_bcnt1_i32_b64 %2, %1\n\t"
+                         "s_cmp_lt_u32 %2, %4\n\t"
+                         "s_cselect_b64 %0, exec, %0"
+                         : "=&s"(stop), "=&s"(internal), "=&s"(cnt) : "v"(cur), "s"(n_keep) : "scc");
+            if (__builtin_amdgcn_inverse_ballot_w64(stop)) break;
+        }
+    }
+}
+
+/* Pops one entry (sp > 0): it is taken iff !(dist > best) (src/objects.cu:501); through a collapsed chain iff dist < best (:517) - the distance is
+ * never NaN, so that is dist < best, or dist == best on a plain edge.  A refused entry leaves the lane on the empty leaf: it pops again next step. */
+template <int NT>
+__device__ __forceinline__ uint32_t rt_pop(int &sp, const uint2 *my_stack, float w_best)
+{
+    sp--;
+    const uint2 e = my_stack[sp * NT];
+    const float dd = __uint_as_float(e.x);
+    const bool take = dd < w_best || (dd == w_best && !(e.y & RT_REF_CHAIN));
+    return take ? e.y : RT_REF_EMPTY_LEAF;
+}
+
+/* A lane of a macro step goes through rt_descend_pop (rather than straight to the leaf section): it is on an internal node, or on the empty
+ * leaf with entries left on its stack (the post-leaf pop refused one) */
+__device__ __forceinline__ bool rt_descend_pop_enters(uint32_t cur, int sp)
+{
+    return !(cur & RT_REF_LEAF) || (cur == RT_REF_EMPTY_LEAF && sp > 0);
+}
+
+/* rt_descend with the pop of a dead end inside the loop (the render kernels' form; while-while traversal).  A lane whose node entered no child
+ * does not leave for the (empty) leaf section and the pop behind it: it pops its next deferred sibling here, with rt_pop's rule, and goes
+ * on descending from a taken internal node in the following iterations.  A lane leaves once it is on a leaf: one with triangles, the empty
+ * leaf with sp == 0 (the mesh is finished), or the empty leaf after a refused entry - that lane pops again in the leaf section and at the
+ * head of its next call, as it does after rt_descend (rare: keeping it in the loop costs every iteration a select and a compare for
+ * it, profiles/r12/experiments/).  The `descend_keep` rule and the single divergent exit are rt_descend's, on the lanes on an internal node;
+ * which shapes run this loop, and the fraction they run it with by default, is rt_descend_pops / RT_DEF_DESCEND_KEEP_POP_LDS (rt_device_scene.h).
+ * The body stays branch-free: the top of the stack is read with the node, every iteration, and the pop is selects on it.
+ * Nothing a frame is made of changes: w_best does not change in here and no triangle is tested, so every take / refuse decision, every
+ * box test, the push order and the visit order of a lane are those of rt_descend + rt_pop one macro step at a time - the frames are bit-identical. */
+template <int NT, bool MED3>
+__device__ __forceinline__ void rt_descend_pop(uint32_t &cur, int &sp, uint2 *my_stack, const Lds &L, V3 o, V3 inv, float w_best, int descend_keep RT_STAT_PARAMS)
+{
+    /* a lane that comes in on the empty leaf (the post-leaf pop refused its entry): pops until an entry is taken or the stack is empty (rare) */
+    while (cur == RT_REF_EMPTY_LEAF && sp > 0) {
+        RT_STAT(ST_POP_LOOP);
+        cur = rt_pop<NT>(sp, my_stack, w_best);
+    }
+    if (cur & RT_REF_LEAF) return;
+    const int n_enter = __popcll(__ballot(1));
+    const int n_keep = (n_enter * descend_keep) >> 6;
+    for (;;) {
+        RT_STAT(ST_NODE);
+        RT_COST(c_steps++);
+        /* the top of the stack, asked for together with the node: a dead end below pops it without a second LDS round trip (nothing is
+         * pushed in an iteration that enters no child, so it still is the top then; with sp == 0 slot 0 is read and not used) */
+        const int top_slot = sp - (sp > 0 ? 1 : 0);
+        const uint2 top = my_stack[top_slot * NT];
+        const v4f *n = L.nodes + 4 * (int)(cur & RT_REF_NODE_MASK);
+        const v4f q0 = n[0], q1 = n[1], q2 = n[2];
+        const uint2 refs = *(const uint2 *)(n + 3);          /* the two child references: 8 of the last 16 bytes */
+        float ld, rdist;
+        const bool l_push = MED3 ? box_enter_med3(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, w_best, ld)
+                                 : box_enter(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, w_best, ld);
+        const bool r_push = MED3 ? box_enter_med3(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, w_best, rdist)
+                                 : box_enter(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, w_best, rdist);
+        const uint32_t lref = refs.x, rref = refs.y;
+        const bool l_first = ld < rdist;
+        /* (rt_descend's step: the deferred sibling always stored above the top, sp moves when both children are entered) */
+        const bool both = l_push && r_push;
+        const bool entered = l_push || r_push;
+        const unsigned long long l_first_lanes = __builtin_amdgcn_fcmpf(ld, rdist, RT_FCMP_OLT);
+        const uint32_t deferred_ref = rt_sel_u32(l_first_lanes, lref, rref);
+        const float deferred_d = rt_sel_f32(l_first_lanes, ld, rdist);
+        my_stack[sp * NT] = make_uint2(__float_as_uint(deferred_d), deferred_ref);
+        const uint32_t next = both ? (l_first ? rref : lref) : (l_push ? lref : rref);
+        /* a dead end with entries left pops the top by rt_pop's rule: taken, the lane goes on from it; refused, the lane is on the empty leaf */
+        const float dd = __uint_as_float(top.x);
+        const unsigned long long take = __builtin_amdgcn_sicmp(sp, 0, RT_ICMP_SGT) &
+            (__builtin_amdgcn_fcmpf(dd, w_best, RT_FCMP_OLT) | (__builtin_amdgcn_fcmpf(dd, w_best, RT_FCMP_OEQ) & __builtin_amdgcn_uicmp(top.y & RT_REF_CHAIN, 0u, RT_ICMP_EQ)));
+        if (!entered && sp > 0) RT_STAT(ST_POP_LOOP);      /* (development builds only) */
+        /* what a lane that entered no child goes on with: the popped entry if it has one and takes it, else the empty leaf (finished with
+         * sp == 0, refused otherwise); lane masks and selects, so that the body stays one block */
+        const uint32_t popped = rt_sel_u32(take, top.y, RT_REF_EMPTY_LEAF);
+        cur = entered ? next : popped;
+        sp = entered ? sp + (both ? 1 : 0) : top_slot;
+        {
+            /* rt_descend's single divergent exit, same five instructions: the lanes on a leaf leave, or everybody once fewer than n_keep are on
+             * an internal node */
             unsigned long long stop, internal;
             int cnt;
             asm volatile("v_cmp_gt_i32_e64 %0, 0, %3\n\t"
@@ -138,18 +230,6 @@ __device__ __forceinline__ void rt_leaf_tris(uint32_t cur, const Lds &L, V3 o, V
         w_best = rt_sel_f32(closer, t, w_best);
         w_prim = (int)rt_sel_u32(closer, (uint32_t)(start + k), (uint32_t)w_prim);
     }
-}
-
-/* Pops one entry (sp > 0): it is taken iff !(dist > best) (src/objects.cu:501); through a collapsed chain iff dist < best (:517) - the distance is
- * never NaN, so that is dist < best, or dist == best on a plain edge.  A refused entry leaves the lane on the empty leaf: it pops again next step. */
-template <int NT>
-__device__ __forceinline__ uint32_t rt_pop(int &sp, const uint2 *my_stack, float w_best)
-{
-    sp--;
-    const uint2 e = my_stack[sp * NT];
-    const float dd = __uint_as_float(e.x);
-    const bool take = dd < w_best || (dd == w_best && !(e.y & RT_REF_CHAIN));
-    return take ? e.y : RT_REF_EMPTY_LEAF;
 }
 
 /* A mesh is done: its closest triangle against the closest hit so far - smaller distance, or equal and later in the object list (the mesh's place in

@@ -17,8 +17,8 @@ for _ in range(2):
     ms = ctx.last_kernel_ms()
 buf = (C.c_uint64 * 48)()
 rt.lib().rt_debug_read_stats(ctx._h, buf)
-names = ["ITER", "SHADE", "SHADE_HIT", "FETCH", "GEN", "MESH", "MESH_START", "WORK_ITER", "NODE", "LEAF_TRI", "POP", "DONE_MESH"]
-cost = {"ITER": 20, "SHADE": 30, "SHADE_HIT": 700, "GEN": 300, "MESH": 40, "WORK_ITER": 15, "NODE": 84, "LEAF_TRI": 95, "POP": 12}
+names = ["ITER", "SHADE", "SHADE_HIT", "FETCH", "GEN", "MESH", "MESH_START", "WORK_ITER", "NODE", "LEAF_TRI", "POP", "DONE_MESH", "POP_LOOP"]
+cost = {"ITER": 20, "SHADE": 30, "SHADE_HIT": 700, "GEN": 300, "MESH": 40, "WORK_ITER": 15, "NODE": 84, "LEAF_TRI": 95, "POP": 12, "POP_LOOP": 8}
 samples = W * H * spp
 print("monkey close-up %dx%d spp=%d: %.2f ms, %.1f Msamples/s, frame mean %.4f" % (W, H, spp, ms, samples / ms / 1e3, out.mean().item()))
 tot = sum(buf[2 * i] * 64 * cost.get(n, 0) for i, n in enumerate(names))

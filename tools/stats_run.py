@@ -21,8 +21,8 @@ else:
 ms = ctx.last_kernel_ms()
 buf = (C.c_uint64 * 48)()
 rt.lib().rt_debug_read_stats(ctx._h, buf)
-names = ["ITER", "SHADE", "SHADE_HIT", "FETCH", "GEN", "MESH", "MESH_START", "WORK_ITER", "NODE", "LEAF_TRI", "POP", "DONE_MESH"]
-cost = {"ITER": 20, "SHADE": 30, "SHADE_HIT": 700, "GEN": 300, "MESH": 40, "WORK_ITER": 15, "NODE": 75, "LEAF_TRI": 95, "POP": 12}
+names = ["ITER", "SHADE", "SHADE_HIT", "FETCH", "GEN", "MESH", "MESH_START", "WORK_ITER", "NODE", "LEAF_TRI", "POP", "DONE_MESH", "POP_LOOP"]
+cost = {"ITER": 20, "SHADE": 30, "SHADE_HIT": 700, "GEN": 300, "MESH": 40, "WORK_ITER": 15, "NODE": 75, "LEAF_TRI": 95, "POP": 12, "POP_LOOP": 8}
 print("%s %dx%d spp=%d x %d frame(s): %.2f ms, %.1f Msamples/s  (info %s)" % (name, W, H, spp, frames, ms, W * H * spp * frames / ms / 1e3, scene.info()))
 samples = W * H * spp * frames
 tot_slots = tot_useful = 0
@@ -40,7 +40,8 @@ for i, n in enumerate(names):
         print("    %-10s share of issued slots %5.1f%%  (util %.2f)" % (n, 100.0 * ex * 64 * c / tot_slots, buf[2 * i + 1] / ex / 64))
 
 tn = ["CTL", "SHADE", "FETCH", "GEN", "MESH", "DESCEND", "LEAF", "POP"]
-t = [buf[24 + i] for i in range(8)]
+TB = 2 * len(names)      # RT_STATS_TIME_BASE (rt_instrument.h): the lap times follow the counter pairs
+t = [buf[TB + i] for i in range(8)]
 if sum(t):
     print("  wave time by section: " + "  ".join("%s %.1f%%" % (n, 100.0 * v / sum(t)) for n, v in zip(tn, t)))
-    print("  waves %d, mean wave lifetime %.1f ms" % (buf[33], buf[32] / max(buf[33], 1) * 1e-5))
+    print("  waves %d, mean wave lifetime %.1f ms" % (buf[TB + 9], buf[TB + 8] / max(buf[TB + 9], 1) * 1e-5))

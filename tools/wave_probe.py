@@ -23,14 +23,15 @@ for _ in range(2):
 ms = ctx.last_kernel_ms()
 buf = (C.c_uint64 * 48)()
 rt.lib().rt_debug_read_stats(ctx._h, buf)
-names = ["ITER", "SHADE", "SHADE_HIT", "FETCH", "GEN", "MESH", "MESH_START", "WORK_ITER", "NODE", "LEAF_TRI", "POP", "DONE_MESH"]
+names = ["ITER", "SHADE", "SHADE_HIT", "FETCH", "GEN", "MESH", "MESH_START", "WORK_ITER", "NODE", "LEAF_TRI", "POP", "DONE_MESH", "POP_LOOP"]
 print("window tiles (%d,%d)+%dx%d spp=%d: kernel %.2f ms" % (tx, ty, tw, th, spp, ms))
 for i, n in enumerate(names):
     if buf[2 * i]:
         print("  %-10s wave-execs %10d  lanes/exec %5.1f" % (n, buf[2 * i], buf[2 * i + 1] / buf[2 * i]))
 tn = ["CTL", "SHADE", "FETCH", "GEN", "MESH", "DESCEND", "LEAF", "POP"]
-t = [buf[24 + i] for i in range(8)]
-waves, life = buf[33], buf[32]
+TB = 2 * len(names)      # RT_STATS_TIME_BASE (rt_instrument.h)
+t = [buf[TB + i] for i in range(8)]
+waves, life = buf[TB + 9], buf[TB + 8]
 tot = float(sum(t))
 if tot == 0:
     sys.exit(0)          # not a -DRT_STATS build: only the kernel time is meaningful
