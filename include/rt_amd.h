@@ -166,6 +166,29 @@ typedef struct rt_scene_info {
 } rt_scene_info;
 rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *out);
 
+/* ---- time-varying geometry: a committed mesh rebuilt from new vertices, on the device -------------------------------------------------
+ * A committed scene renders many frames, views and queries; these two calls give it the next time step.  The mesh keeps its triangle count, and
+ * with it everything the reference's builder derives from the count alone (node indices, child references, leaf ranges, the chain edges,
+ * the per-lane stack depth, every offset of the device layout, the LDS placement and the kernel shape: DESIGN.md section 21); the triangles' order
+ * in the leaves and every box are rebuilt by kernels, exactly as the host builder would make them: */
+/* object_index names an RT_OBJ_MESH of n triangles (its count at commit); triangle i of the mesh (commit input order: row i of rt_scene_add_mesh's array,
+ * or of rt_obj_get_triangles for an .obj mesh) becomes the three points d_triangles[9 i .. 9 i + 9). */
+rt_status rt_scene_update_mesh_device(rt_ctx *ctx, rt_scene *scene, int32_t object_index, const float *d_triangles, int32_t n, void *hip_stream);
+rt_status rt_scene_update_mesh(rt_ctx *ctx, rt_scene *scene, int32_t object_index, const float *triangles, int32_t n);   /* host memory; returns when done */
+/* Result: everything the kernels read of the scene is then, as bytes, what rt_scene_commit uploads for a builder that differs only in this
+ * mesh's triangles - its triangle records and their order, its node boxes, its entry of the mesh table, its object record (both copies), the
+ * box in its shading record, its rows of the texture coordinates (a triangle keeps the coordinates it had at commit) - and nothing else is
+ * written: every entry point's output on the updated scene is its output on a scene committed with the new triangles.
+ * Inputs: finite coordinates of magnitude at most 2^28; the host form refuses others (RT_ERR_INVALID), the device form cannot look: with other
+ * inputs the scene's content is unspecified, but the call stays memory-safe.  A zero-area triangle's normal is a NaN, as at commit.
+ * Order: the device form is asynchronous on hip_stream (d_triangles is read there) and takes its place in the context's launch order like
+ * rt_render_device: a launch issued before it reads the old mesh, a launch issued after it the new one, on whatever streams; it is queued
+ * behind the frames in flight.  The context owns the scratch.  The scene's cached view (tile order and costs) is dropped.
+ * RT_ERR_INVALID, with the scene and the launch order untouched: a null pointer, a scene of another context, an index that is out of range
+ * or names no mesh, n different from the mesh's count.  n == 0 for an empty mesh succeeds and does nothing.  A mesh whose triangle count
+ * changes is rt_scene_commit's. */
+#define RT_REBUILD_LDS_TRIS 2048   /* the most triangles of a tree level's segment that one workgroup rebuilds in LDS (sized in rt_rebuild.h): a mesh up to this size is one launch */
+
 /* ---- the per-frame call: render() src/dispatch.cu:156-163 --------------------------------- */
 /* Host-buffer form, same contract as the reference: previous_render (W*H*3 floats, row-major
  * interleaved RGB) is read, blended as (colour + prev*frame_num)/(frame_num+1)
@@ -667,6 +690,9 @@ typedef struct rt_flat_view {
     const float *tri_uv; int32_t num_triangles, num_nodes, has_mesh;
 } rt_flat_view;
 rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out);
+/* the same view of a committed scene AS IT IS ON THE DEVICE (waits for the device first): what rt_scene_update_mesh[_device] is tested by.
+ * Pointers stay valid until the next call on the same scene or its destruction. */
+rt_status rt_debug_scene_read(rt_ctx *ctx, rt_scene *scene, rt_flat_view *out);
 /* evaluates one function of the shared math / RNG headers ON THE DEVICE, element-wise, on raw
  * 32-bit patterns (host pointers).  op: 0 rt_logf, 1 rt_cosf, 2 rt_sinf, 3 rt_asinf, 4 rt_acosf,
  * 5 rt_u01, 6 rt_jitter, 7 rt_theta (5-7 take the uint32 hash output), 8 sqrtf, 9 1.0f/x,

@@ -66,6 +66,7 @@ class rt_adaptive_params(C.Structure):
 
 ADAPTIVE_MAX_PASSES, ADAPTIVE_MAX_SPP = 64, 1 << 24   # RT_ADAPTIVE_*
 BUDGET_MAX = 65535                                     # RT_BUDGET_MAX: the most samples one budget render gives a pixel
+REBUILD_LDS_TRIS = 2048                                # RT_REBUILD_LDS_TRIS: the largest tree segment one workgroup rebuilds in LDS (update_mesh)
 VIEWS_MAX = 32                                         # RT_VIEWS_MAX: the views one launch of render_views_device renders
 
 
@@ -133,6 +134,8 @@ ABI = {
     "rt_scene_commit": (st, [vp, vp, vpp]),
     "rt_scene_destroy": (None, [vp]),
     "rt_scene_get_info": (st, [vp, C.POINTER(rt_scene_info)]),
+    "rt_scene_update_mesh_device": (st, [vp, vp, i32, vp, i32, vp]),
+    "rt_scene_update_mesh": (st, [vp, vp, i32, fp, i32]),
     "rt_render": (st, [vp, vp, cam, rs, i32, i32p, fp]),
     "rt_render_frames": (st, [vp, vp, cam, rs, i32p, i32, i32p, fp]),
     "rt_render_device": (st, [vp, vp, cam, rs, i32, i32, tiles, vp, vp, vp]),
@@ -178,6 +181,7 @@ ABI = {
     "rt_peer_access": (i32, [vp, vp]),
     "rt_to_rgba8_device": (st, [vp, vp, i32, i32, vp, vp]),
     "rt_debug_flatten": (st, [vp, C.POINTER(rt_flat_view)]),
+    "rt_debug_scene_read": (st, [vp, vp, C.POINTER(rt_flat_view)]),
     "rt_debug_eval": (st, [vp, i32, u32p, u32p, i32]),
     "rt_debug_exhaustive": (st, [vp, u64p]),
     "rt_debug_read_stats": (st, [vp, u64p]),

@@ -121,6 +121,12 @@ rt_status TileListCache::on_device(rt_ctx *ctx, const uint32_t *list, int n, hip
     return RT_OK;
 }
 
+uint32_t rt_detail::next_scene_uid()
+{
+    static std::atomic<uint32_t> next_uid{1};
+    return next_uid.fetch_add(1);
+}
+
 int rt_detail::batch_cap(const rt_ctx *ctx, size_t plane_floats)
 {
     const size_t plane_bytes = plane_floats * 4;
@@ -201,8 +207,7 @@ extern "C" rt_status rt_scene_commit(rt_ctx *ctx, const rt_scene_builder *b, rt_
     rt_scene *s = new (std::nothrow) rt_scene();
     if (!s) return RT_ERR_NOMEM;
     s->ctx = ctx;
-    static std::atomic<uint32_t> next_uid{1};
-    s->uid = next_uid.fetch_add(1);
+    s->uid = next_scene_uid();
     std::string err = rt_flatten(*b, s->flat);
     if (!err.empty()) { delete s; return set_err(ctx, RT_ERR_UNSUPPORTED, err); }
 

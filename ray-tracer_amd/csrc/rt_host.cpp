@@ -201,6 +201,7 @@ rt_status add_mesh_tris(rt_scene_builder *b, const std::vector<HostTri> &tris, c
     o.nodes = std::move(bb.nodes);
     o.tris.reserve(tris.size());
     for (int i : bb.order) o.tris.push_back(tris[i]);
+    o.order = std::move(bb.order);
     keep_texels(o);
     b->objs.push_back(std::move(o));
     return RT_OK;
@@ -701,6 +702,7 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
     out.num_nodes = (int)n_nodes;
     out.num_tris = (int)n_tris;
     if (any_uv) out.tri_uv.resize(n_tris * 6, 0.0f);
+    out.tri_order.assign(n_tris, 0);
 
     size_t node_base = 0, tri_base = 0, mesh_i = 0;
     for (size_t oi = 0; oi < b.objs.size(); oi++) {
@@ -744,6 +746,7 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
             q[1] = rt_f4{t.s1[1], t.s1[2], t.s2[0], t.s2[1]};
             q[2] = rt_f4{t.s2[2], t.n[0], t.n[1], t.n[2]};
             if (any_uv) std::memcpy(&out.tri_uv[(tri_base + k) * 6], t.uv, 24);
+            if (k < o.order.size()) out.tri_order[tri_base + k] = (int32_t)o.order[k];
         }
         /* per-object shading record */
         const rt_material &m = o.mat;

@@ -3,7 +3,7 @@
  * Stream), the context and its parts (rt_ctx: the tile-list cache, the view, the frame pipeline, the multi-GPU rank state, the knobs), the
  * committed scene (rt_scene), the error helpers, the functions of rt_capi.cpp that the other translation units call, the host-buffer round
  * trip and, at the end, what the entry points beside the renderer (rt_query_capi.cpp, rt_occlusion_capi.cpp, rt_ao_capi.cpp,
- * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp) have in common: the argument checks, the context's launch bracket and the
+ * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp, rt_update_capi.cpp) have in common: the argument checks, the context's launch bracket and the
  * ray kernels' argument block and launch.  It includes rt_launch.h, the kernel launchers' declarations: no translation unit declares one
  * itself.  rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed: include/rt_amd.h is the interface.
  */
@@ -21,6 +21,7 @@
 #include "rt_host.h"
 #include "rt_launch.h"         /* the kernel launchers: the seam to rt_kernel.hip */
 #include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
+#include "rt_rebuild.h"        /* the per-mesh plan of rt_scene_update_mesh, and its kernels' launcher */
 #include "rt_schedule.h"
 
 /* what crosses the library's translation units without being part of its interface: not in the dynamic symbol table */
@@ -228,14 +229,31 @@ struct rt_ctx {
     DevBuf<float> d_adaptive_ab;
     DevBuf<uint32_t> d_adaptive_count, d_adaptive_tiles;
     DevBuf<uint16_t> d_adaptive_budget;
+    /* rt_scene_update_mesh[_device] (rt_update_capi.cpp): the segments' boxes, the sort's words, two generations of the triangle list, and the
+     * host form's vertices on the device.  Shared by the updates of every scene of the context, in the launch order */
+    DevBuf<float> d_update_boxes, d_update_pts;
+    DevBuf<unsigned long long> d_update_words;
+    DevBuf<int32_t> d_update_perm;
     ViewsState views;
     Pipeline pipe;
     MultiRank multi;
 };
 
 
+/* What rt_scene_update_mesh[_device] keeps per mesh of a scene, made at the mesh's first update (rt_update_capi.cpp) */
+struct MeshUpdate {
+    int32_t n = 0, tri_base = 0, node_base = 0, mesh_index = 0;
+    rt_rb_plan plan;                     /* from n alone, checked against the tree the builder made */
+    DevBuf<rt_rb_seg> d_segs;
+    DevBuf<rt_rb_slot> d_slots;
+    DevBuf<float> d_uv0;                 /* the mesh's texture coordinates in commit order (scenes with UVs) */
+};
+
 struct rt_scene {
     rt_ctx *ctx = nullptr;
+    std::map<int32_t, MeshUpdate> updates;   /* by object index */
+    DevBuf<int32_t> d_perm;              /* per triangle of a mesh: the commit index of the one at that leaf position, as of the last update */
+    FlatScene debug_read;                /* rt_debug_scene_read's copy of what is on the device */
     /* (members go in reverse order: the blob is freed first, the texels last) */
     DevBuf<float> d_tex;
     DevBuf<float> d_tri_uv;
@@ -292,6 +310,8 @@ RT_HIDDEN rt_kernel_args kernel_args(const rt_ctx *ctx, const rt_scene *scene, c
                                      int32_t n_frames, int32_t frame_num, const rt_sched::Layout &L, const float *d_prev, float *d_out, uint32_t *tile_counter);
 RT_HIDDEN int launch_blocks(const rt_ctx *ctx, const rt_scene *scene, int num_tiles);
 RT_HIDDEN int batch_cap(const rt_ctx *ctx, size_t plane_floats);
+/* a scene's uid: at commit, and again after an update of its geometry (what was cached for the old one - the view, its tile costs - is then not found) */
+RT_HIDDEN uint32_t next_scene_uid();
 RT_HIDDEN void push_camera(std::vector<uint32_t> &key, const rt_camera *cam);
 
 /* The host-buffer forms' round trip (render() src/dispatch.cu:156-163): the caller's frame goes into the persistent buffer `into`

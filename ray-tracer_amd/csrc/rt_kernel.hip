@@ -51,3 +51,4 @@
 #include "rt_frame_kernels.h"      /* blend, tile copy, RGBA8 */
 #include "rt_debug_kernels.h"      /* the math headers evaluated on the device, for the tests */
 #include "rt_render_kernel.h"      /* the render kernel and its shape table */
+#include "rt_rebuild_kernel.h"     /* a committed mesh's BVH rebuilt from new vertices: nothing of the traversal either (last: the kernels before it are emitted as they were) */

@@ -154,6 +154,15 @@ public:
     void translate(float offset_x, float offset_y, float offset_z) { rt_obj_translate(h_, offset_x, offset_y, offset_z); }
     int num_vertices() const { return rt_obj_num_vertices(h_); }
     int num_faces() const { return rt_obj_num_faces(h_); }
+    /* the mesh's triangles, nine floats each, in the order a scene commits them (a quad gives two): what Renderer::update_mesh takes */
+    std::vector<float> triangles() const
+    {
+        const int n = rt_obj_num_triangles(h_);
+        if (n < 0) throw std::logic_error("Only triangle or quad meshes are supported.\n");
+        std::vector<float> out((size_t)n * 9);
+        if (n > 0 && rt_obj_get_triangles(h_, out.data()) != RT_OK) throw std::invalid_argument("face references a missing vertex");
+        return out;
+    }
     const rt_obj *handle() const { return h_; }
 
 private:
@@ -206,6 +215,12 @@ public:
     }
     /* SceneObjects::create_mesh src/main.cu:127-148 */
     void create_mesh(const ObjFileMesh &obj, const Material &mat) { check(rt_scene_add_obj_mesh(b_, obj.handle(), &mat.c)); }
+    /* ... from an array of triangles, nine floats each (rt_scene_add_mesh) */
+    void create_mesh(const std::vector<float> &triangles, const Material &mat)
+    {
+        if (triangles.size() % 9) throw std::invalid_argument("nine floats per triangle");
+        check(rt_scene_add_mesh(b_, triangles.data(), (int32_t)(triangles.size() / 9), &mat.c));
+    }
 
     /* create_cornell_box src/main.cu:252-288 */
     void create_cornell_box(Vec3 tl_near_pos, float width, float height, float depth, float light_width)
@@ -350,12 +365,20 @@ public:
         scene_ = nullptr;
         check(rt_scene_commit(ctx_, objs.handle(), &scene_));
     }
+    /* The next time step of the scene: the mesh at object_index (the index of its create_mesh call among the scene's objects) gets new vertices,
+     * nine floats per triangle in the order the mesh was committed with, as many triangles as it has.  Its BVH is rebuilt on the GPU; every later
+     * render sees what a scene committed with these triangles would show (rt_scene_update_mesh). */
+    void update_mesh(int object_index, const std::vector<float> &triangles)
+    {
+        if (triangles.size() % 9) throw std::invalid_argument("nine floats per triangle");
+        check(rt_scene_update_mesh(ctx_, scene_, object_index, triangles.data(), (int32_t)(triangles.size() / 9)));
+    }
     /* render(VariableRenderData*, int) src/dispatch.cu:156-163 */
     void render(const Camera &cam, const RenderData &rd, VariableRenderData *data, int current_time_ms)
     {
         if (data->previous_render.size() != (size_t)cam.c.width * (size_t)cam.c.height * 3) throw std::invalid_argument("previous_render has the wrong size");
         int32_t fn = data->frame_num;
-        check(rt_render(ctx_, scene_, &cam.c, &rd.c, current_time_ms, &fn, data->previous_render.data()));
+        check(rt_render(ctx_, scene_,&cam.c, &rd.c, current_time_ms, &fn, data->previous_render.data()));
         data->frame_num = fn;
     }
     /* several passes of the main loop body at once (src/main.cu:421-424, one seed per frame): the same

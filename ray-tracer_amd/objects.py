@@ -160,6 +160,18 @@ class ObjFileMesh(_Handle):
         return out
 
 
+def _flat_view_arrays(v):
+    """an rt_flat_view (rt_debug_flatten, rt_debug_scene_read) as a dict of copies"""
+    blob = np.ctypeslib.as_array(v.blob, shape=(v.blob_f4, 4)).copy() if v.blob_f4 else np.zeros((0, 4), np.float32)
+    raw = C.string_at(v.objects, v.num_objects * v.object_stride) if v.num_objects else b""
+    objs = np.frombuffer(raw, dtype=np.dtype([("type", "<i4"), ("prim_start", "<i4"), ("need_uv", "<i4"), ("root_ref", "<u4"), ("v", "<f4", (8,))]))
+    uv = np.ctypeslib.as_array(v.tri_uv, shape=(v.num_triangles, 6)).copy() if v.tri_uv else None
+    return {"blob": blob, "off_nodes": v.off_nodes, "off_tris": v.off_tris, "off_objlds": v.off_objlds,
+            "off_meshes": v.off_meshes, "num_meshes": v.num_meshes, "stack_entries": v.stack_entries,
+            "objects": objs, "tri_uv": uv, "num_triangles": v.num_triangles, "num_nodes": v.num_nodes,
+            "has_mesh": bool(v.has_mesh)}
+
+
 class SceneObjects(_Handle):
     """The object list of a scene: reference SceneObjects src/main.cu:94-296 with the
     Object::create_* factories of src/objects.cu:845-906 as methods."""
@@ -246,14 +258,7 @@ class SceneObjects(_Handle):
         """The flattened device layout as numpy arrays (tests only)."""
         v = rt_flat_view()
         self._check(lib().rt_debug_flatten(self._h, C.byref(v)))
-        blob = np.ctypeslib.as_array(v.blob, shape=(v.blob_f4, 4)).copy() if v.blob_f4 else np.zeros((0, 4), np.float32)
-        raw = C.string_at(v.objects, v.num_objects * v.object_stride) if v.num_objects else b""
-        objs = np.frombuffer(raw, dtype=np.dtype([("type", "<i4"), ("prim_start", "<i4"), ("need_uv", "<i4"), ("root_ref", "<u4"), ("v", "<f4", (8,))]))
-        uv = np.ctypeslib.as_array(v.tri_uv, shape=(v.num_triangles, 6)).copy() if v.tri_uv else None
-        return {"blob": blob, "off_nodes": v.off_nodes, "off_tris": v.off_tris, "off_objlds": v.off_objlds,
-                "off_meshes": v.off_meshes, "num_meshes": v.num_meshes, "stack_entries": v.stack_entries,
-                "objects": objs, "tri_uv": uv, "num_triangles": v.num_triangles, "num_nodes": v.num_nodes,
-                "has_mesh": bool(v.has_mesh)}
+        return _flat_view_arrays(v)
 
 
 class Camera:

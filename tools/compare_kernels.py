@@ -33,6 +33,10 @@ def encodings(co):
             m = re.search(r"// [0-9A-F]+: ((?:[0-9A-F]{8} ?)+)", line)
             if m:
                 cur.append(m.group(1).strip())
+    # the s_nop padding up to the next function's alignment is listed with the function before it, and changes with what follows: not its code
+    for words in out.values():
+        while words and words[-1] == "BF800000":
+            words.pop()
     return out
 
 
