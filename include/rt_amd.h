@@ -339,6 +339,52 @@ rt_status rt_render_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *c
  * not positive and finite, an offset that is not finite, a delta_u or delta_v of length 0. */
 rt_status rt_camera_lens(const rt_camera *cam, float focal_len, float focus_dist, float lens_u, float lens_v, rt_camera *out);
 
+/* ---- environment lighting: a cube-map sky ------------------------------------------------------
+ * Everywhere else a ray that leaves the scene sees one constant, rt_render_settings::sky_colour.  Here it sees a texel of a cube map: six
+ * square faces of n x n texels, 1 <= n <= RT_SKY_MAX_FACE, three binary32 values each.  No texel value is inspected: HDR values, Inf and
+ * NaN pass through.  The faces are numbered 0..5 = +X, -X, +Y, -Y, +Z, -Z; the caller's array is faces[face][row][col][3], row-major.
+ * (A cube map and not a latitude / longitude image: the lookup is compares, two divisions, two multiply-adds and two conversions, once per
+ * sample, and needs no inverse trigonometric function.)
+ *
+ * Lookup of a direction d = (x, y, z) - the ray's direction at the miss, the jittered, renormalised direction it was traced with.  Every
+ * operation is binary32, rounded once, nothing fused:
+ *     ax = |x|, ay = |y|, az = |z|
+ *     axis = (ax >= ay && ax >= az) ? X : (ay >= az ? Y : Z)          (a NaN compares false)
+ *     c = d[axis];  m = |c|;  face = 2 * axis + (c < 0 ? 1 : 0)       (-0 is the positive face)
+ *     (a, b) = the other two components in cyclic order: X: (y, z)   Y: (z, x)   Z: (x, y)
+ *     s = a / m;  t = b / m
+ *     col = clamp(f2i((s * 0.5f + 0.5f) * (float)n), 0, n - 1)        (mul, add, mul: three roundings)
+ *     row = clamp(f2i((t * 0.5f + 0.5f) * (float)n), 0, n - 1)
+ *     texel = faces[face][row][col]
+ * f2i converts towards zero, saturating, NaN -> 0.  The miss then adds, per channel, L = texel * sky_colour (one rounding) as
+ * fin = fin + L * thr: the renderer's own line with L in the place of sky_colour.  So rs->sky_colour is the map's tint and exposure,
+ * (1,1,1) leaves the map as it is, and two identities hold as uint32: a map of all 1.0f renders what rt_render_views_device renders with the
+ * same sky_colour, and a constant map c with tint s renders what sky_colour = fl(c * s) renders.
+ *
+ * The inverse mapping, for filling a map from any function of direction: rt_sky_texel_direction gives the direction through the centre of
+ * texel (face, row, col) of an n-face map:
+ *     s = ((float)col + 0.5f) / (float)n * 2.0f - 1.0f                 (t from row likewise)
+ * the major component is +1 or -1 and s, t are placed by the table above; the result is not normalised.  The lookup of that direction is
+ * (face, row, col) again - also of the direction normalised, and of the direction scaled by 1e-3f.  RT_ERR_INVALID: a null out, a
+ * face_size outside 1 .. RT_SKY_MAX_FACE, a face outside 0 .. 5, a row or col outside 0 .. face_size - 1 (out untouched). */
+typedef struct rt_sky rt_sky;
+#define RT_SKY_MAX_FACE 2048
+/* faces_rgb is host memory, 6 * face_size * face_size * 3 floats; it is copied and uploaded, and the call returns when the copy is done.
+ * The sky belongs to ctx.  RT_ERR_INVALID: a null ctx, faces_rgb or out; face_size out of range. */
+rt_status rt_sky_create(rt_ctx *ctx, int32_t face_size, const float *faces_rgb, rt_sky **out);
+/* waits for the context's launches first, as rt_ctx_synchronize does; destroy a context's skies before the context */
+void rt_sky_destroy(rt_sky *sky);
+rt_status rt_sky_texel_direction(int32_t face_size, int32_t face, int32_t row, int32_t col, float out[3]);
+/* rt_render_views_device with a sky: its modes, limits, seeds, schedule, launch order and rt_last_kernel_ms window, and like it the call
+ * leaves the context's cached view alone.  One camera repeated is a progressive batch of a still view; n_views = 1 is a single frame.
+ * RT_ERR_INVALID: everything rt_render_views_device refuses, a null sky, a sky of another context.  A refused call touches nothing. */
+rt_status rt_render_sky_device(rt_ctx *ctx, const rt_scene *scene, const rt_sky *sky, const rt_camera *cams, const int32_t *times_ms,
+                               int32_t n_views, const rt_render_settings *rs, int32_t accumulate, int32_t frame_num,
+                               float *d_frames, void *hip_stream);
+/* Host-buffer form, with rt_render_views' contract */
+rt_status rt_render_sky(rt_ctx *ctx, const rt_scene *scene, const rt_sky *sky, const rt_camera *cams, const int32_t *times_ms,
+                        int32_t n_views, const rt_render_settings *rs, int32_t accumulate, int32_t *frame_num, float *frames);
+
 /* number of rows a rank owns under a band tile spec (host helper for sizing compact buffers) */
 int32_t rt_tile_owned_rows(const rt_tile_spec *tiles, int32_t height);
 

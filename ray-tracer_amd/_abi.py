@@ -68,6 +68,7 @@ ADAPTIVE_MAX_PASSES, ADAPTIVE_MAX_SPP = 64, 1 << 24   # RT_ADAPTIVE_*
 BUDGET_MAX = 65535                                     # RT_BUDGET_MAX: the most samples one budget render gives a pixel
 REBUILD_LDS_TRIS = 2048                                # RT_REBUILD_LDS_TRIS: the largest tree segment one workgroup rebuilds in LDS (update_mesh)
 VIEWS_MAX = 32                                         # RT_VIEWS_MAX: the views one launch of render_views_device renders
+SKY_MAX_FACE = 2048                                    # RT_SKY_MAX_FACE: the most texels on the side of a cube-map sky's face
 
 
 class rt_adaptive_stats(C.Structure):
@@ -149,6 +150,11 @@ ABI = {
     "rt_render_views_device": (st, [vp, vp, cam, i32p, i32, rs, i32, i32, vp, vp]),
     "rt_render_views": (st, [vp, vp, cam, i32p, i32, rs, i32, i32p, fp]),
     "rt_camera_lens": (st, [cam, f32, f32, f32, f32, cam]),
+    "rt_sky_create": (st, [vp, i32, fp, vpp]),
+    "rt_sky_destroy": (None, [vp]),
+    "rt_sky_texel_direction": (st, [i32, i32, i32, i32, fp]),
+    "rt_render_sky_device": (st, [vp, vp, vp, cam, i32p, i32, rs, i32, i32, vp, vp]),
+    "rt_render_sky": (st, [vp, vp, vp, cam, i32p, i32, rs, i32, i32p, fp]),
     "rt_tile_owned_rows": (i32, [tiles, i32]),
     "rt_tile_costs": (st, [vp, u32p, u32p, u32p, i32, i32p]),
     "rt_partition_tiles": (st, [u32p, i32, i32, i32, i32p]),

@@ -3,7 +3,7 @@
  * Stream), the context and its parts (rt_ctx: the tile-list cache, the view, the frame pipeline, the multi-GPU rank state, the knobs), the
  * committed scene (rt_scene), the error helpers, the functions of rt_capi.cpp that the other translation units call, the host-buffer round
  * trip and, at the end, what the entry points beside the renderer (rt_query_capi.cpp, rt_occlusion_capi.cpp, rt_ao_capi.cpp,
- * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp, rt_update_capi.cpp) have in common: the argument checks, the context's launch bracket and the
+ * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp, rt_sky_capi.cpp, rt_update_capi.cpp) have in common: the argument checks, the context's launch bracket and the
  * ray kernels' argument block and launch.  It includes rt_launch.h, the kernel launchers' declarations: no translation unit declares one
  * itself.  rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed: include/rt_amd.h is the interface.
  */
@@ -13,6 +13,7 @@
 
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -264,6 +265,13 @@ struct rt_scene {
     uint32_t uid = 0;        /* distinguishes scenes in the tile-order cache (addresses get reused) */
 };
 
+/* a cube-map sky (rt_sky_capi.cpp, rt_sky.h): its context, the side of a face, the texels on the device (RT_SKY_TEXEL_FLOATS each) */
+struct rt_sky {
+    rt_ctx *ctx = nullptr;
+    int32_t face_size = 0;
+    DevBuf<float> d_texels;
+};
+
 /* check_cuda_error src/utils.cu:5-10 */
 inline rt_status hip_fail(rt_ctx *ctx, hipError_t e, const char *what)
 {
@@ -313,6 +321,18 @@ RT_HIDDEN int batch_cap(const rt_ctx *ctx, size_t plane_floats);
 /* a scene's uid: at commit, and again after an update of its geometry (what was cached for the old one - the view, its tile costs - is then not found) */
 RT_HIDDEN uint32_t next_scene_uid();
 RT_HIDDEN void push_camera(std::vector<uint32_t> &key, const rt_camera *cam);
+
+/* ---- what rt_sky_capi.cpp calls in rt_views_capi.cpp: the camera sequences with the kernel left open ---- */
+/* launches the views kernel, or a variant of it, for one block of arguments and the device's camera table */
+using ViewsLauncher = std::function<hipError_t(const rt_kernel_args &a, const float *d_cams, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream)>;
+/* a device form with everything but the views of one chunk bound: (cams, times_ms, n_views, frame_num, d_frames) */
+using ViewsDeviceForm = std::function<rt_status(const rt_camera *, const int32_t *, int32_t, int32_t, float *)>;
+RT_HIDDEN rt_status check_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views, const rt_render_settings *rs,
+                                int32_t accumulate, int32_t frame_num, const void *frames, bool device);
+RT_HIDDEN rt_status views_launch(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views, const rt_render_settings *rs,
+                                 int32_t accumulate, int32_t frame_num, float *d_frames, hipStream_t stream, const ViewsLauncher &launcher);
+RT_HIDDEN rt_status views_host_form(rt_ctx *ctx, const rt_camera *cams, const int32_t *times_ms, int32_t n_views, int32_t accumulate, int32_t *frame_num, float *frames,
+                                    const ViewsDeviceForm &device_form);
 
 /* The host-buffer forms' round trip (render() src/dispatch.cu:156-163): the caller's frame goes into the persistent buffer `into`
  * (d_prev or d_out), `render_and_wait(bytes)` renders n_frames frames into d_out and waits for them, the frame comes back and

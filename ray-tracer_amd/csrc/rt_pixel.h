@@ -16,6 +16,7 @@
 #include "rt_intersect.h"
 #include "rt_math.h"
 #include "rt_rng.h"
+#include "rt_sky.h"
 #include "rt_traverse.h"
 #include "rt_vec.h"
 
@@ -66,6 +67,15 @@ struct rt_views_args : rt_kernel_args {
     const float *cams;           /* num_frames x 12: cam_pos, tl_pixel_pos, delta_u, delta_v of frame k at cams + 12 * k */
 };
 __device__ __forceinline__ const rt_views_args &px_views(const rt_kernel_args &a) { return static_cast<const rt_views_args &>(a); }
+
+/* The argument block of the sky variant (rt_sky_kernel, rt_render_kernel.h; rt_render_sky_device in include/rt_amd.h): the views variant's,
+ * and the cube map a ray that leaves the scene looks its light up in (rt_sky.h).  Only under SKY, and only rt_sky_loop sets it: see
+ * px_budget. */
+struct rt_sky_args : rt_views_args {
+    const float *sky_texels;     /* 6 x sky_n x sky_n texels of RT_SKY_TEXEL_FLOATS floats: faces +X, -X, +Y, -Y, +Z, -Z, rows, columns */
+    int32_t sky_n;               /* texels on a face's side, 1 .. RT_SKY_MAX_FACE */
+};
+__device__ __forceinline__ const rt_sky_args &px_sky(const rt_kernel_args &a) { return static_cast<const rt_sky_args &>(a); }
 
 /* wave-uniform pixel chunk: linear pixel ids [next, end) of one 8x8 tile */
 struct Chunk {
@@ -239,9 +249,27 @@ __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, co
 }
 
 /* ================= SHADE, a ray that hit nothing (src/raytracer.cu:76-80): sky, end of sample == */
-template <bool BUDGET = false, bool VIEWS = false>
+/* SKY: the sky is the texel of the cube map in the ray's direction (rt_sky_lookup: compares, two divisions, two conversions) times the
+ * constant, which becomes the map's tint.  One load from global memory per sample, at an address that differs across the lanes; it is issued
+ * at the end of a path, where nothing else of the lane is in flight, and the wave's other lanes wait for it with this one - the SIMD's other
+ * waves cover it (DESIGN.md section 22 has what it costs).  The map is not staged into LDS: the scene's shape would change with it. */
+template <bool BUDGET = false, bool VIEWS = false, bool SKY = false>
 __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, const Frame &f)
 {
+    if (SKY) {
+        const rt_sky_args &s = px_sky(a);
+        const float *tx = s.sky_texels + (size_t)rt_sky_lookup(p.d.x, p.d.y, p.d.z, s.sky_n, nullptr, nullptr, nullptr) * RT_SKY_TEXEL_FLOATS;
+#if RT_SKY_TEXEL_FLOATS == 4
+        const v4f t = *(const v4f *)tx;
+        const V3 light = v3(t.x, t.y, t.z) * f.sky;
+#else
+        const V3 light = v3(tx[0], tx[1], tx[2]) * f.sky;
+#endif
+        p.fin = p.fin + light * p.thr;
+        p.mode = M_GEN;
+        px_end_sample<BUDGET, VIEWS>(p, a, f);
+        return;
+    }
     p.fin = p.fin + f.sky * p.thr;
     p.mode = M_GEN;
     px_end_sample<BUDGET, VIEWS>(p, a, f);

@@ -42,7 +42,9 @@ template <int NT, bool HAS_MESH, int MODE>
 __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES : RT_SMALL_WG_WAVES + 1)) void rt_render_kernel(const rt_kernel_args a)
 #define RT_LOOP_BUDGET false
 #define RT_LOOP_VIEWS false
+#define RT_LOOP_SKY false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
 
@@ -54,7 +56,9 @@ template <int NT, bool HAS_MESH, int MODE>
 __device__ __forceinline__ void rt_budget_loop(const rt_budget_args &a)
 #define RT_LOOP_BUDGET true
 #define RT_LOOP_VIEWS false
+#define RT_LOOP_SKY false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
 
@@ -72,7 +76,9 @@ template <int NT, bool HAS_MESH, int MODE>
 __device__ __forceinline__ void rt_views_loop(const rt_views_args &a)
 #define RT_LOOP_BUDGET false
 #define RT_LOOP_VIEWS true
+#define RT_LOOP_SKY false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
 
@@ -82,7 +88,26 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
     rt_views_loop<NT, HAS_MESH, MODE>(a);
 }
 
-/* ---- launchers (rt_launch.h) -------------------------------------------------------------- */
+/* The sky variant: the views variant whose rays that leave the scene look their light up in a cube map (rt_render_sky_device, rt_sky.h), same
+ * shapes and launch bounds.  What differs is px_shade_miss under SKY (rt_pixel.h); the loop is a function taking the block by reference like
+ * the other variants' (DESIGN.md section 22 has the registers per shape). */
+template <int NT, bool HAS_MESH, int MODE>
+__device__ __forceinline__ void rt_sky_loop(const rt_sky_args &a)
+#define RT_LOOP_BUDGET false
+#define RT_LOOP_VIEWS true
+#define RT_LOOP_SKY true
+#include "rt_render_loop.inc"
+#undef RT_LOOP_SKY
+#undef RT_LOOP_VIEWS
+#undef RT_LOOP_BUDGET
+
+template <int NT, bool HAS_MESH, int MODE>
+__global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES : RT_SMALL_WG_WAVES + 1)) void rt_sky_kernel(const rt_sky_args a)
+{
+    rt_sky_loop<NT, HAS_MESH, MODE>(a);
+}
+
+/* ---- launchers (rt_launch.h; the sky variant's: rt_sky.h) -------------------------------------------------------------- */
 template <int NT, bool HAS_MESH, int MODE>
 static int rt_blocks_one(size_t lds_bytes)
 {
@@ -92,7 +117,7 @@ static int rt_blocks_one(size_t lds_bytes)
     return n;
 }
 
-/* one launch of KERNEL (rt_render_kernel, rt_budget_kernel or rt_views_kernel of one shape) with its argument block */
+/* one launch of KERNEL (rt_render_kernel, rt_budget_kernel, rt_views_kernel or rt_sky_kernel of one shape) with its argument block */
 template <int NT, class Args, void (*KERNEL)(Args)>
 static void rt_launch_one(const Args *args, int blocks, size_t lds_bytes, hipStream_t stream)
 {
@@ -106,13 +131,15 @@ struct rt_shape_fns {
     void (*launch)(const rt_kernel_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
     void (*launch_budget)(const rt_budget_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
     void (*launch_views)(const rt_views_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
+    void (*launch_sky)(const rt_sky_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
 };
 template <size_t... I> static constexpr std::array<rt_shape_fns, sizeof...(I)> rt_shape_fns_of(std::index_sequence<I...>)
 {
     return {{{rt_blocks_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
               rt_launch_one<RT_SHAPES[I].threads, rt_kernel_args, rt_render_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
               rt_launch_one<RT_SHAPES[I].threads, rt_budget_args, rt_budget_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
-              rt_launch_one<RT_SHAPES[I].threads, rt_views_args, rt_views_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>}...}};
+              rt_launch_one<RT_SHAPES[I].threads, rt_views_args, rt_views_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
+              rt_launch_one<RT_SHAPES[I].threads, rt_sky_args, rt_sky_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>}...}};
 }
 static constexpr auto rt_shape_table = rt_shape_fns_of(std::make_index_sequence<std::size(RT_SHAPES)>());
 
@@ -155,6 +182,21 @@ extern "C" hipError_t rt_launch_views(const rt_kernel_args *args, const float *c
     static_cast<rt_kernel_args &>(v) = *args;
     v.cams = cams;
     rt_shape_table[i].launch_views(&v, blocks, lds_bytes, stream);
+    return hipGetLastError();
+}
+
+/* the sky variant on the same shape (declared in rt_sky.h): the views launch and the cube map's texels */
+extern "C" hipError_t rt_sky_enqueue(const rt_kernel_args *args, const float *cams, const float *texels, int32_t face_size, rt_shape shape, int blocks, size_t lds_bytes,
+                                     hipStream_t stream)
+{
+    const int i = rt_shape_index(shape);
+    if (i < 0) return hipErrorInvalidValue;
+    rt_sky_args s;
+    static_cast<rt_kernel_args &>(s) = *args;
+    s.cams = cams;
+    s.sky_texels = texels;
+    s.sky_n = face_size;
+    rt_shape_table[i].launch_sky(&s, blocks, lds_bytes, stream);
     return hipGetLastError();
 }
 

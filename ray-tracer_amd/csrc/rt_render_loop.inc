@@ -1,12 +1,14 @@
 /*
  * rt_render_loop.inc — the body of the render kernel: included by rt_render_kernel.h once per kernel that runs the wave loop, behind the
  * head of what runs it (template <int NT, bool HAS_MESH, int MODE> ... (ARGS a)), with RT_LOOP_BUDGET defined as false (rt_render_kernel,
- * rt_views_loop) or true (rt_budget_loop) and RT_LOOP_VIEWS as true (rt_views_loop: a camera per frame of the launch) or false.  Text, not a function: called as a function the loop compiles to other code in all thirteen render
+ * rt_views_loop, rt_sky_loop) or true (rt_budget_loop), RT_LOOP_VIEWS as true (rt_views_loop, rt_sky_loop: a camera per frame of the launch) or
+ * false and RT_LOOP_SKY as true (rt_sky_loop: a miss looks the sky up in a cube map) or false.  Text, not a function: called as a function the loop compiles to other code in all thirteen render
  * kernels, and the render kernel's code is kept byte for byte.
  */
 {
     constexpr bool BUDGET = RT_LOOP_BUDGET;
     constexpr bool VIEWS = RT_LOOP_VIEWS;
+    constexpr bool SKY = RT_LOOP_SKY;
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
     const int lane = tid & (RT_WAVE - 1);
@@ -67,7 +69,7 @@
          * condition has to take the batch, or the wave comes back with nothing changed.  Both conditions are stated in
          * rt_device_scene.h (RT_ROUND_SHADES, rt_traversal_yields), where tests/sanitize/capi_host_fuzz.cpp (check_progress) takes
          * them from too. */
-        if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss<BUDGET, VIEWS>(p, a, f);
+        if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss<BUDGET, VIEWS, SKY>(p, a, f);
         {
             const int n_hit = __popcll(__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_SHADE, RT_ICMP_EQ));
             const bool others = (__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_GEN, RT_ICMP_EQ) |

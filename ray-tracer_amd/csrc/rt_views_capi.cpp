@@ -4,6 +4,8 @@
  * rt_views_kernel (the render kernel with a camera per frame of the launch), the fold is rt_capi.cpp's; the argument checks, the host
  * form's chunking and the lens are rt_views.h, the schedule is rt_sched::views_job_order (neither needs HIP:
  * tests/sanitize/views_host_fuzz.cpp drives them on the host).  The context's cached view (rt_ctx::view) is neither read nor written here.
+ * The checks, the launch and the host form's loop are functions of rt_detail (rt_internal.h) taking the kernel's launcher: rt_sky_capi.cpp
+ * runs the sky variant through them.
  */
 #include <cstdint>
 #include <cstring>
@@ -16,6 +18,10 @@
 namespace {
 
 constexpr size_t CAM_WORDS = (size_t)RT_VIEWS_MAX * 12;      /* the camera table's place at the head of ViewsState::d_table */
+
+}  // namespace
+
+namespace rt_detail {
 
 /* device: one launch's limit on the number of views applies (rt_views::launch_cap); the host form takes any number */
 rt_status check_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views, const rt_render_settings *rs,
@@ -30,14 +36,11 @@ rt_status check_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams,
     return RT_OK;
 }
 
-}  // namespace
-
-extern "C" rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views,
-                                            const rt_render_settings *rs, int32_t accumulate, int32_t frame_num, float *d_frames, void *hip_stream)
+/* The device form of a views launch whose arguments have passed check_views, with the kernel's launcher the caller's: rt_launch_views here,
+ * the sky variant's in rt_sky_capi.cpp (this translation unit references only the former). */
+rt_status views_launch(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views, const rt_render_settings *rs,
+                       int32_t accumulate, int32_t frame_num, float *d_frames, hipStream_t stream, const ViewsLauncher &launcher)
 {
-    rt_status st = check_views(ctx, scene, cams, times_ms, n_views, rs, accumulate, frame_num, d_frames, true);
-    if (st != RT_OK) return st;
-    hipStream_t stream = (hipStream_t)hip_stream;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     const rt_sched::Layout L(rt_sched::whole_image_spec(), cams[0].width, cams[0].height);
     const size_t plane_floats = L.plane_floats();
@@ -72,7 +75,7 @@ extern "C" rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, 
         vs.uploaded = true;
         RT_HIP(ctx, hipMemsetAsync(a.tile_counter, 0, 512, stream), "clearing tile counter");
         RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");        /* (again: rt_last_kernel_ms starts at the render kernel) */
-        RT_HIP(ctx, rt_launch_views(&a, (const float *)vs.d_table.p, scene->kernel.shape, blocks, scene->kernel.lds_bytes, stream), "launching views kernel");
+        RT_HIP(ctx, launcher(a, (const float *)vs.d_table.p, scene->kernel.shape, blocks, scene->kernel.lds_bytes, stream), "launching views kernel");
         if (accumulate) return fold(ctx, L, ctx->d_partial.p, n_views, frame_num, d_frames, nullptr, stream);
         /* separate frames: each plane becomes frame 0 of its view in place - (c + 0 * 0) / 1, a NaN as the canonical quiet NaN - which is
          * the blend of one plane at frame_num 0.  All planes in one pass while a launch can index them, else view by view */
@@ -88,12 +91,11 @@ extern "C" rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, 
     });
 }
 
-extern "C" rt_status rt_render_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views,
-                                     const rt_render_settings *rs, int32_t accumulate, int32_t *frame_num, float *frames)
+/* The host form over a device form (rt_render_views_device, or the sky's): frames through the context's buffer, in launches of up to the
+ * device form's limit.  The arguments have passed check_views' host variant. */
+rt_status views_host_form(rt_ctx *ctx, const rt_camera *cams, const int32_t *times_ms, int32_t n_views, int32_t accumulate, int32_t *frame_num, float *frames,
+                          const ViewsDeviceForm &device_form)
 {
-    if (!frame_num) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    rt_status st = check_views(ctx, scene, cams, times_ms, n_views, rs, accumulate, *frame_num, frames, false);
-    if (st != RT_OK) return st;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     const size_t frame_floats = (size_t)cams[0].width * (size_t)cams[0].height * 3;
     const int32_t cap = rt_views::launch_cap(accumulate, batch_cap(ctx, frame_floats));
@@ -102,7 +104,7 @@ extern "C" rt_status rt_render_views(rt_ctx *ctx, const rt_scene *scene, const r
     if (accumulate && *frame_num > 0) RT_HIP(ctx, hipMemcpy(d.p, frames, frame_floats * 4, hipMemcpyHostToDevice), "copying previous frame");
     for (int32_t done = 0; done < n_views;) {
         const int32_t k = rt_views::next_chunk(n_views, done, cap);
-        st = rt_render_views_device(ctx, scene, cams + done, times_ms + done, k, rs, accumulate, accumulate ? *frame_num + done : 0, d.p, nullptr);
+        const rt_status st = device_form(cams + done, times_ms + done, k, accumulate ? *frame_num + done : 0, d.p);
         if (st != RT_OK) return st;
         if (!accumulate) {
             RT_HIP(ctx, hipDeviceSynchronize(), "views kernel");
@@ -117,6 +119,30 @@ extern "C" rt_status rt_render_views(rt_ctx *ctx, const rt_scene *scene, const r
     }
     RT_HIP(ctx, hipPeekAtLastError(), "final check after render");
     return RT_OK;
+}
+
+}  // namespace rt_detail
+
+extern "C" rt_status rt_render_views_device(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views,
+                                            const rt_render_settings *rs, int32_t accumulate, int32_t frame_num, float *d_frames, void *hip_stream)
+{
+    rt_status st = check_views(ctx, scene, cams, times_ms, n_views, rs, accumulate, frame_num, d_frames, true);
+    if (st != RT_OK) return st;
+    return views_launch(ctx, scene, cams, times_ms, n_views, rs, accumulate, frame_num, d_frames, (hipStream_t)hip_stream,
+                        [](const rt_kernel_args &a, const float *d_cams, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream) {
+                            return rt_launch_views(&a, d_cams, shape, blocks, lds_bytes, stream);
+                        });
+}
+
+extern "C" rt_status rt_render_views(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cams, const int32_t *times_ms, int32_t n_views,
+                                     const rt_render_settings *rs, int32_t accumulate, int32_t *frame_num, float *frames)
+{
+    if (!frame_num) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    rt_status st = check_views(ctx, scene, cams, times_ms, n_views, rs, accumulate, *frame_num, frames, false);
+    if (st != RT_OK) return st;
+    return views_host_form(ctx, cams, times_ms, n_views, accumulate, frame_num, frames, [&](const rt_camera *c, const int32_t *t, int32_t k, int32_t fn, float *d) {
+        return rt_render_views_device(ctx, scene, c, t, k, rs, accumulate, fn, d, nullptr);
+    });
 }
 
 extern "C" rt_status rt_camera_lens(const rt_camera *cam, float focal_len, float focus_dist, float lens_u, float lens_v, rt_camera *out)

@@ -341,6 +341,31 @@ struct VariableRenderData {
     std::vector<float> previous_render;
 };
 
+/* A cube-map sky on a renderer's GPU (rt_sky_create; Renderer::create_sky makes one, Renderer::render_sky renders under it).  It must go
+ * before the renderer it came from. */
+class Sky {
+public:
+    Sky(Sky &&o) noexcept : h_(o.h_), face_size_(o.face_size_) { o.h_ = nullptr; }
+    Sky(const Sky &) = delete;
+    Sky &operator=(const Sky &) = delete;
+    ~Sky() { rt_sky_destroy(h_); }
+    const rt_sky *handle() const { return h_; }
+    int face_size() const { return face_size_; }
+    /* the direction through the centre of texel (face, row, col) of an n-face map (rt_sky_texel_direction): fill a map with any function of it */
+    static Vec3 texel_direction(int face_size, int face, int row, int col)
+    {
+        float d[3];
+        if (rt_sky_texel_direction(face_size, face, row, col, d) != RT_OK) throw std::invalid_argument("no such texel");
+        return Vec3(d[0], d[1], d[2]);
+    }
+
+private:
+    friend class Renderer;
+    Sky(rt_sky *h, int face_size) : h_(h), face_size_(face_size) {}
+    rt_sky *h_ = nullptr;
+    int face_size_ = 0;
+};
+
 /* One GPU: owns the HIP context and the uploaded scene (replaces the __constant__ symbols and
  * allocate_constant_mem, src/dispatch.cu:104-108). */
 class Renderer {
@@ -414,6 +439,36 @@ public:
         std::vector<float> frames(frame * cams.size());
         int32_t fn = 0;
         check(rt_render_views(ctx_, scene_, c.data(), t.data(), (int32_t)c.size(), &rd.c, 0, &fn, frames.data()));
+        return frames;
+    }
+    /* A sky from faces[6][n][n][3] (faces +X, -X, +Y, -Y, +Z, -Z; rows; columns), copied to the GPU */
+    Sky create_sky(int face_size, const std::vector<float> &faces_rgb)
+    {
+        if (face_size < 1 || faces_rgb.size() != (size_t)6 * (size_t)face_size * (size_t)face_size * 3) throw std::invalid_argument("faces must hold 6 * n * n * 3 floats");
+        rt_sky *h = nullptr;
+        check(rt_sky_create(ctx_, face_size, faces_rgb.data(), &h));
+        return Sky(h, face_size);
+    }
+    /* render_views under a sky (rt_render_sky): a ray that leaves the scene takes its light from the map, tinted by rd's sky colour */
+    std::vector<float> render_sky(const Sky &sky, const std::vector<Camera> &cams, const RenderData &rd, const std::vector<int> &times_ms, bool accumulate = false,
+                                  VariableRenderData *data = nullptr)
+    {
+        if (cams.empty() || cams.size() != times_ms.size()) throw std::invalid_argument("one time per camera, at least one camera");
+        if (accumulate && !data) throw std::invalid_argument("an accumulated sequence needs the frame it goes into");
+        const size_t frame = (size_t)cams[0].c.width * (size_t)cams[0].c.height * 3;
+        if (accumulate && data->previous_render.size() != frame) throw std::invalid_argument("previous_render has the wrong size");
+        std::vector<rt_camera> c;
+        for (const Camera &cam : cams) c.push_back(cam.c);
+        std::vector<int32_t> t(times_ms.begin(), times_ms.end());
+        if (accumulate) {
+            int32_t fn = data->frame_num;
+            check(rt_render_sky(ctx_, scene_, sky.handle(), c.data(), t.data(), (int32_t)c.size(), &rd.c, 1, &fn, data->previous_render.data()));
+            data->frame_num = fn;
+            return data->previous_render;
+        }
+        std::vector<float> frames(frame * cams.size());
+        int32_t fn = 0;
+        check(rt_render_sky(ctx_, scene_, sky.handle(), c.data(), t.data(), (int32_t)c.size(), &rd.c, 0, &fn, frames.data()));
         return frames;
     }
     float last_kernel_ms()
