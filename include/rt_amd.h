@@ -160,9 +160,16 @@ void rt_scene_destroy(rt_scene *s);
 /* introspection for tests: bytes of LDS per workgroup, node / triangle counts, the launch shape chosen for the
  * scene (workgroup size and how many workgroups are resident per CU); scene_in_lds: 1 the whole scene is staged
  * into LDS, 2 everything but the triangles (a mesh of more than ~1,500 triangles: its BVH still fits), 0 nothing
- * (the kernel reads the scene from global memory / L2) */
+ * (the kernel reads the scene from global memory / L2); kernel_variant: which render kernel of that shape plain frames run
+ * (rt_render_device, rt_render_device_batch, the frame pipeline, rt_render_multi_device) - 0 the generic one, 1 the one compiled
+ * for scenes whose objects besides at most one mesh are all spheres and whose materials need no texture coordinates, refraction or
+ * texture.  Decided at commit from the scene alone; RT_AMD_KERNEL_VARIANT=generic in the environment of rt_scene_commit keeps 0.
+ * Both compute the same frames bit for bit */
+#define RT_KERNEL_VARIANT_GENERIC 0
+#define RT_KERNEL_VARIANT_TRAITS 1
 typedef struct rt_scene_info {
     int32_t num_objects, num_triangles, num_nodes, lds_bytes, scene_in_lds, threads_per_block, stack_entries, blocks_per_cu;
+    int32_t kernel_variant;
 } rt_scene_info;
 rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *out);
 
@@ -734,6 +741,10 @@ typedef struct rt_flat_view {
     int32_t off_nodes, off_tris, off_objlds, off_meshes, num_meshes, stack_entries;
     const void *objects; int32_t num_objects, object_stride;
     const float *tri_uv; int32_t num_triangles, num_nodes, has_mesh;
+    /* traits: bit 0 every object that is not a mesh is a sphere, bit 1 at most one mesh, bit 2 no material needs texture coordinates,
+     * refracts or carries a texture; kernel_variant: the render kernel a scene of these traits runs, as rt_scene_info reports it (decided
+     * on the host from the traits and RT_AMD_KERNEL_VARIANT alone: rt_debug_flatten needs no device for it) */
+    int32_t traits, kernel_variant;
 } rt_flat_view;
 rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out);
 /* the same view of a committed scene AS IT IS ON THE DEVICE (waits for the device first): what rt_scene_update_mesh[_device] is tested by.

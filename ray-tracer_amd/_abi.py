@@ -43,7 +43,12 @@ class rt_rank(C.Structure):
 
 
 class rt_scene_info(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("num_objects", "num_triangles", "num_nodes", "lds_bytes", "scene_in_lds", "threads_per_block", "stack_entries", "blocks_per_cu")]
+    _fields_ = [(n, C.c_int32) for n in ("num_objects", "num_triangles", "num_nodes", "lds_bytes", "scene_in_lds", "threads_per_block", "stack_entries", "blocks_per_cu", "kernel_variant")]
+
+
+# rt_scene_info.kernel_variant / rt_flat_view.kernel_variant by name, and rt_flat_view.traits' bits (rt_device_scene.h RT_TRAIT_*)
+KERNEL_VARIANTS = ("generic", "traits")
+SCENE_TRAITS = {"SPHERES_ONLY": 1, "ONE_MESH": 2, "PLAIN_MATERIALS": 4}
 
 
 class rt_flat_view(C.Structure):
@@ -51,7 +56,8 @@ class rt_flat_view(C.Structure):
                 ("off_tris", C.c_int32), ("off_objlds", C.c_int32), ("off_meshes", C.c_int32), ("num_meshes", C.c_int32),
                 ("stack_entries", C.c_int32), ("objects", C.c_void_p),
                 ("num_objects", C.c_int32), ("object_stride", C.c_int32), ("tri_uv", C.POINTER(C.c_float)),
-                ("num_triangles", C.c_int32), ("num_nodes", C.c_int32), ("has_mesh", C.c_int32)]
+                ("num_triangles", C.c_int32), ("num_nodes", C.c_int32), ("has_mesh", C.c_int32),
+                ("traits", C.c_int32), ("kernel_variant", C.c_int32)]
 
 
 class rt_denoise_params(C.Structure):

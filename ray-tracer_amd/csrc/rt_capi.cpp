@@ -221,9 +221,18 @@ extern "C" rt_status rt_scene_commit(rt_ctx *ctx, const rt_scene_builder *b, rt_
     const size_t per_thread = s->flat.has_mesh ? (size_t)(s->flat.stack_entries + 1) * 8 : 0;
     const char *shape_err = nullptr;
     (void)hipSetDevice(ctx->device);
+    /* which render kernel of a shape the scene runs (rt_sched::choose_variant) is fixed by its traits: the occupancy probes ask about that kernel */
+    const uint32_t traits = s->flat.traits;
+    const bool generic = rt_sched::variant_forced_generic(getenv("RT_AMD_KERNEL_VARIANT"));
     const rt_status st = rt_sched::choose_shape(s->flat.has_mesh, blob_bytes, (size_t)s->flat.off_tris * sizeof(rt_f4), per_thread, ov,
-                                                rt_kernel_blocks_per_cu, s->kernel, &shape_err);
+                                                [traits, generic](rt_shape shape, size_t lds_bytes) {
+                                                    shape.variant = rt_sched::choose_variant(traits, generic, shape);
+                                                    return rt_kernel_blocks_per_cu(shape, lds_bytes);
+                                                },
+                                                s->kernel, &shape_err);
     if (st != RT_OK) { delete s; return set_err(ctx, st, shape_err); }
+    s->kernel.shape.variant = rt_sched::choose_variant(traits, generic, s->kernel.shape);
+    s->kernel.shape.mesh_obj = s->flat.mesh_obj;
     /* the occupancy probes discard their errors: a failed probe must not surface later as a launch error */
     (void)hipGetLastError();
 
@@ -266,6 +275,7 @@ extern "C" rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *out)
     out->threads_per_block = s->kernel.shape.threads;
     out->stack_entries = s->flat.stack_entries;
     out->blocks_per_cu = s->kernel.blocks_per_cu;
+    out->kernel_variant = s->kernel.shape.variant;
     return RT_OK;
 }
 

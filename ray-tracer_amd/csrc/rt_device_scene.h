@@ -36,11 +36,43 @@
 #define RT_SCENE_GLOBAL 0            /* every section from global memory; LDS holds only the traversal stacks */
 #define RT_SCENE_LDS 1               /* the whole blob staged into LDS */
 #define RT_SCENE_HYBRID 2            /* everything but the triangles in LDS, the triangles from global memory */
+/* What is fixed about a scene when it is committed and lets the render kernel leave out control flow that would come out the same for every
+ * lane, ray and hit (rt_flatten decides them, rt_host.cpp; rt_sched::choose_variant picks the kernel, rt_schedule.h):
+ *   SPHERES_ONLY     every object that is not a mesh is a sphere: the walk over the object list is the sphere test alone
+ *   ONE_MESH         at most one mesh: a generated ray tests its root box once and a finished traversal goes straight to shading
+ *   PLAIN_MATERIALS  no material needs texture coordinates, refracts or carries a texture: shading has no such regions */
+#define RT_TRAIT_SPHERES_ONLY 1
+#define RT_TRAIT_ONE_MESH 2
+#define RT_TRAIT_PLAIN_MATERIALS 4
+#define RT_TRAITS_ALL (RT_TRAIT_SPHERES_ONLY | RT_TRAIT_ONE_MESH | RT_TRAIT_PLAIN_MATERIALS)
+/* A scene that has ALL the traits runs rt_traits_kernel (rt_render_kernel.h) where its shape has one.  Which of the traits that kernel makes
+ * use of is a matter of the shape: each set below is the one measured fastest on that class of shapes, and a class where none gained, or that
+ * no qualifying scene was measured on, has no traits kernel (0) and keeps rt_render_kernel (DESIGN.md section 23 has the figures: less source
+ * is not always fewer issued instructions here).  A development build may name other sets (tools/build_variants.py
+ * name=-DRT_VARIANT_TRAITS_MESH_1024=1): that is how each trait was measured alone. */
+#ifndef RT_VARIANT_TRAITS_NO_MESH
+#define RT_VARIANT_TRAITS_NO_MESH RT_TRAITS_ALL                                             /* three spheres: -9.5 % */
+#endif
+#ifndef RT_VARIANT_TRAITS_MESH_1024
+#define RT_VARIANT_TRAITS_MESH_1024 (RT_TRAIT_SPHERES_ONLY | RT_TRAIT_ONE_MESH)            /* monkey: -3.5 % (with PLAIN_MATERIALS as well: -1.2 %) */
+#endif
+#ifndef RT_VARIANT_TRAITS_MESH_SMALL
+#define RT_VARIANT_TRAITS_MESH_SMALL (RT_TRAIT_ONE_MESH | RT_TRAIT_PLAIN_MATERIALS)        /* cube, 256 threads: -3.3 % (all three: +3.9 %) */
+#endif
+constexpr int rt_variant_traits(int has_mesh, int mode, int threads)
+{
+    return mode != RT_SCENE_LDS ? 0 : (!has_mesh ? (RT_VARIANT_TRAITS_NO_MESH) : (threads == 1024 ? (RT_VARIANT_TRAITS_MESH_1024) : (RT_VARIANT_TRAITS_MESH_SMALL)));
+}
 /* A shape of the render kernel: rt_render_kernel<threads, has_mesh, mode>.  RT_SHAPES are the ones built (rt_render_kernel.h
  * instantiates exactly these), in the order a scene's shape is chosen from them (rt_sched::choose_shape): without a mesh
  * the smaller workgroup first, with one the larger. */
+#define RT_VARIANT_GENERIC 0         /* rt_render_kernel */
+#define RT_VARIANT_TRAITS_KERNEL 1   /* rt_traits_kernel */
+/* `variant` and `mesh_obj` ride along to the launch (rt_launch_render): which of the two render kernels of the shape runs, and for
+ * rt_traits_kernel the one mesh's place in the object list (-1: no mesh).  They are no part of a shape's identity. */
 struct rt_shape {
     int32_t has_mesh, mode, threads;
+    int32_t variant = RT_VARIANT_GENERIC, mesh_obj = -1;
     constexpr bool operator==(const rt_shape &o) const { return has_mesh == o.has_mesh && mode == o.mode && threads == o.threads; }
 };
 inline constexpr rt_shape RT_SHAPES[] = {

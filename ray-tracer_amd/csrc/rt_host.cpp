@@ -21,6 +21,7 @@
 #include <new>
 
 #include "rt_math.h"
+#include "rt_schedule.h"
 
 namespace {
 
@@ -675,9 +676,26 @@ extern "C" void rt_camera_default(int32_t W, int32_t H, rt_camera *out)
 }
 
 /* ================================ flattening =============================================== */
+/* The traits as the kernel would find them in the records written below: the object's type, and of the material the three things px_shade
+ * (rt_pixel.h) tests in `packed` - bit 4 (need_uv), bits 1..0 (the type) and bits 3..2 (the texture). */
+uint32_t rt_scene_traits(const rt_scene_builder &b)
+{
+    uint32_t traits = RT_TRAITS_ALL;
+    size_t n_meshes = 0;
+    for (const HostObject &o : b.objs) {
+        if (o.type == RT_OBJ_MESH) n_meshes++;
+        else if (o.type != RT_OBJ_SPHERE) traits &= ~(uint32_t)RT_TRAIT_SPHERES_ONLY;
+        const rt_material &m = o.mat;
+        if (m.need_uv || ((uint32_t)m.type & 3u) == RT_DEV_MAT_REFRACTIVE || ((uint32_t)m.tex_type & 3u) != 0u) traits &= ~(uint32_t)RT_TRAIT_PLAIN_MATERIALS;
+    }
+    if (n_meshes > 1) traits &= ~(uint32_t)RT_TRAIT_ONE_MESH;
+    return traits;
+}
+
 std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
 {
     out = FlatScene();
+    out.traits = rt_scene_traits(b);
     size_t n_nodes = 0, n_tris = 0;
     bool any_uv = false;
     for (const HostObject &o : b.objs) {
@@ -730,6 +748,7 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
             rt_f4 *mt = &out.blob[(size_t)out.off_meshes + mesh_i * 2];
             mt[0] = rt_f4{o.v[0], o.v[1], o.v[2], o.v[3]};
             mt[1] = rt_f4{o.v[4], o.v[5], rt_u2f(ro.root_ref), rt_u2f((uint32_t)oi)};
+            if (mesh_i == 0) out.mesh_obj = (int)oi;
             mesh_i++;
             out.stack_entries = std::max(out.stack_entries, o.stack_need);
         }
@@ -795,5 +814,7 @@ extern "C" rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out)
     out->num_triangles = f.num_tris;
     out->num_nodes = f.num_nodes;
     out->has_mesh = f.has_mesh ? 1 : 0;
+    out->traits = (int32_t)f.traits;
+    out->kernel_variant = rt_sched::choose_variant(f.traits, rt_sched::variant_forced_generic(getenv("RT_AMD_KERNEL_VARIANT")));
     return RT_OK;
 }

@@ -54,7 +54,12 @@ struct FlatScene {
     std::vector<float> tex_data;                 /* IMAGE texels of all objects, back to back */
     int num_tris = 0, num_nodes = 0;
     bool has_mesh = false;
+    uint32_t traits = 0;                         /* RT_TRAIT_* (rt_device_scene.h): what of the scene lets the render kernel leave control flow out */
+    int mesh_obj = -1;                           /* the first mesh's place in the object list (with RT_TRAIT_ONE_MESH: the only one's), or -1 */
 };
+
+/* the traits of a flattened object list: from the object types and the materials alone, so rt_scene_update_mesh never changes them */
+uint32_t rt_scene_traits(const rt_scene_builder &b);
 
 /* returns "" or an error message */
 std::string rt_flatten(const rt_scene_builder &b, FlatScene &out);

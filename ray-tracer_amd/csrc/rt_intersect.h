@@ -143,9 +143,39 @@ __device__ __forceinline__ bool quad_test(const v4f *tris, int first, V3 o, V3 d
 
 /* The closest hit among the non-mesh objects: get_ray_collision src/raytracer.cu:24-46, shared by the render kernels (px_gen,
  * UNIT_DIR: the direction comes out of normalised()) and the query kernels (rt_query_kernel.h: any direction). */
-template <bool UNIT_DIR>
-__device__ __forceinline__ void rt_closest_simple(V3 o, V3 d, int num_objects, const Lds &L, float &best_t_out, int &best_obj_out, int &best_prim_out)
+/* TRAITS (RT_TRAIT_*, rt_device_scene.h; 0 everywhere but in rt_traits_kernel): what the scene's commit has fixed about the list.
+ * SPHERES_ONLY: every entry is a sphere or a mesh, so the body is the sphere test alone, the same operations in the same order, from the one
+ * record of the three that a sphere uses.  With ONE_MESH as well the mesh is the entry `skip` (a kernel argument, -1 without a mesh) and is
+ * passed over by a scalar compare without reading anything of it; without, an entry's type is read and compared once. */
+template <bool UNIT_DIR, int TRAITS = 0>
+__device__ __forceinline__ void rt_closest_simple(V3 o, V3 d, int num_objects, const Lds &L, float &best_t_out, int &best_obj_out, int &best_prim_out, int skip = -1)
 {
+    if (TRAITS & RT_TRAIT_SPHERES_ONLY) {
+        float best_t = RT_INF_F;
+        int best_obj = -1;
+        /* (kept rolled: the trip count is a launch argument, and copies of the body would only add to the scalar registers held across the round) */
+#pragma unroll 1
+        for (int i = 0; i < num_objects; i++) {
+            if (TRAITS & RT_TRAIT_ONE_MESH) {
+                if (i == skip) continue;
+            } else if ((int32_t)__float_as_uint(L.objtab[3 * i].x) != RT_OBJ_SPHERE) {
+                continue;
+            }
+            const v4f ob1 = L.objtab[3 * i + 1];
+            /* Sphere::hit as below: see there for the division */
+            V3 cq = v3(ob1.x, ob1.y, ob1.z) - o;
+            float qa = dot(d, d);
+            float qb = dot(d, cq) * (-2.0f);
+            float qc = dot(cq, cq) - ob1.w * ob1.w;
+            float disc = qb * qb - 4.0f * qa * qc;
+            if (disc >= 0.0f) {
+                float dist = UNIT_DIR ? rt__div_benign(-qb - rt_sqrt(disc), 2.0f * qa) : (-qb - rt_sqrt(disc)) / (2.0f * qa);
+                if (dist > RT_EPS_F && dist <= best_t) { best_t = dist; best_obj = i; }
+            }
+        }
+        best_t_out = best_t; best_obj_out = best_obj; best_prim_out = -1;
+        return;
+    }
     /* get_ray_collision src/raytracer.cu:24-46 over the non-mesh objects, in list order
      * (`<=`: the later object wins ties, :36; the precision_error term is a no-op for
      * accepted hits).  Meshes are merged afterwards with the same

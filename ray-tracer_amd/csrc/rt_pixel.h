@@ -77,6 +77,14 @@ struct rt_sky_args : rt_views_args {
 };
 __device__ __forceinline__ const rt_sky_args &px_sky(const rt_kernel_args &a) { return static_cast<const rt_sky_args &>(a); }
 
+/* The argument block of the traits variant (rt_traits_kernel, rt_render_kernel.h): the render kernel's, and the one mesh's place in the object
+ * list, which rt_render_kernel reads from the mesh table in LDS whenever a traversal ends.  Only under RT_TRAIT_ONE_MESH, and only
+ * rt_traits_kernel sets it: see px_budget. */
+struct rt_traits_args : rt_kernel_args {
+    int32_t mesh_obj;            /* -1: the scene has no mesh */
+};
+__device__ __forceinline__ const rt_traits_args &px_traits(const rt_kernel_args &a) { return static_cast<const rt_traits_args &>(a); }
+
 /* wave-uniform pixel chunk: linear pixel ids [next, end) of one 8x8 tile */
 struct Chunk {
     uint32_t next, end;
@@ -281,7 +289,9 @@ __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, co
 /* GENERAL_FUNCTIONS: Box-Muller through rt_logf / rt_cosf instead of their forms for a draw's arguments (again the same values): the hybrid
  * kernels (nodes in LDS, triangles from L2) are 2.8 % FASTER that way on the 6,000-triangle scene and indifferent on the 50,880-triangle one
  * (profiles/r04/experiments/box_muller_on_its_domain.txt) */
-template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false, bool VIEWS = false>
+/* PLAIN (RT_TRAIT_PLAIN_MATERIALS; rt_traits_kernel alone): no material of the scene needs texture coordinates, refracts or carries a texture,
+ * so the three regions that every hit would test for and skip are not compiled in; what is left is the same operations in the same order */
+template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false, bool VIEWS = false, bool PLAIN = false>
 __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const Frame &f, const Lds &L)
 {
     V3 &o = p.o, &d = p.d;
@@ -297,7 +307,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
         if (packed & 32u) {
             const v4f sc = L.objs[RT_OBJLDS_F4 * best_obj + 2];
             N = normalised(P - v3(sc.x, sc.y, sc.z));
-            if (packed & 16u) {
+            if (!PLAIN && (packed & 16u)) {
                 /* Sphere::assign_texture_coords src/objects.cu:82-97 (latitude / longitude) */
                 const float PI = 3.141592653589793f;
                 const float theta = rt_asinf((P.y - sc.y) / sc.w);
@@ -312,7 +322,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
             const v4f q2 = L.tris[3 * best_prim + 2];
             V3 n = v3(q2.y, q2.z, q2.w);
             N = (dot(n, d) > 0.0f) ? neg(n) : n;
-            if (packed & 16u) {
+            if (!PLAIN && (packed & 16u)) {
                 /* Triangle::assign_texture_coords src/objects.cu:160,196-199, called as (w,u,v) */
                 float t, u, v;
                 tri_test(L.tris, best_prim, o, d, t, u, v);
@@ -327,7 +337,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
          * back to reflect(); everything else reflects */
         bool do_reflect = true;
         V3 refr_dir = v3(0.f, 0.f, 0.f);
-        if (mtype == RT_DEV_MAT_REFRACTIVE) {
+        if (!PLAIN && mtype == RT_DEV_MAT_REFRACTIVE) {
             const float mat_n = L.objs[RT_OBJLDS_F4 * best_obj + 3].x;
             float n1, n2;
             V3 rn;
@@ -375,7 +385,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
         } else {
             V3 tc;
             const int tex = (int)((packed >> 2) & 3u);
-            if (tex == 0) {
+            if (PLAIN || tex == 0) {
                 tc = v3(ma.x, ma.y, ma.z);
             } else if (tex == 1) {
                 tc = v3(tex_u, tex_v, 0.f);                              /* gradient src/material.cu:80-82 */
@@ -547,7 +557,9 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
 }
 
 /* ================= GEN: jitter the direction, test the simple objects ====================== */
-template <bool HAS_MESH>
+/* TRAITS: see rt_closest_simple (rt_intersect.h).  With RT_TRAIT_ONE_MESH a ray leaves as M_SHADE and the caller tests the one mesh's root box
+ * at once (rt_render_loop.inc): there is no M_MESH and no mesh counter */
+template <bool HAS_MESH, int TRAITS = 0>
 __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds &L)
 {
     V3 &o = p.o, &d = p.d;
@@ -564,8 +576,10 @@ __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds
 
     float best_t;
     int best_obj, best_prim;
-    rt_closest_simple<true>(o, d, a.num_objects, L, best_t, best_obj, best_prim);
+    if (TRAITS & RT_TRAIT_SPHERES_ONLY) rt_closest_simple<true, TRAITS>(o, d, a.num_objects, L, best_t, best_obj, best_prim, (TRAITS & RT_TRAIT_ONE_MESH) ? px_traits(a).mesh_obj : -1);
+    else rt_closest_simple<true>(o, d, a.num_objects, L, best_t, best_obj, best_prim);
     p.best_t = best_t; p.best_obj = best_obj; p.best_prim = best_prim;
+    if (HAS_MESH && (TRAITS & RT_TRAIT_ONE_MESH)) { p.mode = M_SHADE; return; }
     p.next_mesh = 0;
     p.mode = (HAS_MESH && a.num_meshes > 0) ? M_MESH : M_SHADE;
 }

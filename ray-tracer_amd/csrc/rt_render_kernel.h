@@ -43,7 +43,25 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 #define RT_LOOP_BUDGET false
 #define RT_LOOP_VIEWS false
 #define RT_LOOP_SKY false
+#define RT_LOOP_TRAITS 0
 #include "rt_render_loop.inc"
+#undef RT_LOOP_TRAITS
+#undef RT_LOOP_SKY
+#undef RT_LOOP_VIEWS
+#undef RT_LOOP_BUDGET
+
+/* The traits variant: the render kernel for a scene whose commit has fixed what the generic kernel decides again per lane, ray and hit
+ * (RT_TRAIT_*, rt_device_scene.h): the same loop text with the traits of the shape's class switched on
+ * (rt_variant_traits; instantiated for the shapes that have any), the same launch bounds, the same frames bit for bit.  Stated in the kernel like rt_render_kernel's, not as a function.  A name of its own, so that every kernel there was
+ * keeps its symbol and its code (tools/compare_kernels.py). */
+template <int NT, bool HAS_MESH, int MODE>
+__global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES : RT_SMALL_WG_WAVES + 1)) void rt_traits_kernel(const rt_traits_args a)
+#define RT_LOOP_BUDGET false
+#define RT_LOOP_VIEWS false
+#define RT_LOOP_SKY false
+#define RT_LOOP_TRAITS rt_variant_traits(HAS_MESH, MODE, NT)
+#include "rt_render_loop.inc"
+#undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
@@ -57,7 +75,9 @@ __device__ __forceinline__ void rt_budget_loop(const rt_budget_args &a)
 #define RT_LOOP_BUDGET true
 #define RT_LOOP_VIEWS false
 #define RT_LOOP_SKY false
+#define RT_LOOP_TRAITS 0
 #include "rt_render_loop.inc"
+#undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
@@ -77,7 +97,9 @@ __device__ __forceinline__ void rt_views_loop(const rt_views_args &a)
 #define RT_LOOP_BUDGET false
 #define RT_LOOP_VIEWS true
 #define RT_LOOP_SKY false
+#define RT_LOOP_TRAITS 0
 #include "rt_render_loop.inc"
+#undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
@@ -96,7 +118,9 @@ __device__ __forceinline__ void rt_sky_loop(const rt_sky_args &a)
 #define RT_LOOP_BUDGET false
 #define RT_LOOP_VIEWS true
 #define RT_LOOP_SKY true
+#define RT_LOOP_TRAITS 0
 #include "rt_render_loop.inc"
+#undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
@@ -108,12 +132,12 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 }
 
 /* ---- launchers (rt_launch.h; the sky variant's: rt_sky.h) -------------------------------------------------------------- */
-template <int NT, bool HAS_MESH, int MODE>
+template <int NT, class Args, void (*KERNEL)(Args)>
 static int rt_blocks_one(size_t lds_bytes)
 {
     int n = 0;
-    (void)hipFuncSetAttribute((const void *)rt_render_kernel<NT, HAS_MESH, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)rt_render_kernel<NT, HAS_MESH, MODE>, NT, lds_bytes) != hipSuccess) n = 0;
+    (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)KERNEL, NT, lds_bytes) != hipSuccess) n = 0;
     return n;
 }
 
@@ -125,36 +149,63 @@ static void rt_launch_one(const Args *args, int blocks, size_t lds_bytes, hipStr
     hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(NT), lds_bytes, stream, *args);
 }
 
+/* rt_traits_kernel's probe and launcher of a shape, or null where the shape has no traits kernel (and none is instantiated) */
+template <int NT, bool HAS_MESH, int MODE, bool BUILT = rt_variant_traits(HAS_MESH, MODE, NT) != 0>
+struct rt_traits_fns {
+    static constexpr int (*blocks)(size_t) = rt_blocks_one<NT, rt_traits_args, rt_traits_kernel<NT, HAS_MESH, MODE>>;
+    static constexpr void (*launch)(const rt_traits_args *, int, size_t, hipStream_t) = rt_launch_one<NT, rt_traits_args, rt_traits_kernel<NT, HAS_MESH, MODE>>;
+};
+template <int NT, bool HAS_MESH, int MODE>
+struct rt_traits_fns<NT, HAS_MESH, MODE, false> {
+    static constexpr int (*blocks)(size_t) = nullptr;
+    static constexpr void (*launch)(const rt_traits_args *, int, size_t, hipStream_t) = nullptr;
+};
+
 /* the occupancy probe and the launcher of every built shape, in RT_SHAPES' order: the kernel is instantiated from that list alone */
 struct rt_shape_fns {
     int (*blocks)(size_t lds_bytes);
     void (*launch)(const rt_kernel_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
+    int (*blocks_traits)(size_t lds_bytes);
+    void (*launch_traits)(const rt_traits_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
     void (*launch_budget)(const rt_budget_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
     void (*launch_views)(const rt_views_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
     void (*launch_sky)(const rt_sky_args *args, int blocks, size_t lds_bytes, hipStream_t stream);
 };
 template <size_t... I> static constexpr std::array<rt_shape_fns, sizeof...(I)> rt_shape_fns_of(std::index_sequence<I...>)
 {
-    return {{{rt_blocks_one<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>,
+    return {{{rt_blocks_one<RT_SHAPES[I].threads, rt_kernel_args, rt_render_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
               rt_launch_one<RT_SHAPES[I].threads, rt_kernel_args, rt_render_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
+              rt_traits_fns<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>::blocks,
+              rt_traits_fns<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>::launch,
               rt_launch_one<RT_SHAPES[I].threads, rt_budget_args, rt_budget_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
               rt_launch_one<RT_SHAPES[I].threads, rt_views_args, rt_views_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>,
               rt_launch_one<RT_SHAPES[I].threads, rt_sky_args, rt_sky_kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>>}...}};
 }
 static constexpr auto rt_shape_table = rt_shape_fns_of(std::make_index_sequence<std::size(RT_SHAPES)>());
 
-/* workgroups of this shape of rt_render_kernel that are resident on one CU (registers, LDS, wave slots), as the
- * runtime reports it; 0 if the shape is not built */
+/* workgroups of this shape of rt_render_kernel (shape.variant: of rt_traits_kernel) that are resident on one CU (registers, LDS, wave
+ * slots), as the runtime reports it; 0 if the shape is not built */
 extern "C" int rt_kernel_blocks_per_cu(rt_shape shape, size_t lds_bytes)
 {
     const int i = rt_shape_index(shape);
-    return i < 0 ? 0 : rt_shape_table[i].blocks(lds_bytes);
+    if (i < 0) return 0;
+    return shape.variant == RT_VARIANT_TRAITS_KERNEL && rt_shape_table[i].blocks_traits ? rt_shape_table[i].blocks_traits(lds_bytes) : rt_shape_table[i].blocks(lds_bytes);
 }
 
 extern "C" hipError_t rt_launch_render(const rt_kernel_args *args, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream)
 {
     const int i = rt_shape_index(shape);
     if (i < 0) return hipErrorInvalidValue;
+    if (shape.variant == RT_VARIANT_TRAITS_KERNEL) {
+        /* the scene has the traits and the shape a traits kernel (rt_sched::choose_variant decided at commit): every caller of this launcher
+         * gets it through the shape it hands over.  A missing kernel is an error, not a reason to run the other one */
+        if (!rt_shape_table[i].launch_traits) return hipErrorInvalidValue;
+        rt_traits_args t;
+        static_cast<rt_kernel_args &>(t) = *args;
+        t.mesh_obj = shape.mesh_obj;
+        rt_shape_table[i].launch_traits(&t, blocks, lds_bytes, stream);
+        return hipGetLastError();
+    }
     rt_shape_table[i].launch(args, blocks, lds_bytes, stream);
     return hipGetLastError();
 }

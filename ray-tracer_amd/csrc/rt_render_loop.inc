@@ -2,13 +2,16 @@
  * rt_render_loop.inc — the body of the render kernel: included by rt_render_kernel.h once per kernel that runs the wave loop, behind the
  * head of what runs it (template <int NT, bool HAS_MESH, int MODE> ... (ARGS a)), with RT_LOOP_BUDGET defined as false (rt_render_kernel,
  * rt_views_loop, rt_sky_loop) or true (rt_budget_loop), RT_LOOP_VIEWS as true (rt_views_loop, rt_sky_loop: a camera per frame of the launch) or
- * false and RT_LOOP_SKY as true (rt_sky_loop: a miss looks the sky up in a cube map) or false.  Text, not a function: called as a function the loop compiles to other code in all thirteen render
+ * false, RT_LOOP_SKY as true (rt_sky_loop: a miss looks the sky up in a cube map) or false and RT_LOOP_TRAITS as the scene traits the kernel is
+ * compiled for (rt_traits_kernel: rt_variant_traits of its shape) or 0.  Text, not a function: called as a function the loop compiles to other code in all thirteen render
  * kernels, and the render kernel's code is kept byte for byte.
  */
 {
     constexpr bool BUDGET = RT_LOOP_BUDGET;
     constexpr bool VIEWS = RT_LOOP_VIEWS;
     constexpr bool SKY = RT_LOOP_SKY;
+    constexpr int TRAITS = RT_LOOP_TRAITS;      /* RT_TRAIT_* the scene is known to have (rt_traits_kernel; `a` is then an rt_traits_args), 0 everywhere else */
+    constexpr bool ONE_MESH = HAS_MESH && (TRAITS & RT_TRAIT_ONE_MESH) != 0;
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
     const int lane = tid & (RT_WAVE - 1);
@@ -78,7 +81,7 @@
             if (RT_ROUND_SHADES(a, HAS_MESH, n_hit, n_trav, others)) {
                 if (p.mode == M_SHADE) {
                     RT_STAT(ST_SHADE);
-                    px_shade<!(NT == 1024 && HAS_MESH), MODE == RT_SCENE_HYBRID, BUDGET, VIEWS>(p, a, f, L);
+                    px_shade<!(NT == 1024 && HAS_MESH), MODE == RT_SCENE_HYBRID, BUDGET, VIEWS, (TRAITS & RT_TRAIT_PLAIN_MATERIALS) != 0>(p, a, f, L);
                 }
             }
         }
@@ -95,13 +98,31 @@
         RT_LAP(TM_FETCH);
         if (p.mode == M_GEN) {
             RT_STAT(ST_GEN);
-            px_gen<HAS_MESH>(p, a, L);
+            px_gen<HAS_MESH, TRAITS>(p, a, L);
+            if (ONE_MESH) {
+                /* the one mesh's root box, tested here and once: the MESH section's trip below with next_mesh == 0, and none after it (the
+                 * ray came out of px_gen as M_SHADE, which it stays unless it enters the box) */
+                RT_STAT(ST_MESH);
+                const v4f m0 = L.meshes[0], m1 = L.meshes[1];
+                if (!(p.d.x != p.d.x || p.d.y != p.d.y || p.d.z != p.d.z)) {
+                    const uint32_t root_ref = __float_as_uint(m1.z);
+                    float rd;
+                    const bool rh = box_test(m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, p.o, p.inv, rd);
+                    if (!(!rh || rd > RT_INF_F || ((root_ref & RT_REF_CHAIN) && !(rd < RT_INF_F)))) {
+                        cur = root_ref; sp = 0; w_best = RT_INF_F; w_prim = -1;
+                        w_zero_dir = (p.d.x == 0.0f || p.d.y == 0.0f || p.d.z == 0.0f) ? 1u : 0u;
+                        p.mode = M_WAIT;
+                        p.frame_steps |= 0x80000000u;
+                        RT_STAT(ST_MESH_START);
+                    }
+                }
+            }
         }
         RT_LAP(TM_GEN);
 
         if (HAS_MESH) {
             /* ================= MESH: find the next mesh whose root box the ray enters ======= */
-            while (p.mode == M_MESH) {
+            while (!ONE_MESH && p.mode == M_MESH) {
                 RT_STAT(ST_MESH);
                 if (p.next_mesh >= a.num_meshes) { p.mode = M_SHADE; break; }
                 const v4f m0 = L.meshes[2 * p.next_mesh], m1 = L.meshes[2 * p.next_mesh + 1];
@@ -194,11 +215,11 @@
                             RT_STAT(ST_DONE_MESH);
                             /* this mesh is done: merge (smaller distance, or equal and later in the list);
                              * its place in the object list is read again here rather than kept in a register */
-                            const int w_obj = (int)__float_as_uint(L.meshes[2 * (p.next_mesh - 1) + 1].w);
+                            const int w_obj = ONE_MESH ? px_traits(a).mesh_obj : (int)__float_as_uint(L.meshes[2 * (p.next_mesh - 1) + 1].w);
                             if (w_prim >= 0 && (w_best < p.best_t || (w_best == p.best_t && w_obj > p.best_obj))) {
                                 p.best_t = w_best; p.best_obj = w_obj; p.best_prim = w_prim;
                             }
-                            p.mode = p.next_mesh >= a.num_meshes ? M_SHADE : M_MESH;
+                            p.mode = ONE_MESH || p.next_mesh >= a.num_meshes ? M_SHADE : M_MESH;
                         }
                     }
                 }

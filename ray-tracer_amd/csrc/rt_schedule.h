@@ -366,6 +366,28 @@ inline int render_descend_keep(const Knobs &k, const rt_shape &shape)
     return shape.has_mesh && shape.mode == RT_SCENE_LDS && rt_descend_pops(shape.threads, shape.mode) ? RT_DEF_DESCEND_KEEP_POP_LDS : k.descend_keep;
 }
 
+/* Which of a shape's two render kernels a scene of these traits (RT_TRAIT_*) runs: rt_traits_kernel if it has all three, else
+ * rt_render_kernel.  force_generic (RT_AMD_KERNEL_VARIANT=generic, the A side of an A/B and of the tests) keeps rt_render_kernel.  Next to the
+ * shape and not part of it: both kernels of a shape have its launch bounds and its LDS.  This form depends on the scene alone (what
+ * rt_debug_flatten reports without a device) ... */
+inline int choose_variant(uint32_t traits, bool force_generic)
+{
+    return !force_generic && (traits & RT_TRAITS_ALL) == RT_TRAITS_ALL ? RT_VARIANT_TRAITS_KERNEL : RT_VARIANT_GENERIC;
+}
+/* ... and on the shape chosen for it: a shape without a traits kernel (rt_variant_traits: the hybrid and the global ones) keeps rt_render_kernel */
+inline int choose_variant(uint32_t traits, bool force_generic, const rt_shape &shape)
+{
+    return rt_variant_traits(shape.has_mesh, shape.mode, shape.threads) != 0 ? choose_variant(traits, force_generic) : RT_VARIANT_GENERIC;
+}
+/* the value of RT_AMD_KERNEL_VARIANT (may be NULL): "generic" forces rt_render_kernel, anything else leaves the choice to the traits */
+inline bool variant_forced_generic(const char *env)
+{
+    const char *g = "generic";
+    if (!env) return false;
+    while (*g && *env == *g) { env++; g++; }
+    return *g == 0 && *env == 0;
+}
+
 /* rt_partition_tiles' owner table dealt out per rank: its tiles (ascending image indices) and, with cost and peak
  * (indexed by image tile), their costs and peaks; without them the rank's costs and peaks stay empty */
 inline void deal_tiles(const std::vector<int32_t> &owner, int n_ranks, const uint32_t *cost, const uint32_t *peak, std::vector<std::vector<uint32_t>> &lists,

@@ -214,5 +214,7 @@ extern "C" rt_status rt_debug_scene_read(rt_ctx *ctx, rt_scene *scene, rt_flat_v
     out->num_triangles = f.num_tris;
     out->num_nodes = f.num_nodes;
     out->has_mesh = f.has_mesh ? 1 : 0;
+    out->traits = (int32_t)f.traits;
+    out->kernel_variant = scene->kernel.shape.variant;      /* (what the committed scene runs, as rt_scene_get_info reports it) */
     return RT_OK;
 }

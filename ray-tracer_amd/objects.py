@@ -5,7 +5,7 @@ import os
 import numpy as np
 
 from . import scenes
-from ._abi import (RT_ERR_BUSY, RT_ERR_INVALID, RT_ERR_IO, RT_ERR_NO_DEVICE, RT_ERR_UNSUPPORTED, RT_OK, PipelineFullError, RayTracerError,
+from ._abi import (KERNEL_VARIANTS, SCENE_TRAITS, RT_ERR_BUSY, RT_ERR_INVALID, RT_ERR_IO, RT_ERR_NO_DEVICE, RT_ERR_UNSUPPORTED, RT_OK, PipelineFullError, RayTracerError,
                    UnsupportedMeshError, _fp, lib, rt_camera, rt_flat_view, rt_material, rt_render_settings, rt_scene_info)
 
 
@@ -169,7 +169,8 @@ def _flat_view_arrays(v):
     return {"blob": blob, "off_nodes": v.off_nodes, "off_tris": v.off_tris, "off_objlds": v.off_objlds,
             "off_meshes": v.off_meshes, "num_meshes": v.num_meshes, "stack_entries": v.stack_entries,
             "objects": objs, "tri_uv": uv, "num_triangles": v.num_triangles, "num_nodes": v.num_nodes,
-            "has_mesh": bool(v.has_mesh)}
+            "has_mesh": bool(v.has_mesh),
+            "traits": {name for name, bit in SCENE_TRAITS.items() if v.traits & bit}, "kernel_variant": KERNEL_VARIANTS[v.kernel_variant]}
 
 
 class SceneObjects(_Handle):
@@ -393,4 +394,6 @@ class Scene(_Handle):
     def info(self):
         i = rt_scene_info()
         self.ctx._check(lib().rt_scene_get_info(self._h, C.byref(i)))
-        return {n: getattr(i, n) for n, _ in i._fields_}
+        out = {n: getattr(i, n) for n, _ in i._fields_}
+        out["kernel_variant"] = KERNEL_VARIANTS[i.kernel_variant]      # "generic" or "traits": which render kernel the scene's plain frames run
+        return out

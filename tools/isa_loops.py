@@ -1,16 +1,18 @@
 """Instruction counts of the render kernel's hot loops, from the compiler's assembly (development tool, CPU only):
    python tools/isa_loops.py [-DFLAG ...]      prints, for rt_render_kernel<1024,true,1>, the basic-block span of the descend loop
    (the one holding the stack's ds_write_b64) and of the leaf loop (the one holding v_div_fixup), by instruction class.
-   --budget: the same for rt_budget_kernel<1024,true,1>, the budget variant of that shape."""
+   --budget: the same for rt_budget_kernel<1024,true,1>, the budget variant of that shape; --traits: for rt_traits_kernel<1024,true,1>."""
 import os, re, subprocess, sys, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-flags = [a for a in sys.argv[1:] if a.startswith("-") and a not in ("-v", "--budget")]
+flags = [a for a in sys.argv[1:] if a.startswith("-") and a not in ("-v", "--budget", "--traits")]
 out = "/tmp/isa/rk_%s.s" % (re.sub(r"[^A-Za-z0-9]+", "_", "".join(flags)) or "base")
 os.makedirs("/tmp/isa", exist_ok=True)
 subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
                        "-S", "--cuda-device-only", os.path.join(ROOT, "ray-tracer_amd", "csrc", "rt_kernel.hip"), "-o", out] + flags, stderr=subprocess.DEVNULL)
 txt = open(out).read()
 name = "_Z16rt_budget_kernelILi1024ELb1ELi1EEv14rt_budget_args" if "--budget" in sys.argv else "_Z16rt_render_kernelILi1024ELb1ELi1EEv14rt_kernel_args"
+if "--traits" in sys.argv:
+    name = "_Z16rt_traits_kernelILi1024ELb1ELi1EEv14rt_traits_args"
 body = txt[txt.index(name + ":"):]
 body = body[:body.index("s_endpgm")]
 lines = [l for l in body.splitlines() if l.strip() and not l.strip().startswith(";")]
