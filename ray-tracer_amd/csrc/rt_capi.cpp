@@ -27,6 +27,12 @@
 
 #include "rt_internal.h"
 
+/* The pre-pass's launcher is referenced weakly: the host programs that link this file without rt_kernel.hip (tests/sanitize/: some of them
+ * create contexts over a stand-in for the HIP runtime) go on linking without a stub for it, and render without a plane.  In the library the
+ * kernel is always there: rt_debug_primary_cull_linked says so and tests/test_primary_cull.py holds every build to it, so that a library which
+ * lost the kernel fails a CPU test instead of quietly rendering every launch without a plane */
+#pragma weak rt_cull_enqueue
+
 std::mutex rt_detail::g_ctx_mutex;
 
 namespace {
@@ -166,6 +172,7 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     for (const rt_sched::KnobRange &r : rt_sched::KNOB_RANGES) k.*r.field = env_int(r.env, r.lo, r.hi, k.*r.field);
     k.descend_keep_given = env_int("RT_AMD_DESCEND_KEEP", 0, 64, -1) >= 0;      /* (an explicit value replaces the per-shape default: rt_sched::render_descend_keep) */
     ctx->multi.careful = env_int("RT_AMD_MULTI_CAREFUL", INT_MIN, INT_MAX, 0) != 0;
+    ctx->cull.enabled = env_int("RT_AMD_PRIMARY_CULL", 0, 1, 1) != 0;
     if (ctx->tile_counter.grow(256) != hipSuccess ||
         hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
         delete ctx;
@@ -668,6 +675,48 @@ static rt_status bind_output(rt_ctx *ctx, rt_kernel_args &a, const rt_sched::Lay
     return RT_OK;
 }
 
+/* The view's cull plane for the launch `a` (rt_cull.h): reused if it was computed for this scene revision, camera, image size and antialias
+ * flag, else computed now by the pre-pass on the launch's stream - no host wait, the render kernel is the next kernel on that stream.  A
+ * scene's uid changes with every update of its geometry (rt_update_capi.cpp), so a commit and an update both find the plane stale.  Nothing
+ * here fails the launch: without an allocation, a launcher or an event the launch renders without a plane, which costs time and nothing else.
+ * Only a scene whose kernel reads the plane gets one (rt_loop_culls). */
+static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const rt_render_settings *rs, rt_kernel_args &a, FrameSlot *slot, hipStream_t stream)
+{
+    CullPlane &cp = ctx->cull;
+    const rt_shape &sh = scene->kernel.shape;
+    const bool enabled = cp.enabled && rt_cull_enqueue != nullptr && scene->flat.num_meshes > 0 && rt_loop_culls(sh.has_mesh, sh.mode, sh.threads, sh.variant);
+    rt_cull_host::Key k;
+    k.scene_uid = scene->uid;
+    camera_floats(*cam, k.cam);
+    k.width = cam->width; k.height = cam->height; k.antialias = rs->antialias ? 1 : 0;
+    const rt_cull_host::Step step = cp.plan.next(k, enabled, [&](size_t words) {
+        /* (the old plane is freed first, which waits for the launches that read it) */
+        const bool ok = cp.d.grow(words) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        return ok;
+    });
+    if (step == rt_cull_host::Step::none) return;
+    bool ok = true;
+    if (step == rt_cull_host::Step::run) {
+        /* the plane is rewritten: ordinary launches are already behind every launch that read it (render_frames); a pipelined frame
+         * overlaps the others in flight, whose render kernels are waited for here - once per view */
+        if (slot)
+            for (FrameSlot &fs : ctx->pipe.slots)
+                if (fs.used && &fs != slot) ok = ok && hipEventSynchronize(fs.ev_done) == hipSuccess;
+        if (ok && !cp.ev.e) ok = hipEventCreateWithFlags(&cp.ev.e, hipEventDisableTiming) == hipSuccess;
+        ok = ok && rt_cull_enqueue(k.cam, k.width, k.height, k.antialias, scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
+                                   scene->flat.num_meshes, cp.d.p, stream) == hipSuccess;
+        ok = ok && hipEventRecord(cp.ev, stream) == hipSuccess;
+        cp.stream = stream;
+        cp.plan.ran(k, ok);
+    } else if (cp.stream != stream) {
+        ok = hipStreamWaitEvent(stream, cp.ev, 0) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return; }
+    rt_kernel_args_set_cull(a, cp.d.p);
+    cp.plan.used_last = true;
+}
+
 static rt_status launch(rt_ctx *ctx, const rt_scene *scene, const rt_kernel_args &a, bool pipelined, hipStream_t stream)
 {
     int blocks = launch_blocks(ctx, scene, a.num_tiles);
@@ -710,6 +759,7 @@ rt_status rt_detail::render_frames(rt_ctx *ctx, const rt_scene *scene, const rt_
     bool collecting = false;
     if (a.num_tiles > 0 && (st = prepare_view(ctx, scene, cam, rs, t, a, L.plane_floats(), in_place, slot, stream, &collecting)) != RT_OK) return st;
     if ((st = bind_output(ctx, a, L, in_place, slot)) != RT_OK) return st;
+    if (a.num_tiles > 0) bind_cull(ctx, scene, cam, rs, a, slot, stream);
     if (!slot) {
         RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");
         ctx->have_timing = false;
@@ -830,6 +880,66 @@ extern "C" rt_status rt_debug_read_stats(rt_ctx *ctx, unsigned long long *out48)
     if (!ctx || !out48) return RT_ERR_INVALID;
     RT_HIP(ctx, hipDeviceSynchronize(), "waiting for render kernel");
     RT_HIP(ctx, hipMemcpy(out48, ctx->tile_counter.p + 16, 48 * 8, hipMemcpyDeviceToHost), "reading stats");
+    return RT_OK;
+}
+
+/* test hook: the cull plane the last render launch of the context was handed, read back (waits for the device).  info4 = {1 if that launch
+ * was handed a plane else 0, the plane's image width, its height, its words}; with words == NULL or too small a capacity only info4 is written */
+extern "C" rt_status rt_debug_primary_cull(rt_ctx *ctx, uint32_t *words, int32_t capacity_words, int32_t *info4)
+{
+    if (!ctx || !info4 || capacity_words < 0) return set_err(ctx, RT_ERR_INVALID, "bad argument");
+    const CullPlane &cp = ctx->cull;
+    const bool have = cp.plan.valid && cp.plan.used_last && cp.d.p;
+    const size_t n = have ? rt_cull_words(cp.plan.key.width, cp.plan.key.height) : 0;
+    info4[0] = have ? 1 : 0;
+    info4[1] = have ? cp.plan.key.width : 0;
+    info4[2] = have ? cp.plan.key.height : 0;
+    info4[3] = (int32_t)n;
+    if (!have || !words || (size_t)capacity_words < n) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
+    RT_HIP(ctx, hipMemcpy(words, cp.d.p, n * 4, hipMemcpyDeviceToHost), "reading the cull plane");
+    return RT_OK;
+}
+
+extern "C" int32_t rt_debug_primary_cull_linked(void) { return rt_cull_enqueue != nullptr ? 1 : 0; }
+
+/* test / development hook, host only (no device is touched): the predicate of rt_cull.h evaluated per pixel of `cam`'s image on a flattened
+ * scene (rt_debug_flatten's view, or rt_debug_scene_read's).  words: rt_cull_words-many, or NULL.  stats6, or NULL: {pixels whose cone may
+ * enter some mesh's root box, those of them that are flagged, nodes the centre direction's walk visits in flagged pixels, ... in all
+ * root-entering pixels, pixels flagged in all, words of the plane} - what tools/primary_cull_estimate.py prints. */
+extern "C" rt_status rt_debug_primary_cull_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats6)
+{
+    if (!view || !cam || !view->blob || cam->width <= 0 || cam->height <= 0 || (int64_t)cam->width * cam->height > (1 << 28)) return RT_ERR_INVALID;
+    float c12[12];
+    camera_floats(*cam, c12);
+    const size_t n_words = rt_cull_words(cam->width, cam->height);
+    if (words) std::memset(words, 0, n_words * 4);
+    int64_t st[6] = {0, 0, 0, 0, 0, (int64_t)n_words};
+    for (int py = 0; py < cam->height; py++)
+        for (int px = 0; px < cam->width; px++) {
+            float P[3];
+            rt_cull_primary(c12, px, py, P);
+            const rt_cull_cone cone = rt_cull_cone_of(P, c12, antialias);
+            const bool flagged = rt_cull_no_leaf(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, view->num_meshes, rt_cull_local_stack());
+            const size_t pixel = (size_t)py * (size_t)cam->width + (size_t)px;
+            if (flagged && words) words[pixel >> 5] |= 1u << (pixel & 31);
+            st[4] += flagged;
+            bool enters = false;
+            for (int32_t m = 0; m < view->num_meshes && !enters; m++) {
+                const float *m0 = view->blob + 4 * ((size_t)view->off_meshes + 2 * (size_t)m);
+                enters = !rt_cull_box_missed(cone, m0[0], m0[1], m0[2], m0[3], m0[4], m0[5]);
+            }
+            if (!enters) continue;
+            /* what the pixel's centre ray walks: the single direction P, every node whose box it may enter */
+            int32_t steps = 0;
+            (void)rt_cull_no_leaf(rt_cull_cone_of(P, c12, 0), view->blob, view->off_nodes, view->num_nodes, view->off_meshes, view->num_meshes, rt_cull_local_stack(), &steps, false);
+            st[0]++;
+            st[1] += flagged;
+            st[2] += flagged ? steps : 0;
+            st[3] += steps;
+        }
+    if (stats6) std::memcpy(stats6, st, sizeof st);
     return RT_OK;
 }
 

@@ -29,6 +29,7 @@
 #ifndef RT_DEVICE_SCENE_H
 #define RT_DEVICE_SCENE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #define RT_BVH_DEPTH 10              /* reference src/objects.cu:786 */
@@ -221,8 +222,12 @@ typedef struct {
     const uint32_t *tile_list;     /* or NULL (bands): local tile t is the image's tile tile_list[t] = ty * tiles_x + tx; with `compact`
                                       the output holds the listed tiles back to back, 64 pixels each, row-major inside a tile */
     uint32_t tile_stride;          /* ticket t renders tile (t * tile_stride) % num_tiles; coprime to num_tiles */
+    uint32_t cull_lo;              /* the primary-ray cull's bit plane (rt_cull.h), or NULL: the address's low half here and its high half in cull_hi.
+                                      The two words fill what were alignment holes in front of a pointer, so that no other field moves and every
+                                      kernel that does not read the plane keeps its code byte for byte (rt_kernel_args_cull / rt_kernel_args_set_cull) */
     const uint32_t *tile_order;    /* or, if not NULL, tile tile_order[t] (expensive-looking tiles first) */
     int32_t num_heavy_tiles;       /* multi-frame launches: this many leading entries of tile_order go first for ALL frames */
+    uint32_t cull_hi;              /* (see cull_lo) */
     const uint32_t *job_order;     /* or, if not NULL, the whole schedule of a multi-frame launch: ticket t renders tile
                                       (job_order[t] & RT_JOB_TILE_MASK) of frame (job_order[t] >> RT_JOB_FRAME_SHIFT) */
     /* scene */
@@ -251,6 +256,19 @@ typedef struct {
     unsigned long long *stats;     /* development builds only (-DRT_STATS): section counters */
 } rt_kernel_args;
 
+static_assert(offsetof(rt_kernel_args, cull_lo) + 4 == offsetof(rt_kernel_args, tile_order) && offsetof(rt_kernel_args, cull_hi) + 4 == offsetof(rt_kernel_args, job_order),
+              "cull_lo / cull_hi sit in the alignment holes in front of tile_order and job_order: no field of the block moves for them");
+/* Which render kernels read the primary-ray cull's plane (rt_cull.h; RT_LOOP_CULL of rt_render_loop.inc), decided by measurement per shape
+ * (DESIGN.md section 24): rt_traits_kernel<1024, true, RT_SCENE_LDS> with the ONE_MESH trait (monkey: -3.4 %), and no other.  The generic
+ * kernel's form of it (a flagged primary ray leaving px_gen as M_SHADE instead of M_MESH) was measured in rt_render_kernel of the same shape on
+ * reference scene 0, lost 0.5 %, and is not built: nothing of it is in the tree.  The smaller workgroups and the hybrid and global shapes were
+ * not measured with it and keep their code; the budget, views and sky loops never read it. */
+constexpr bool rt_loop_culls(int has_mesh, int mode, int threads, int variant)
+{
+    return has_mesh && mode == RT_SCENE_LDS && threads == 1024 && variant == RT_VARIANT_TRAITS_KERNEL &&
+           (rt_variant_traits(has_mesh, mode, threads) & RT_TRAIT_ONE_MESH) != 0;
+}
+
 /* ---- the two conditions the render kernel's wave loop makes progress by, stated once -------------------------------------------------
  * rt_render_kernel (rt_render_kernel.h) uses them on its argument block, tests/sanitize/capi_host_fuzz.cpp (check_progress) on
  * rt_sched::KernelKnobs, which carries the same field names: it tries them on every wave state for every knob value the library accepts;
@@ -261,6 +279,13 @@ typedef struct {
 #else
 #define RT_SCENE_HD inline
 #endif
+/* the plane of a block (NULL: none) and its setter */
+RT_SCENE_HD const uint32_t *rt_kernel_args_cull(const rt_kernel_args &a) { return (const uint32_t *)(uintptr_t)(((uint64_t)a.cull_hi << 32) | (uint64_t)a.cull_lo); }
+RT_SCENE_HD void rt_kernel_args_set_cull(rt_kernel_args &a, const uint32_t *plane)
+{
+    a.cull_lo = (uint32_t)(uintptr_t)plane;
+    a.cull_hi = (uint32_t)((uint64_t)(uintptr_t)plane >> 32);
+}
 /* the traversal loop leaves (n_active > 0): lanes holding a hit wait for a batch of `hit_break`; the cheap kinds of ready lane (generate,
  * fetch, next mesh, a miss) for one of `ready_break`; or a smaller batch of hits that, together with the cheap-work lanes, is worth the round */
 template <class K> RT_SCENE_HD bool rt_traversal_yields(const K &a, int n_hit, int n_active, int n_light)

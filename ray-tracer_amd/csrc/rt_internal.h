@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_cull.h"           /* the primary-ray cull: its plane's bookkeeping, and its pre-pass's launcher (apart from rt_launch.h's, like rt_sky.h's) */
 #include "rt_host.h"
 #include "rt_launch.h"         /* the kernel launchers: the seam to rt_kernel.hip */
 #include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
@@ -165,6 +166,17 @@ struct ViewsState {
     bool uploaded = false;               /* ev_up has been recorded */
 };
 
+/* The primary-ray cull's bit plane of the current view (rt_cull.h), beside the view's tile costs: one bit per pixel of the full image, written by
+ * the pre-pass on the stream of the launch that found the view new and read by every render launch of the view after it - tile lists, bands
+ * and batches alike.  `plan` says what a launch does (rt_cull_host::Plan); ev / stream order a reader on another stream behind the pre-pass. */
+struct CullPlane {
+    DevBuf<uint32_t> d;
+    rt_cull_host::Plan plan;
+    Event ev;                            /* recorded behind the pre-pass */
+    hipStream_t stream = nullptr;        /* ... on this stream (the caller's: not owned) */
+    bool enabled = true;                 /* RT_AMD_PRIMARY_CULL=0: every launch renders without the plane */
+};
+
 /* knobs (RT_AMD_*), none changes an image: rt_schedule.h has them, their accepted ranges and what the kernel is handed for them
  * (rt_sched::kernel_knobs; RT_AMD_HIT_LOW is clamped to RT_AMD_HIT_BREAK there) */
 using rt_sched::Knobs;
@@ -218,6 +230,7 @@ struct rt_ctx {
     DevBuf<float> d_prev, d_out;
     View view;
     DevBuf<float> d_partial;             /* multi-frame launches: one plane of per-pixel frame means per frame; the pilot's scratch plane */
+    CullPlane cull;
     TileListCache tile_lists;
     Knobs knobs;
     /* the host-buffer forms of the ray queries and the AOV pass (rt_query_capi.cpp): the rays on the device, and the records / planes */

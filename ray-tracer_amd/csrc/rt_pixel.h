@@ -20,6 +20,8 @@
 #include "rt_traverse.h"
 #include "rt_vec.h"
 
+#define PX_NOCULL 0x80000000u         /* Px::id in the kernels that read the cull plane (rt_loop_culls): the pixel is NOT flagged by it */
+
 /* per-lane pixel state (registers) */
 struct Px {
     int mode;
@@ -170,7 +172,8 @@ __device__ __forceinline__ void px_finish_budget(Px &p, const rt_kernel_args &a,
  * (plain stores, no ordering between frames needed), and a small kernel launched behind this one
  * (rt_blend_kernel) folds the planes into the frame buffer in frame order; NaN pixels are made the one
  * canonical quiet NaN there (any NaN plane value makes the blended value a NaN). */
-template <bool BUDGET = false, bool VIEWS = false>
+/* CULL (rt_loop_culls): bit 31 of p.id is not part of the pixel's id (px_fetch keeps the pixel's cull bit there) */
+template <bool BUDGET = false, bool VIEWS = false, bool CULL = false>
 __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     if (BUDGET) { px_finish_budget(p, a, f); return; }
@@ -188,12 +191,13 @@ __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, 
         return;
     }
     const V3 c = p.colour / (float)f.spp;
-    const int tile = (int)(p.id >> 6), within = (int)(p.id & 63u);
+    const unsigned id = CULL ? p.id & ~PX_NOCULL : p.id;
+    const int tile = (int)(id >> 6), within = (int)(id & 63u);
     int tx, ty, compact_row;
     tile_place(a, f, tile, tx, ty, compact_row);
     const int px = tx * 8 + (within & 7), py = ty * 8 + (within >> 3);
     size_t pixel = (size_t)py * (size_t)f.W + (size_t)px;
-    if (a.compact) pixel = a.tile_list ? (size_t)p.id : (size_t)(compact_row + (within >> 3)) * (size_t)f.W + (size_t)px;
+    if (a.compact) pixel = a.tile_list ? (size_t)id : (size_t)(compact_row + (within >> 3)) * (size_t)f.W + (size_t)px;
     /* (first launch of a view) what this pixel cost, charged to its tile */
     if (a.tile_cost && (p.frame_steps & (unsigned)(RT_MAX_BATCH_FRAMES - 1)) == 0u) {
         /* (frame 0 of the launch only: the figures describe the view, not the launch, and a 32-frame sum could wrap)
@@ -227,7 +231,7 @@ __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, 
 
 /* the end of a sample (src/raytracer.cu:102-105): add it to the pixel, restart from a copy of the
  * primary ray; after the last sample the pixel is finished */
-template <bool BUDGET = false, bool VIEWS = false>
+template <bool BUDGET = false, bool VIEWS = false, bool CULL = false>
 __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     p.colour = p.colour + p.fin;
@@ -253,7 +257,7 @@ __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, co
     p.sample++;
     p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
     p.o = f.cam_pos; p.d = p.primary; p.bounce = 0; p.cur_n = 1.0f;
-    if (p.sample >= f.spp) px_finish_pixel(p, a, f);
+    if (p.sample >= f.spp) px_finish_pixel<false, false, CULL>(p, a, f);
 }
 
 /* ================= SHADE, a ray that hit nothing (src/raytracer.cu:76-80): sky, end of sample == */
@@ -261,7 +265,7 @@ __device__ __forceinline__ void px_end_sample(Px &p, const rt_kernel_args &a, co
  * constant, which becomes the map's tint.  One load from global memory per sample, at an address that differs across the lanes; it is issued
  * at the end of a path, where nothing else of the lane is in flight, and the wave's other lanes wait for it with this one - the SIMD's other
  * waves cover it (DESIGN.md section 22 has what it costs).  The map is not staged into LDS: the scene's shape would change with it. */
-template <bool BUDGET = false, bool VIEWS = false, bool SKY = false>
+template <bool BUDGET = false, bool VIEWS = false, bool SKY = false, bool CULL = false>
 __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, const Frame &f)
 {
     if (SKY) {
@@ -280,7 +284,7 @@ __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, co
     }
     p.fin = p.fin + f.sky * p.thr;
     p.mode = M_GEN;
-    px_end_sample<BUDGET, VIEWS>(p, a, f);
+    px_end_sample<BUDGET, VIEWS, CULL>(p, a, f);
 }
 
 /* ================= SHADE: the closest hit of this bounce is known (p.best_obj >= 0) ========= */
@@ -291,7 +295,7 @@ __device__ __forceinline__ void px_shade_miss(Px &p, const rt_kernel_args &a, co
  * (profiles/r04/experiments/box_muller_on_its_domain.txt) */
 /* PLAIN (RT_TRAIT_PLAIN_MATERIALS; rt_traits_kernel alone): no material of the scene needs texture coordinates, refracts or carries a texture,
  * so the three regions that every hit would test for and skip are not compiled in; what is left is the same operations in the same order */
-template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false, bool VIEWS = false, bool PLAIN = false>
+template <bool SHORT_DIVIDE, bool GENERAL_FUNCTIONS, bool BUDGET = false, bool VIEWS = false, bool PLAIN = false, bool CULL = false>
 __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const Frame &f, const Lds &L)
 {
     V3 &o = p.o, &d = p.d;
@@ -408,7 +412,7 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
         p.frame_steps += (unsigned)(RT_COST_HIT * RT_MAX_BATCH_FRAMES);
     }
     p.mode = M_GEN;
-    if (p.bounce >= f.limit) px_end_sample<BUDGET, VIEWS>(p, a, f);
+    if (p.bounce >= f.limit) px_end_sample<BUDGET, VIEWS, CULL>(p, a, f);
 }
 
 /* ================= FETCH: lanes without a pixel take the next ones =========================
@@ -417,7 +421,11 @@ __device__ __forceinline__ void px_shade(Px &p, const rt_kernel_args &a, const F
  * by the whole wave.  Every call with a lane in M_FETCH either hands that lane a slot it has not been handed before or, once the tiles
  * are out, ends it (M_DONE): a lane that stays in M_FETCH (a slot outside the image; BUDGET: a pixel of budget 0) has used a slot up, so
  * calling again until no lane is in M_FETCH ends after at most (tiles * 64) slots, whatever the budgets are. */
-template <bool BUDGET = false, bool VIEWS = false>
+/* CULL: the pixel's bit of the view's cull plane is read here, once per pixel and frame (a null plane, tested wave-uniformly: no bit), into
+ * bit 31 of p.id, which no id reaches (at most 2^28 pixels: check_image_size) - PX_NOCULL is set unless the plane says that no primary ray
+ * of this pixel reaches a leaf of any mesh.  A spare bit, not a member of Px: a member, even a dead one, changes the register numbering of
+ * every kernel built from Px, and a register of its own held across the traversal loops changed their schedule (monkey +1.6 %). */
+template <bool BUDGET = false, bool VIEWS = false, bool CULL = false>
 __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args &a, const Frame &f, int lane)
 {
     const bool want = p.mode == M_FETCH;
@@ -539,6 +547,24 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
         RT_COST(p.c_steps = 0; p.c_wsteps = 0; p.c_t0 = (unsigned)wall_clock64());
         V3 plane_point = f.du * (float)px + f.dv * (float)py;
         p.primary = normalised((f.tl + plane_point) - f.cam_pos);
+        if (CULL) {
+            /* (the address is put together from two words of the block, so the compiler is told where it points: global memory) */
+            typedef const __attribute__((address_space(1))) uint32_t *cull_words;
+            /* the two words are read here, from the kernel's argument segment and by two volatile scalar loads of their own: as ordinary reads
+             * of a.cull_lo / a.cull_hi they join the block's other argument loads into wider ones, and the compiler then keeps the whole block
+             * in spilled scalar registers instead of loading an argument again where it is used (monkey +5 %).  The offsets are the block's,
+             * so the block has to be the kernel's first parameter: rt_render_kernel.h asserts it for every kernel compiled with CULL */
+            typedef const volatile __attribute__((address_space(4))) uint32_t *arg_words;
+            const arg_words args = (arg_words)__builtin_amdgcn_kernarg_segment_ptr();
+            const uint32_t plane_lo = args[offsetof(rt_kernel_args, cull_lo) / 4], plane_hi = args[offsetof(rt_kernel_args, cull_hi) / 4];
+            const cull_words plane = (cull_words)(uintptr_t)(((uint64_t)plane_hi << 32) | (uint64_t)plane_lo);
+            unsigned nocull = PX_NOCULL;
+            if (plane) {
+                const unsigned pixel = (unsigned)(py * f.W + px);
+                nocull = (~(plane[pixel >> 5] >> (pixel & 31u))) << 31;
+            }
+            p.id |= nocull;
+        }
         p.colour = v3(0.f, 0.f, 0.f);
         p.fin = v3(0.f, 0.f, 0.f); p.thr = v3(1.f, 1.f, 1.f);
         p.o = f.cam_pos; p.d = p.primary;
@@ -548,7 +574,7 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
         if (p.sample >= f.spp) {
             const float q = 0.0f / (float)f.spp;               /* NaN for spp == 0, like the reference */
             p.colour = v3(q, q, q) * (float)f.spp;             /* px_finish_pixel divides by spp again: q either way */
-            px_finish_pixel(p, a, f);                          /* M_FETCH: takes another pixel next time round */
+            px_finish_pixel<false, false, CULL>(p, a, f);      /* M_FETCH: takes another pixel next time round */
         } else {
             p.mode = M_GEN;
         }

@@ -14,6 +14,7 @@
 
 #include <array>
 #include <iterator>
+#include <type_traits>
 #include <utility>
 
 #include "rt_device_scene.h"
@@ -44,7 +45,9 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 #define RT_LOOP_VIEWS false
 #define RT_LOOP_SKY false
 #define RT_LOOP_TRAITS 0
+#define RT_LOOP_CULL rt_loop_culls(HAS_MESH, MODE, NT, RT_VARIANT_GENERIC)
 #include "rt_render_loop.inc"
+#undef RT_LOOP_CULL
 #undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
@@ -60,11 +63,23 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
 #define RT_LOOP_VIEWS false
 #define RT_LOOP_SKY false
 #define RT_LOOP_TRAITS rt_variant_traits(HAS_MESH, MODE, NT)
+#define RT_LOOP_CULL rt_loop_culls(HAS_MESH, MODE, NT, RT_VARIANT_TRAITS_KERNEL)
 #include "rt_render_loop.inc"
+#undef RT_LOOP_CULL
 #undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
 #undef RT_LOOP_BUDGET
+
+/* px_fetch under CULL reads rt_kernel_args::cull_lo / cull_hi at their offsets in the kernel's argument segment (rt_pixel.h): the block has to
+ * start that segment.  Only rt_traits_kernel is compiled with CULL (rt_loop_culls is false for RT_VARIANT_GENERIC): its one parameter is an
+ * rt_traits_args, whose first - and only - base is the block, in front of the members it adds. */
+static_assert(!rt_loop_culls(1, RT_SCENE_LDS, 1024, RT_VARIANT_GENERIC), "rt_render_kernel is not compiled with CULL: its loop has no form of the cull");
+static_assert(std::is_same<decltype(&rt_traits_kernel<1024, true, RT_SCENE_LDS>), void (*)(rt_traits_args)>::value,
+              "the block is rt_traits_kernel's only parameter: px_fetch reads the cull plane's address at the block's offsets in the argument segment");
+static_assert(std::is_base_of<rt_kernel_args, rt_traits_args>::value && !std::is_polymorphic<rt_traits_args>::value && std::is_standard_layout<rt_kernel_args>::value &&
+                  sizeof(rt_traits_args) == sizeof(rt_kernel_args) + 8,
+              "rt_traits_args is the block and, behind it, mesh_obj and its padding: nothing virtual, no second base in front of the block");
 
 /* The budget variant: per-pixel sample counts (rt_render_budget_device), same shapes and launch bounds.  Its loop is a function taking the
  * argument block by reference: stated in the kernel like the render kernel's, the same text is allocated 101-113 registers in the
@@ -76,7 +91,9 @@ __device__ __forceinline__ void rt_budget_loop(const rt_budget_args &a)
 #define RT_LOOP_VIEWS false
 #define RT_LOOP_SKY false
 #define RT_LOOP_TRAITS 0
+#define RT_LOOP_CULL false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_CULL
 #undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
@@ -98,7 +115,9 @@ __device__ __forceinline__ void rt_views_loop(const rt_views_args &a)
 #define RT_LOOP_VIEWS true
 #define RT_LOOP_SKY false
 #define RT_LOOP_TRAITS 0
+#define RT_LOOP_CULL false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_CULL
 #undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS
@@ -119,7 +138,9 @@ __device__ __forceinline__ void rt_sky_loop(const rt_sky_args &a)
 #define RT_LOOP_VIEWS true
 #define RT_LOOP_SKY true
 #define RT_LOOP_TRAITS 0
+#define RT_LOOP_CULL false
 #include "rt_render_loop.inc"
+#undef RT_LOOP_CULL
 #undef RT_LOOP_TRAITS
 #undef RT_LOOP_SKY
 #undef RT_LOOP_VIEWS

@@ -3,7 +3,8 @@
  * head of what runs it (template <int NT, bool HAS_MESH, int MODE> ... (ARGS a)), with RT_LOOP_BUDGET defined as false (rt_render_kernel,
  * rt_views_loop, rt_sky_loop) or true (rt_budget_loop), RT_LOOP_VIEWS as true (rt_views_loop, rt_sky_loop: a camera per frame of the launch) or
  * false, RT_LOOP_SKY as true (rt_sky_loop: a miss looks the sky up in a cube map) or false and RT_LOOP_TRAITS as the scene traits the kernel is
- * compiled for (rt_traits_kernel: rt_variant_traits of its shape) or 0.  Text, not a function: called as a function the loop compiles to other code in all thirteen render
+ * compiled for (rt_traits_kernel: rt_variant_traits of its shape) or 0, and RT_LOOP_CULL as whether the kernel reads the primary-ray cull's plane
+ * (rt_render_kernel and rt_traits_kernel: rt_loop_culls of the shape and the kernel; false in the loops).  Text, not a function: called as a function the loop compiles to other code in all thirteen render
  * kernels, and the render kernel's code is kept byte for byte.
  */
 {
@@ -11,7 +12,9 @@
     constexpr bool VIEWS = RT_LOOP_VIEWS;
     constexpr bool SKY = RT_LOOP_SKY;
     constexpr int TRAITS = RT_LOOP_TRAITS;      /* RT_TRAIT_* the scene is known to have (rt_traits_kernel; `a` is then an rt_traits_args), 0 everywhere else */
+    constexpr bool CULL = RT_LOOP_CULL;         /* primary rays of pixels the view's cull plane flags skip the meshes (rt_cull.h) */
     constexpr bool ONE_MESH = HAS_MESH && (TRAITS & RT_TRAIT_ONE_MESH) != 0;
+    static_assert(!CULL || ONE_MESH, "the cull acts where the ONE_MESH kernel tests its one root box: there is no form of it for the MESH section");
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
     const int lane = tid & (RT_WAVE - 1);
@@ -72,7 +75,7 @@
          * condition has to take the batch, or the wave comes back with nothing changed.  Both conditions are stated in
          * rt_device_scene.h (RT_ROUND_SHADES, rt_traversal_yields), where tests/sanitize/capi_host_fuzz.cpp (check_progress) takes
          * them from too. */
-        if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss<BUDGET, VIEWS, SKY>(p, a, f);
+        if (p.mode == M_SHADE && p.best_obj < 0) px_shade_miss<BUDGET, VIEWS, SKY, CULL>(p, a, f);
         {
             const int n_hit = __popcll(__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_SHADE, RT_ICMP_EQ));
             const bool others = (__builtin_amdgcn_uicmp((unsigned)p.mode, (unsigned)M_GEN, RT_ICMP_EQ) |
@@ -81,12 +84,12 @@
             if (RT_ROUND_SHADES(a, HAS_MESH, n_hit, n_trav, others)) {
                 if (p.mode == M_SHADE) {
                     RT_STAT(ST_SHADE);
-                    px_shade<!(NT == 1024 && HAS_MESH), MODE == RT_SCENE_HYBRID, BUDGET, VIEWS, (TRAITS & RT_TRAIT_PLAIN_MATERIALS) != 0>(p, a, f, L);
+                    px_shade<!(NT == 1024 && HAS_MESH), MODE == RT_SCENE_HYBRID, BUDGET, VIEWS, (TRAITS & RT_TRAIT_PLAIN_MATERIALS) != 0, CULL>(p, a, f, L);
                 }
             }
         }
         RT_LAP(TM_SHADE);
-        px_fetch<BUDGET, VIEWS>(p, ch, a, f, lane);
+        px_fetch<BUDGET, VIEWS, CULL>(p, ch, a, f, lane);
         if (BUDGET) {
             /* Where budgets are sparse most slots hand their lane nothing.  A lane left in M_FETCH asks again at once instead of idling through
              * a round of the others' work: until every lane has a pixel to trace or the tiles are out (then px_fetch ends the lanes left).
@@ -104,7 +107,9 @@
                  * ray came out of px_gen as M_SHADE, which it stays unless it enters the box) */
                 RT_STAT(ST_MESH);
                 const v4f m0 = L.meshes[0], m1 = L.meshes[1];
-                if (!(p.d.x != p.d.x || p.d.y != p.d.y || p.d.z != p.d.z)) {
+                /* (CULL: a primary ray - bounce 0 - of a pixel the view's cull plane flags does not test the root box and stays M_SHADE: it would
+                 * enter no leaf, rt_cull.h.  Nothing else about the ray changes: the same draws, the same simple-object hit, the same shade) */
+                if (!(CULL && ((unsigned)p.bounce | (p.id & PX_NOCULL)) == 0u) && !(p.d.x != p.d.x || p.d.y != p.d.y || p.d.z != p.d.z)) {
                     const uint32_t root_ref = __float_as_uint(m1.z);
                     float rd;
                     const bool rh = box_test(m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, p.o, p.inv, rd);

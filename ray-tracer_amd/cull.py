@@ -1,0 +1,50 @@
+"""The primary-ray cull's test and development hooks (csrc/rt_cull.h): the bit plane a context's last render launch was handed, and the same
+plane computed on the host from a flattened scene."""
+import ctypes as C
+
+import numpy as np
+
+from ._abi import lib, rt_flat_view
+from .objects import Scene
+
+_u32p = C.POINTER(C.c_uint32)
+STATS = ("root_entering", "flagged_root_entering", "centre_steps_flagged", "centre_steps_root_entering", "flagged", "words")
+
+
+def plane_words(width, height):
+    """rt_cull_words: 32 pixels to a word, whole pairs of words"""
+    return ((int(width) * int(height) + 63) // 64) * 2
+
+
+def plane_bits(words, width, height):
+    """a plane's words as a (height, width) array of 0 / 1: pixel py * width + px is bit (pixel & 31) of word pixel >> 5"""
+    bits = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")
+    return bits[:int(width) * int(height)].reshape(int(height), int(width))
+
+
+def primary_cull_plane(ctx):
+    """(used, width, height, words): whether the context's last render launch was handed a cull plane, and that plane read back from the device
+    (words is None if it was not); waits for the device"""
+    info = (C.c_int32 * 4)()
+    ctx._check(lib().rt_debug_primary_cull(ctx._h, None, 0, info))
+    if not info[0]:
+        return False, 0, 0, None
+    words = np.zeros(int(info[3]), np.uint32)
+    ctx._check(lib().rt_debug_primary_cull(ctx._h, words.ctypes.data_as(_u32p), words.size, info))
+    return True, int(info[1]), int(info[2]), words
+
+
+def primary_cull_host(scene, camera, antialias=True):
+    """(words, stats) of the predicate evaluated on the host, per pixel of `camera`'s image, on a SceneObjects (its flattened layout) or a committed
+    Scene (what is on the device now: waits for it).  Needs no GPU for a SceneObjects."""
+    v = rt_flat_view()
+    if isinstance(scene, Scene):
+        scene.ctx._check(lib().rt_debug_scene_read(scene.ctx._h, scene._h, C.byref(v)))
+    else:
+        scene._check(lib().rt_debug_flatten(scene._h, C.byref(v)))
+    words = np.zeros(plane_words(camera.c.width, camera.c.height), np.uint32)
+    stats = (C.c_int64 * 6)()
+    st = lib().rt_debug_primary_cull_host(C.byref(v), C.byref(camera.c), 1 if antialias else 0, words.ctypes.data_as(_u32p), stats)
+    if st != 0:
+        raise ValueError("rt_debug_primary_cull_host refused its arguments (status %d)" % st)
+    return words, dict(zip(STATS, (int(x) for x in stats)))

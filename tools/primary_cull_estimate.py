@@ -1,0 +1,49 @@
+"""What the primary-ray cull (csrc/rt_cull.h) flags in a view, on the CPU alone (development tool; no GPU, the project's own flattened tree):
+   python tools/primary_cull_estimate.py [--scene monkey] [--width 128] [--height 72] [--no-antialias]
+For a config scene (ray-tracer_amd/scenes.py) and an image size it evaluates the kernel's predicate per pixel through
+rt_debug_primary_cull_host and prints the flagged share of the pixels whose jitter cone may enter a mesh's root box, and the share of the
+centre-ray node steps of those pixels that the flagged ones carry - the traversal work the render kernel no longer does for primary rays."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def estimate(scene="monkey", width=128, height=72, antialias=True):
+    rt = importlib.import_module("ray-tracer_amd")
+    objs, _sky = getattr(rt.scenes, scene)()
+    _words, st = rt.primary_cull_host(rt.SceneObjects(objs), rt.Camera(width, height), antialias)
+    st = dict(st, scene=scene, width=width, height=height, antialias=bool(antialias), pixels=width * height)
+    st["flagged_share_of_root_entering"] = st["flagged_root_entering"] / st["root_entering"] if st["root_entering"] else 0.0
+    st["step_share_of_flagged"] = st["centre_steps_flagged"] / st["centre_steps_root_entering"] if st["centre_steps_root_entering"] else 0.0
+    return st
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--scene", default="monkey")
+    ap.add_argument("--width", type=int, default=128)
+    ap.add_argument("--height", type=int, default=72)
+    ap.add_argument("--no-antialias", action="store_true")
+    ap.add_argument("--json", action="store_true")
+    a = ap.parse_args()
+    st = estimate(a.scene, a.width, a.height, not a.no_antialias)
+    if a.json:
+        print(json.dumps(st))
+        return
+    print("%s %dx%d antialias=%s" % (st["scene"], st["width"], st["height"], st["antialias"]))
+    print("pixels whose cone may enter a root box: %d of %d" % (st["root_entering"], st["pixels"]))
+    print("of those, flagged (no leaf reachable):  %d (%.1f %%)" % (st["flagged_root_entering"], 100 * st["flagged_share_of_root_entering"]))
+    print("flagged pixels in all:                  %d (%.1f %% of the image)" % (st["flagged"], 100.0 * st["flagged"] / st["pixels"]))
+    print("centre-ray node steps: %.1f per flagged root-entering pixel, %.1f per other root-entering pixel" % (
+        st["centre_steps_flagged"] / max(st["flagged_root_entering"], 1),
+        (st["centre_steps_root_entering"] - st["centre_steps_flagged"]) / max(st["root_entering"] - st["flagged_root_entering"], 1)))
+    print("share of those steps carried by the flagged pixels: %.1f %%" % (100 * st["step_share_of_flagged"]))
+
+
+if __name__ == "__main__":
+    main()
