@@ -482,6 +482,64 @@ rt_status rt_render_aov_device(rt_ctx *ctx, const rt_scene *scene, const rt_came
 rt_status rt_render_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, const float sky_colour[3],
                         float *depth, float *normal, float *albedo, int32_t *object, float *ray);
 
+/* ---- nearest-surface queries: closest point and distance ------------------------------------------
+ * "How far is this point from the scene, and where is the closest surface point?" - the question a particle, a cloth vertex, a
+ * distance-field bake or a snap-to-surface asks, which no ray answers: a ray probes one direction somebody chose.  For n points at
+ * once, over the records the kernels read (rt_debug_flatten: spheres (c, r), triangles (p0, s1, s2), the meshes' trees).  The
+ * distance is UNSIGNED: inside / outside needs watertight meshes and a parity rule for rays through edges, and is out of scope.
+ *
+ * The result is DEFINED, not approximated: binary32 + - * / sqrt, comparisons and selects, every operation rounded once (no fused
+ * multiply-add), in the order written here, so tests/nearest_ref.py (NumPy float32, every candidate of every point, no traversal)
+ * gives the same bytes.  dot(a, b) = (ax*bx + ay*by) + az*bz; sq(a) = dot(a, a).
+ *
+ * Candidates: every object of the scene, for the point p.
+ *   sphere (c, r):   v = p - c; l = sqrt(sq(v)); s = l - r; d2 = s*s; point = c + v * (r / l) (the quotient first, then three
+ *                    products, then three sums); for l == 0, point = c + (r, 0, 0).  triangle = -1.
+ *   triangle record (p0, s1, s2) - a loose triangle, the two of a quad (a one-way quad counts from both sides), the twelve of a
+ *   cuboid, every triangle of a mesh: the closest point of the triangle by the region test of Ericson, Real-Time Collision Detection
+ *   5.1.5, with a = p0, ab = s1, ac = s2 on the record as stored (the second and third vertex are not formed again):
+ *                    ap = p - p0; bp = ap - s1; cp = ap - s2;
+ *                    d1 = dot(s1, ap); d2 = dot(s2, ap); d3 = dot(s1, bp); d4 = dot(s2, bp); d5 = dot(s1, cp); d6 = dot(s2, cp);
+ *                    vc = d1*d4 - d3*d2; vb = d5*d2 - d1*d6; va = d3*d6 - d5*d4;
+ *                    the first of these that holds gives the barycentrics (v, w):
+ *                      d1 <= 0 and d2 <= 0                        (0, 0)
+ *                      d3 >= 0 and d4 <= d3                       (1, 0)
+ *                      vc <= 0 and d1 >= 0 and d3 <= 0            (d1 / (d1 - d3), 0)
+ *                      d6 >= 0 and d5 <= d6                       (0, 1)
+ *                      vb <= 0 and d2 >= 0 and d6 <= 0            (0, d2 / (d2 - d6))
+ *                      va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0  w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w
+ *                      otherwise                                  k = 1 / ((va + vb) + vc), v = vb * k, w = vc * k
+ *                    q = s1*v + s2*w (per component: two products, one sum); point = p0 + q; r = ap - q; dist2 = sq(r).
+ *                    (A comparison with a NaN does not hold; a NaN then reaches dist2.)
+ *   a mesh's triangle, additionally: dist2 = B where dist2 < B, with B the largest BOX DISTANCE over the boxes on the path from the
+ *   mesh's root box to the triangle's leaf (the root box, then the child box stored in each node on the way down).  The box distance
+ *   of (lo, hi): per axis e = max(max(lo - p, p - hi), 0), then sq(e).  Rounded subtraction, squaring and addition are monotone, so an
+ *   enclosing box never computes a larger distance than a box inside it, and a candidate that is by definition no nearer than every box
+ *   on its path can be pruned by "this subtree's path value is greater than the best so far" without an error analysis: the result
+ *   is the exhaustive minimum in whatever order a traversal visits the tree.  The clamp only bites where rounding put a triangle's
+ *   dist2 a few ulps under a bound that exact arithmetic guarantees.
+ * Winner: the smallest dist2; on equal dist2 the lower object index, then the lower triangle index; a NaN dist2 never wins.  With a
+ * limit max_dist a candidate needs dist2 <= max_dist * max_dist (one rounding); +Inf, or no limit array, is unbounded; a limit that
+ * is NaN or below zero gives a miss; so does a point with a NaN or infinite coordinate. */
+typedef struct __attribute__((aligned(16))) rt_nearest {
+    float distance;        /* sqrt(distance2), correctly rounded; RT_HIT_MISS_T for a miss */
+    float distance2;       /* the winner's dist2; RT_HIT_MISS_T for a miss */
+    float point[3];        /* the closest surface point */
+    int32_t object;        /* index in the scene's object list, as rt_hit.object; -1: a miss */
+    int32_t triangle;      /* index of the triangle in the flattened scene, as rt_hit.triangle; -1 for a sphere or a miss */
+    int32_t reserved;      /* 0 */
+} rt_nearest;              /* 32 bytes.  A miss is {RT_HIT_MISS_T, RT_HIT_MISS_T, {0,0,0}, -1, -1, 0} bit for bit */
+
+/* Device-buffer form: d_points (n x 3 floats), d_max_dist (n floats, or NULL: unbounded) and d_out (n records, 16-byte aligned) are
+ * device memory of ctx's GPU; asynchronous on hip_stream and ordered like rt_trace_rays_device (one launch in flight per context).
+ * n == 0 succeeds and touches nothing; n < 0, n > 2^30, a null pointer (other than d_max_dist) with n > 0, a misaligned d_out and a
+ * scene committed on another context are RT_ERR_INVALID and leave the launch order as it was.  rt_last_kernel_ms then reports the
+ * kernel.  A scene updated by rt_scene_update_mesh_device answers for its new geometry. */
+rt_status rt_nearest_points_device(rt_ctx *ctx, const rt_scene *scene, const float *d_points, const float *d_max_dist, int64_t n,
+                                   rt_nearest *d_out, void *hip_stream);
+/* Host-buffer form: uploads the points (and limits), answers, downloads the records and returns when they are in `out`. */
+rt_status rt_nearest_points(rt_ctx *ctx, const rt_scene *scene, const float *points, const float *max_dist, int64_t n, rt_nearest *out);
+
 /* ---- occlusion (any-hit) ray queries and the light-visibility plane ------------------------------
  * "Is anything in the way?": line of sight, shadow masks, reachability probes.  For a ray (o, d) taken as given and a limit tmax,
  *     occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_trace_rays answers) finds a hit AND its t <= tmax.

@@ -85,6 +85,9 @@ class rt_adaptive_stats(C.Structure):
 HIT_DTYPE = np.dtype([("t", np.float32), ("point", np.float32, (3,)), ("normal", np.float32, (3,)), ("object", np.int32),
                       ("triangle", np.int32), ("u", np.float32), ("v", np.float32), ("reserved", np.int32)])
 HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
+# rt_nearest (include/rt_amd.h) as a NumPy record: what nearest_points returns.  A miss: distance and distance2 HIT_MISS_T, object -1
+NEAREST_DTYPE = np.dtype([("distance", np.float32), ("distance2", np.float32), ("point", np.float32, (3,)), ("object", np.int32),
+                          ("triangle", np.int32), ("reserved", np.int32)])
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
 VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
 AO_PLANES = ("ao", "count")
@@ -172,6 +175,8 @@ ABI = {
     "rt_trace_rays": (st, [vp, vp, fp, fp, i64, vp]),
     "rt_render_aov_device": (st, [vp, vp, cam, fp, vp, vp, vp, vp, vp, vp]),
     "rt_render_aov": (st, [vp, vp, cam, fp, fp, fp, fp, i32p, fp]),
+    "rt_nearest_points_device": (st, [vp, vp, vp, vp, i64, vp, vp]),
+    "rt_nearest_points": (st, [vp, vp, fp, fp, i64, vp]),
     "rt_occluded_rays_device": (st, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "rt_occluded_rays": (st, [vp, vp, fp, fp, fp, i64, vp]),
     "rt_render_visibility_device": (st, [vp, vp, cam, fp, f32, vp, vp]),

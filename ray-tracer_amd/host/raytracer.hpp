@@ -492,6 +492,22 @@ public:
         check(rt_trace_rays(ctx_, scene_, origin.data(), direction.data(), 1, &h));
         return h;
     }
+    /* The closest surface point of the scene for every point (rt_nearest_points): points holds n x 3 floats; max_dist n limits, or none
+     * (unbounded).  The distance is unsigned.  A miss - nothing within the limit - has object -1 and distance RT_HIT_MISS_T. */
+    std::vector<rt_nearest> nearest_points(const std::vector<float> &points, const std::vector<float> &max_dist = {})
+    {
+        if (points.size() % 3 != 0) throw std::invalid_argument("points must hold n x 3 floats");
+        std::vector<rt_nearest> out(points.size() / 3);
+        if (!max_dist.empty() && max_dist.size() != out.size()) throw std::invalid_argument("max_dist must hold n floats, or none");
+        check(rt_nearest_points(ctx_, scene_, points.data(), max_dist.empty() ? nullptr : max_dist.data(), (int64_t)out.size(), out.data()));
+        return out;
+    }
+    rt_nearest nearest_point(Vec3 point, float max_dist = INFINITY)
+    {
+        rt_nearest r;
+        check(rt_nearest_points(ctx_, scene_, point.data(), &max_dist, 1, &r));
+        return r;
+    }
     /* The first-hit planes of a view (rt_render_aov), all five of them: depth W*H, normal / albedo / ray W*H*3, object W*H */
     struct Aov {
         std::vector<float> depth, normal, albedo, ray;

@@ -1,9 +1,10 @@
-"""Ray queries: closest hits and first-hit planes, occlusion (any-hit), the light-visibility plane and the ambient-occlusion plane."""
+"""Queries: closest hits and first-hit planes, occlusion (any-hit), the light-visibility plane, the ambient-occlusion plane, and the
+nearest-surface queries (closest point and distance, which are no ray questions)."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, NEAREST_DTYPE, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -109,3 +110,83 @@ def render_ao_device(ctx, scene, camera, samples=16, radius=float("inf"), bias=1
     the two must be); asynchronous on `stream`."""
     ctx._check(lib().rt_render_ao_device(ctx._h, scene._h, C.byref(camera.c), int(samples), float(radius), float(bias), int(time_ms),
                                          _dptr(d_count), _dptr(d_ao), _dptr(stream)))
+
+
+NearestRecord = NEAREST_DTYPE       # rt_nearest as a structured dtype: distance, distance2, point[3], object, triangle, reserved
+
+
+def _limits(max_dist, n):
+    if max_dist is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, dtype=np.float32), (n,)))
+
+
+def nearest_points(ctx, scene, points, max_dist=None):
+    """The closest surface point of the scene for every point (rt_nearest_points): points [n, 3] float32; max_dist None (unbounded), a
+    scalar or n float32 limits.  Returns n records of NearestRecord: the unsigned distance, its square, the closest point, the object and
+    (for a triangle) the flattened triangle index; a miss - nothing within the limit, a limit that is NaN or negative, a point that is
+    not finite - has object -1 and distance HIT_MISS_T."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    lim = _limits(max_dist, n)
+    out = np.zeros(n, NEAREST_DTYPE)
+    ctx._check(lib().rt_nearest_points(ctx._h, scene._h, _fp(p)[1], _fp(lim)[1] if lim is not None else None, n, C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def _device_floats(t, per_item, what):
+    """a contiguous float32 torch tensor on the GPU -> (pointer, items)"""
+    if str(t.dtype) != "torch.float32" or not t.is_contiguous() or not t.is_cuda or t.numel() % per_item:
+        raise ValueError("%s must be a contiguous float32 tensor on the GPU of %d floats per point" % (what, per_item))
+    return t.data_ptr(), t.numel() // per_item
+
+
+def nearest_points_device(ctx, scene, points, max_dist=None, out=None, n=None, stream=None):
+    """Device-buffer form (rt_nearest_points_device), asynchronous on `stream` (a hipStream_t as an int; None: the default stream) and in
+    the context's launch order.  `points` is a float32 torch tensor of 3 n elements on the scene's GPU, `max_dist` None or one of n, `out`
+    None or a uint8 tensor of 32 n bytes - or all three are device pointers as ints together with n.  With tensors the records come back
+    as a uint8 tensor [n, 32] (the one passed as `out`, or a new one): `.cpu().numpy().view(NearestRecord)` reads them."""
+    if isinstance(points, int):
+        if n is None or out is None:
+            raise ValueError("device pointers need n, the number of points, and out")
+        ctx._check(lib().rt_nearest_points_device(ctx._h, scene._h, _dptr(points), _dptr(max_dist), int(n), _dptr(out), _dptr(stream)))
+        return out
+    import torch
+    ptr, count = _device_floats(points, 3, "points")
+    if n is not None and int(n) != count:
+        raise ValueError("n differs from the points given")
+    lim_ptr = None
+    if max_dist is not None:
+        lim_ptr, n_lim = _device_floats(max_dist, 1, "max_dist")
+        if n_lim != count:
+            raise ValueError("max_dist must hold one limit per point")
+    if out is None:
+        out = torch.empty((count, NEAREST_DTYPE.itemsize), dtype=torch.uint8, device=points.device)
+    elif str(out.dtype) != "torch.uint8" or not out.is_contiguous() or not out.is_cuda or out.numel() != count * NEAREST_DTYPE.itemsize:
+        raise ValueError("out must be a contiguous uint8 tensor on the GPU of 32 bytes per point")
+    ctx._check(lib().rt_nearest_points_device(ctx._h, scene._h, _dptr(ptr), _dptr(lim_ptr), count, _dptr(out.data_ptr()), _dptr(stream)))
+    return out
+
+
+def distance_grid(scene, lo, hi, shape, max_dist=None, stream=None):
+    """The scene's unsigned distance field on a regular lattice: shape = (nx, ny, nz) points from corner lo to corner hi inclusive (a
+    single point along an axis sits at lo), built with torch on the context's GPU and answered by nearest_points_device without a host
+    round trip.  Returns (distance, records): a float32 tensor [nx, ny, nz] and the uint8 records [nx * ny * nz, 32], x slowest."""
+    import torch
+    ctx = scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    axes = []
+    for k in range(3):
+        m = int(shape[k])
+        if m < 1:
+            raise ValueError("shape must be at least 1 along every axis")
+        axes.append(torch.linspace(float(lo[k]), float(hi[k]), m, dtype=torch.float32, device=dev) if m > 1
+                    else torch.full((1,), float(lo[k]), dtype=torch.float32, device=dev))
+    gx, gy, gz = torch.meshgrid(axes[0], axes[1], axes[2], indexing="ij")
+    pts = torch.stack((gx, gy, gz), dim=-1).reshape(-1, 3).contiguous()
+    lim = None if max_dist is None else torch.full((pts.shape[0],), float(max_dist), dtype=torch.float32, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream      # the lattice was produced on it: the query is queued behind
+    rec = nearest_points_device(ctx, scene, pts, lim, stream=stream)
+    dist = rec.view(torch.float32).reshape(-1, 8)[:, 0].reshape(int(shape[0]), int(shape[1]), int(shape[2]))
+    return dist, rec
