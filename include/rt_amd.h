@@ -540,6 +540,56 @@ rt_status rt_nearest_points_device(rt_ctx *ctx, const rt_scene *scene, const flo
 /* Host-buffer form: uploads the points (and limits), answers, downloads the records and returns when they are in `out`. */
 rt_status rt_nearest_points(rt_ctx *ctx, const rt_scene *scene, const float *points, const float *max_dist, int64_t n, rt_nearest *out);
 
+/* ---- multi-hit ray queries: the first k hits of a ray, and hit counts ----------------------------
+ * What lies BEHIND the first surface: transparency and x-ray views, the thickness of a part along a ray, "select through" picking,
+ * the number of surfaces between two points, crossing counts.  One launch instead of k chained rt_trace_rays calls re-rooted at
+ * hit + epsilon, which skip or repeat surfaces and trace rays of other floats than the one asked about.
+ *
+ * The answer is DEFINED to the bit.  The ray (o, d) is taken as given, as for rt_trace_rays: d is not normalised, t is in units of its
+ * length, inv = 1.0f / d per component; a direction with a NaN component has no candidate.  Binary32, nothing fused.
+ *
+ * Candidates: triples (t, object, triangle) from the tests rt_trace_rays runs (src/objects.cu), on the records of rt_debug_flatten.
+ *   sphere:         Sphere::hit's near root, accepted when > 1e-6; triangle = -1.  At most one candidate: the far root (the exit
+ *                   point, or the only hit from inside) is OUT OF SCOPE, as it is for rt_trace_rays.
+ *   loose triangle: Triangle::hit (Moller-Trumbore, two-sided; t > 1e-6, u >= 0, v >= 0, 1 - u - v >= 0).
+ *   quad, one-way quad: Quad::hit's ONE candidate - the first record if it hits, else the second.  A one-way quad offers nothing when
+ *                   dot(d, normal) < 0.
+ *   cuboid:         each of its six quads offers its one candidate.
+ *   mesh:           every triangle record of the mesh that Triangle::hit accepts and whose every box on the path passes the strict slab
+ *                   test (BoundingBox::ray_hits: per axis t1 = (lo - o) * inv, t2 = (hi - o) * inv, tmin = max(tmin, min(t1, t2)),
+ *                   tmax = min(tmax, max(t1, t2)), from tmin = 0 and tmax = RT_HIT_MISS_T, min / max dropping a NaN operand; passed
+ *                   when tmin < tmax and tmax > 0).  The path runs over the flattened tree: the mesh table's root box, then the child
+ *                   box stored in each node on the way down to the triangle's leaf.
+ * Key: K = max(t, B), with B the largest slab ENTRY DISTANCE tmin over the boxes of the candidate's path, 0 for a candidate of no
+ * mesh (tmin starts from 0 and drops NaNs: B is never a NaN).  K orders and limits the candidates; the record reports the raw t, so
+ * record 0 stays the float rt_trace_rays reports.  Every candidate below a box has, by definition, a key no smaller than that box's
+ * entry distance, so "skip a subtree whose box fails the slab test or whose entry distance is GREATER than the threshold (the limit, or
+ * the k-th best key so far)" is exact in whatever order a traversal visits the tree, without an error analysis; a subtree entered AT
+ * the threshold must still be visited, because of the tie rule.  The clamp only bites where rounding put a triangle's t a few ulps
+ * under the entry distance of a box that contains it: there the reported t of successive records can STEP DOWN by those few ulps.
+ * Limit: lim = min(tmax, RT_HIT_MISS_T), or RT_HIT_MISS_T without a limit array; a candidate counts when K <= lim.  A NaN tmax counts
+ * nothing (nor does one that is not positive: K > 1e-6).
+ * Order: ascending K; on equal K the higher object index first (the reference's "later object wins"), within one object the lower
+ * flattened triangle index first.
+ * Output, for ray i: d_counts[i] = min(k, candidates that count) for k > 0; for k == 0, COUNT-ONLY mode, the number of ALL candidates
+ * that count (nothing is recorded, nothing but the limit prunes).  Records 0 .. count-1 (d_hits[i * k + rank]) are rt_hit records
+ * formed exactly as rt_trace_rays forms one for that (t, object, triangle); records count .. k-1 are the miss pattern, bit for bit.
+ * Where rt_trace_rays and record 0 can differ: equal t inside one mesh (the reference keeps the first triangle its traversal meets,
+ * here the lower index), and where the clamp reorders; tests/golden/multihit_meta.json has the measured share of such rays. */
+#define RT_MULTIHIT_MAX 8               /* records per ray, at most */
+/* Device-buffer form: d_origins, d_directions (n x 3 floats each), d_tmax (n floats, or NULL), d_hits (n * k records, [ray][rank],
+ * 16-byte aligned) and d_counts (n int32, may be NULL when k > 0) are device memory of ctx's GPU; asynchronous on hip_stream and
+ * ordered like rt_trace_rays_device.  n == 0 succeeds and touches nothing.  RT_ERR_INVALID, leaving the launch order as it was: n < 0
+ * or n > 2^30; k < 0 or k > RT_MULTIHIT_MAX; a null ray pointer with n > 0; d_hits null or misaligned while k > 0; d_counts null
+ * while k == 0; a scene of another context; a scene of more than 4,096 objects (an object's index shares a register with the
+ * triangle's).  rt_last_kernel_ms then reports the multi-hit kernel. */
+rt_status rt_trace_rays_multi_device(rt_ctx *ctx, const rt_scene *scene, const float *d_origins, const float *d_directions,
+                                     const float *d_tmax, int64_t n, int32_t k, rt_hit *d_hits, int32_t *d_counts, void *hip_stream);
+/* Host-buffer form: uploads the rays (and limits), answers, downloads the records and counts (each where its pointer is not NULL) and
+ * returns when they are in host memory (the context keeps the device buffers). */
+rt_status rt_trace_rays_multi(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions, const float *tmax,
+                              int64_t n, int32_t k, rt_hit *hits, int32_t *counts);
+
 /* ---- occlusion (any-hit) ray queries and the light-visibility plane ------------------------------
  * "Is anything in the way?": line of sight, shadow masks, reachability probes.  For a ray (o, d) taken as given and a limit tmax,
  *     occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_trace_rays answers) finds a hit AND its t <= tmax.

@@ -54,3 +54,4 @@
 #include "rt_rebuild_kernel.h"     /* a committed mesh's BVH rebuilt from new vertices: nothing of the traversal either (last: the kernels before it are emitted as they were) */
 #include "rt_cull_kernel.h"        /* the primary-ray cull's pre-pass: one bit per pixel of a view (behind everything else, for the same reason) */
 #include "rt_nearest_kernel.h"     /* nearest-surface queries: closest point and distance (in every build; last, for the same reason) */
+#include "rt_multihit_kernel.h"    /* multi-hit ray queries: the first k hits of a ray, and hit counts (not in the development builds; last, for the same reason) */

@@ -11,6 +11,7 @@
 #define RT_RAY_KERNELS_H
 
 #if !defined(RT_STATS) && !defined(RT_COSTMAP) && !defined(RT_MARK)
+#define RT_RAY_KERNELS_BUILT 1     /* read by rt_multihit_kernel.h, which rt_kernel.hip includes behind everything else */
 /* closest-hit ray queries and the AOV pass: rt_query_kernel and its launcher */
 #include "rt_query_kernel.h"
 /* occlusion (any-hit) ray queries and the light-visibility plane: rt_occlusion_kernel and its launcher */
@@ -18,6 +19,7 @@
 /* the ambient-occlusion plane: rt_ao_kernel and its launcher */
 #include "rt_ao_kernel.h"
 #else
+#define RT_RAY_KERNELS_BUILT 0
 #include <hip/hip_runtime.h>
 
 #include "rt_launch.h"

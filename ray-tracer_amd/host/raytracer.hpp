@@ -508,6 +508,34 @@ public:
         check(rt_nearest_points(ctx_, scene_, point.data(), &max_dist, 1, &r));
         return r;
     }
+    /* The first k hits of every ray in order along it (rt_trace_rays_multi): origins, directions hold n x 3 floats, tmax n limits or none;
+     * k from 1 to RT_MULTIHIT_MAX.  hits holds n * k records, [ray][rank], the ones behind a ray's last hit being misses; counts the records
+     * each ray has. */
+    struct MultiHits {
+        std::vector<rt_hit> hits;
+        std::vector<int32_t> counts;
+    };
+    MultiHits trace_rays_multi(const std::vector<float> &origins, const std::vector<float> &directions, int k, const std::vector<float> &tmax = {})
+    {
+        if (origins.size() != directions.size() || origins.size() % 3 != 0) throw std::invalid_argument("origins and directions must hold n x 3 floats each");
+        if (k < 1 || k > RT_MULTIHIT_MAX) throw std::invalid_argument("k must be 1 .. RT_MULTIHIT_MAX (count_hits counts without records)");
+        const size_t n = origins.size() / 3;
+        if (!tmax.empty() && tmax.size() != n) throw std::invalid_argument("tmax must hold n floats, or none");
+        MultiHits out;
+        out.hits.resize(n * (size_t)k);
+        out.counts.resize(n);
+        check(rt_trace_rays_multi(ctx_, scene_, origins.data(), directions.data(), tmax.empty() ? nullptr : tmax.data(), (int64_t)n, k, out.hits.data(), out.counts.data()));
+        return out;
+    }
+    /* How many surfaces every ray meets within its limit (rt_trace_rays_multi in count-only mode; a sphere counts once) */
+    std::vector<int32_t> count_hits(const std::vector<float> &origins, const std::vector<float> &directions, const std::vector<float> &tmax = {})
+    {
+        if (origins.size() != directions.size() || origins.size() % 3 != 0) throw std::invalid_argument("origins and directions must hold n x 3 floats each");
+        std::vector<int32_t> counts(origins.size() / 3);
+        if (!tmax.empty() && tmax.size() != counts.size()) throw std::invalid_argument("tmax must hold n floats, or none");
+        check(rt_trace_rays_multi(ctx_, scene_, origins.data(), directions.data(), tmax.empty() ? nullptr : tmax.data(), (int64_t)counts.size(), 0, nullptr, counts.data()));
+        return counts;
+    }
     /* The first-hit planes of a view (rt_render_aov), all five of them: depth W*H, normal / albedo / ray W*H*3, object W*H */
     struct Aov {
         std::vector<float> depth, normal, albedo, ray;

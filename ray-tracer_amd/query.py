@@ -1,10 +1,10 @@
-"""Queries: closest hits and first-hit planes, occlusion (any-hit), the light-visibility plane, the ambient-occlusion plane, and the
-nearest-surface queries (closest point and distance, which are no ray questions)."""
+"""Queries: closest hits and first-hit planes, multi-hit queries (the first k hits of a ray, hit counts), occlusion (any-hit), the
+light-visibility plane, the ambient-occlusion plane, and the nearest-surface queries (closest point and distance, which are no ray questions)."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, NEAREST_DTYPE, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -20,6 +20,74 @@ def trace_rays_device(ctx, scene, d_origins, d_directions, n, d_hits, stream=Non
     """Device-buffer form (rt_trace_rays_device): device pointers (ints, e.g. torch.Tensor.data_ptr()) to n x 3 float32 origins and
     directions and to n records of HIT_DTYPE.itemsize bytes (16-byte aligned); asynchronous on `stream`."""
     ctx._check(lib().rt_trace_rays_device(ctx._h, scene._h, _dptr(d_origins), _dptr(d_directions), int(n), _dptr(d_hits), _dptr(stream)))
+
+
+def _ray_limits(tmax, n):
+    if tmax is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,)))
+
+
+def trace_rays_multi(ctx, scene, origins, directions, k, tmax=None):
+    """The first k hits of every ray in order along it (rt_trace_rays_multi): origins, directions [n, 3] float32, the direction taken as
+    it is; k from 0 to MULTIHIT_MAX; tmax None, a scalar or n float32 limits in units of the direction's length.  Returns (hits, counts):
+    hits [n, k] records of HIT_DTYPE, the ones behind a ray's last hit being misses (object -1, t HIT_MISS_T), and counts [n] int32, the
+    records each ray has - with k == 0 the number of ALL its hits within the limit, and hits is empty."""
+    o, d = _ray_arrays(origins, directions)
+    n, k = o.shape[0], int(k)
+    if not 0 <= k <= MULTIHIT_MAX:
+        raise ValueError("k must be 0 .. %d" % MULTIHIT_MAX)
+    lim = _ray_limits(tmax, n)
+    hits = np.zeros((n, k), HIT_DTYPE)
+    counts = np.zeros(n, np.int32)
+    ctx._check(lib().rt_trace_rays_multi(ctx._h, scene._h, _fp(o)[1], _fp(d)[1], _fp(lim)[1] if lim is not None else None, n, k,
+                                         C.c_void_p(hits.ctypes.data) if hits.size else None, counts.ctypes.data_as(C.POINTER(C.c_int32))))
+    return hits, counts
+
+
+def count_hits(ctx, scene, origins, directions, tmax=None):
+    """How many surfaces every ray meets within its limit (trace_rays_multi in count-only mode): n int32.  Crossing counts, the number
+    of surfaces between two points; a sphere counts once (its near root)."""
+    return trace_rays_multi(ctx, scene, origins, directions, 0, tmax)[1]
+
+
+def trace_rays_multi_device(ctx, scene, origins, directions, k, tmax=None, hits=None, counts=None, n=None, stream=None):
+    """Device-buffer form (rt_trace_rays_multi_device), asynchronous on `stream` (a hipStream_t as an int; None: the default stream) and
+    in the context's launch order.  origins, directions are float32 torch tensors of 3 n elements on the scene's GPU, tmax None or one of
+    n, hits None or a uint8 tensor of n * k * 48 bytes, counts None or an int32 tensor of n - or all are device pointers as ints (hits and
+    counts may be None where the entry point allows it) together with n.  With tensors returns (hits, counts): uint8 [n, k, 48]
+    (`.cpu().numpy().view(HIT_DTYPE)[..., 0]` reads it; None with k == 0) and int32 [n], new ones where none were passed."""
+    k = int(k)
+    if isinstance(origins, int):
+        if n is None:
+            raise ValueError("device pointers need n, the number of rays")
+        ctx._check(lib().rt_trace_rays_multi_device(ctx._h, scene._h, _dptr(origins), _dptr(directions), _dptr(tmax), int(n), k, _dptr(hits), _dptr(counts), _dptr(stream)))
+        return hits, counts
+    import torch
+    o_ptr, count = _device_floats(origins, 3, "origins")
+    d_ptr, n_d = _device_floats(directions, 3, "directions")
+    if n_d != count or (n is not None and int(n) != count):
+        raise ValueError("origins, directions and n differ")
+    t_ptr = None
+    if tmax is not None:
+        t_ptr, n_t = _device_floats(tmax, 1, "tmax")
+        if n_t != count:
+            raise ValueError("tmax must hold one limit per ray")
+    if not 0 <= k <= MULTIHIT_MAX:
+        raise ValueError("k must be 0 .. %d" % MULTIHIT_MAX)
+    if k == 0:
+        hits = None
+    elif hits is None:
+        hits = torch.empty((count, k, HIT_DTYPE.itemsize), dtype=torch.uint8, device=origins.device)
+    elif str(hits.dtype) != "torch.uint8" or not hits.is_contiguous() or not hits.is_cuda or hits.numel() != count * k * HIT_DTYPE.itemsize:
+        raise ValueError("hits must be a contiguous uint8 tensor on the GPU of 48 bytes per record")
+    if counts is None:
+        counts = torch.empty((count,), dtype=torch.int32, device=origins.device)
+    elif str(counts.dtype) != "torch.int32" or not counts.is_contiguous() or not counts.is_cuda or counts.numel() != count:
+        raise ValueError("counts must be a contiguous int32 tensor on the GPU, one per ray")
+    ctx._check(lib().rt_trace_rays_multi_device(ctx._h, scene._h, _dptr(o_ptr), _dptr(d_ptr), _dptr(t_ptr), count, k,
+                                                _dptr(hits.data_ptr() if hits is not None else None), _dptr(counts.data_ptr()), _dptr(stream)))
+    return hits, counts
 
 
 def render_aov(ctx, scene, camera, sky_colour=(0.0, 0.0, 0.0), planes=AOV_PLANES):
