@@ -486,7 +486,7 @@ rt_status rt_render_aov(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam
  * "How far is this point from the scene, and where is the closest surface point?" - the question a particle, a cloth vertex, a
  * distance-field bake or a snap-to-surface asks, which no ray answers: a ray probes one direction somebody chose.  For n points at
  * once, over the records the kernels read (rt_debug_flatten: spheres (c, r), triangles (p0, s1, s2), the meshes' trees).  The
- * distance is UNSIGNED: inside / outside needs watertight meshes and a parity rule for rays through edges, and is out of scope.
+ * distance is UNSIGNED; its sign - inside or outside - comes from the winding-number queries below (rt_signed_distance).
  *
  * The result is DEFINED, not approximated: binary32 + - * / sqrt, comparisons and selects, every operation rounded once (no fused
  * multiply-add), in the order written here, so tests/nearest_ref.py (NumPy float32, every candidate of every point, no traversal)
@@ -539,6 +539,85 @@ rt_status rt_nearest_points_device(rt_ctx *ctx, const rt_scene *scene, const flo
                                    rt_nearest *d_out, void *hip_stream);
 /* Host-buffer form: uploads the points (and limits), answers, downloads the records and returns when they are in `out`. */
 rt_status rt_nearest_points(rt_ctx *ctx, const rt_scene *scene, const float *points, const float *max_dist, int64_t n, rt_nearest *out);
+
+/* ---- winding-number queries: point containment and signed distance -------------------------------
+ * "Is this point inside?" - what a voxeliser, a particle or cloth step, a CSG preview and a signed distance field need, and what no
+ * count of ray crossings answers here: the strict slab test drops hits, a sphere offers one root, and meshes from files are not
+ * watertight.  The answer that survives open, overlapping and leaky meshes is the GENERALIZED WINDING NUMBER (Jacobson, Kavan,
+ * Sorkine-Hornung 2013): the signed solid angle the surface subtends at the point over 4 pi, 1 inside a closed surface, 0 outside, a
+ * fraction near a hole.  Per triangle it is the angle of Van Oosterom and Strackee 1983, summed over the triangle records the kernels
+ * read (rt_debug_flatten).
+ *
+ * Orientation.  The stored records do not all turn the way their faces do: the second triangle of every quad is stored as
+ * (p1, p4, p3), against the first (p1, p2, p3).  So a quad's second record counts negated, and for a mesh the builder keeps one FLIP
+ * bit per triangle - 1 for the second triangle of a quad face of an .obj, 0 for a triangle face and for every triangle of
+ * rt_scene_add_mesh, whose orientation is the caller's - which follows the triangle through the tree build and through
+ * rt_scene_update_mesh[_device] (rt_flat_view.tri_flip).
+ *
+ * The result is DEFINED, like the nearest-surface record: binary32 + - * / sqrt, comparisons and selects, every operation rounded once
+ * (no fused multiply-add), in the order written here, so tests/winding_ref.py (NumPy float32) gives the same bytes.
+ * dot(a, b) = (ax*bx + ay*by) + az*bz; sq(a) = dot(a, a).
+ *
+ * rt_wn_atan2(y, x), no libm:  ay = |y|; ax = |x|; steep = ay > ax; mn = steep ? ax : ay; mx = steep ? ay : ax; q = mn / mx; s = q*q;
+ *   P = C8; P = P*s + C7; ... P = P*s + C0 (Horner, RT_WN_C8 down to RT_WN_C0); r = q*P; r = steep ? RT_WN_PI_2 - r : r;
+ *   r = x < 0 ? RT_WN_PI - r : r; result = y < 0 ? -r : r (the sign bit flipped).  The coefficients are a minimax fit of atan on [0, 1]
+ *   rounded to binary32 (on [0, 1] the polynomial is within 1.72 * 2^-24 of atan); measured against binary64's atan2 over 10^7 random
+ *   arguments the result is within 5.1 * 2^-24 (absolute, radians) - most of it the spacing 2^-22 of the results near pi and the
+ *   rounding of pi itself (tests/winding_ref.py atan2_error, tests/golden/winding_meta.json).
+ * Term of a triangle record (p0, s1, s2) for the point p:
+ *   a = p0 - p; b = a + s1; c = a + s2; la = sqrt(sq(a)); lb = sqrt(sq(b)); lc = sqrt(sq(c));
+ *   nrm = (s1.y*s2.z - s1.z*s2.y, s1.z*s2.x - s1.x*s2.z, s1.x*s2.y - s1.y*s2.x); det = dot(a, nrm);
+ *   den = ((la*lb)*lc + dot(a, b)*lc) + (dot(a, c)*lb + dot(b, c)*la);
+ *   t = 0.0f where det == 0 (the point lies in the triangle's plane: both sides count evenly), else rt_wn_atan2(det, den);
+ *   term = t, or -t (the sign bit flipped) where the record's sign is -1.
+ * Winding number of an object: A = 0.0f; A = A + term over its records in ascending flattened index; w = A * RT_INV_2PI.
+ *   mesh:                every record of its range, signed by the flip bit (-1 where it is 1)
+ *   loose triangle:      its one record, +
+ *   quad, one-way quad:  its two records, the second negated
+ *   sphere (c, r):       no record: 1.0f where sq(p - c) < r*r, else 0.0f
+ *   cuboid:              no record is summed (its near and far faces are stored with the same orientation): 1.0f where lo < p < hi
+ *                        strictly on all three axes, else 0.0f, lo and hi being the componentwise min and max of p0 over its twelve
+ *                        records (every corner coordinate occurs among them)
+ * object >= 0: the answer is that object's w; an open surface (a loose triangle, a quad) gives the fractional value.
+ * object == RT_WINDING_SOLIDS: w = 0.0f; w = w + w_obj over the spheres, cuboids and meshes in list order (loose triangles and quads
+ * are skipped: they enclose nothing).
+ * A point with a NaN or infinite coordinate, and a sum that is a NaN, give w = 0x7FC00000.
+ * inside = |w| >= 0.5f (an inverted mesh still encloses; a NaN is outside).  sdf = inside ? -distance : distance with `distance` from the
+ * rt_nearest record of the same point and w of RT_WINDING_SOLIDS; a miss under a limit gives -RT_HIT_MISS_T or RT_HIT_MISS_T.
+ * The sum is sequential per point and linear in the triangles: a few points against a very large mesh are slow. */
+#define RT_WINDING_SOLIDS (-1)
+#define RT_WN_C0 0x1.fffffcp-1f
+#define RT_WN_C1 (-0x1.555368p-2f)
+#define RT_WN_C2 0x1.994fb6p-3f
+#define RT_WN_C3 (-0x1.2205ap-3f)
+#define RT_WN_C4 0x1.ae096ep-4f
+#define RT_WN_C5 (-0x1.2856fcp-4f)
+#define RT_WN_C6 0x1.45e34ap-5f
+#define RT_WN_C7 (-0x1.d7e76p-7f)
+#define RT_WN_C8 0x1.420206p-9f
+#define RT_WN_PI 0x1.921fb6p+1f         /* pi, pi / 2 and 1 / (2 pi) as the nearest binary32 values */
+#define RT_WN_PI_2 0x1.921fb6p+0f
+#define RT_INV_2PI 0x1.45f306p-3f
+/* Device-buffer form: d_points (n x 3 floats), d_winding (n floats) and d_inside (n bytes, 0 or 1) are device memory of ctx's GPU;
+ * either output may be NULL, not both.  Asynchronous on hip_stream and ordered like rt_nearest_points_device (one launch in flight per
+ * context).  n == 0 succeeds and touches nothing; n < 0, n > 2^30, null points or both outputs null with n > 0, an `object` that is
+ * neither RT_WINDING_SOLIDS nor an index of the scene's object list and a scene committed on another context are RT_ERR_INVALID and
+ * leave the launch order as it was.  The scene's first winding query uploads its flip bytes (and its triangle order, unless an update
+ * already has) before it returns.  rt_last_kernel_ms then reports the kernel.  A scene updated by rt_scene_update_mesh[_device] answers
+ * for its new geometry. */
+rt_status rt_winding_numbers_device(rt_ctx *ctx, rt_scene *scene, const float *d_points, int64_t n, int32_t object, float *d_winding,
+                                    uint8_t *d_inside, void *hip_stream);
+/* Host-buffer form: uploads the points, answers, and returns when the outputs that are not NULL are in host memory. */
+rt_status rt_winding_numbers(rt_ctx *ctx, rt_scene *scene, const float *points, int64_t n, int32_t object, float *winding, uint8_t *inside);
+/* The signed distance of n points: rt_nearest_points_device's launch (d_max_dist: n limits, or NULL) into d_nearest (n records, 16-byte
+ * aligned; NULL: a buffer of the context's), then the winding kernel over RT_WINDING_SOLIDS, which reads the records and writes d_sdf (n
+ * floats) - both on hip_stream, as ONE launch of the context's launch order; rt_last_kernel_ms reports the two together.  Refusals as
+ * above; d_sdf may not be NULL. */
+rt_status rt_signed_distance_device(rt_ctx *ctx, rt_scene *scene, const float *d_points, const float *d_max_dist, int64_t n,
+                                    rt_nearest *d_nearest, float *d_sdf, void *hip_stream);
+/* Host-buffer form: `nearest` (n records) may be NULL. */
+rt_status rt_signed_distance(rt_ctx *ctx, rt_scene *scene, const float *points, const float *max_dist, int64_t n, rt_nearest *nearest,
+                             float *sdf);
 
 /* ---- multi-hit ray queries: the first k hits of a ray, and hit counts ----------------------------
  * What lies BEHIND the first surface: transparency and x-ray views, the thickness of a part along a ray, "select through" picking,
@@ -853,6 +932,10 @@ typedef struct rt_flat_view {
      * refracts or carries a texture; kernel_variant: the render kernel a scene of these traits runs, as rt_scene_info reports it (decided
      * on the host from the traits and RT_AMD_KERNEL_VARIANT alone: rt_debug_flatten needs no device for it) */
     int32_t traits, kernel_variant;
+    /* one byte per triangle record in the flattened order, or NULL without triangles: 1 where a mesh's record is oriented against the face
+     * it came from (the second triangle of a quad face of an .obj), 0 elsewhere and for records of objects that are not meshes: what the
+     * winding-number queries sign a mesh's terms by.  rt_debug_scene_read reports it as the device has it after updates. */
+    const uint8_t *tri_flip;
 } rt_flat_view;
 rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out);
 /* the same view of a committed scene AS IT IS ON THE DEVICE (waits for the device first): what rt_scene_update_mesh[_device] is tested by.

@@ -57,7 +57,7 @@ class rt_flat_view(C.Structure):
                 ("stack_entries", C.c_int32), ("objects", C.c_void_p),
                 ("num_objects", C.c_int32), ("object_stride", C.c_int32), ("tri_uv", C.POINTER(C.c_float)),
                 ("num_triangles", C.c_int32), ("num_nodes", C.c_int32), ("has_mesh", C.c_int32),
-                ("traits", C.c_int32), ("kernel_variant", C.c_int32)]
+                ("traits", C.c_int32), ("kernel_variant", C.c_int32), ("tri_flip", C.POINTER(C.c_uint8))]
 
 
 class rt_denoise_params(C.Structure):
@@ -88,7 +88,8 @@ HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
 # rt_nearest (include/rt_amd.h) as a NumPy record: what nearest_points returns.  A miss: distance and distance2 HIT_MISS_T, object -1
 NEAREST_DTYPE = np.dtype([("distance", np.float32), ("distance2", np.float32), ("point", np.float32, (3,)), ("object", np.int32),
                           ("triangle", np.int32), ("reserved", np.int32)])
-MULTIHIT_MAX = 8                                    # RT_MULTIHIT_MAX: the most records per ray of trace_rays_multi
+WINDING_SOLIDS = -1                                 # RT_WINDING_SOLIDS: the `object` that asks for the sum over the spheres, cuboids and meshes
+MULTIHIT_MAX = 8                                  # RT_MULTIHIT_MAX: the most records per ray of trace_rays_multi
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
 VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
 AO_PLANES = ("ao", "count")
@@ -178,6 +179,10 @@ ABI = {
     "rt_render_aov": (st, [vp, vp, cam, fp, fp, fp, fp, i32p, fp]),
     "rt_nearest_points_device": (st, [vp, vp, vp, vp, i64, vp, vp]),
     "rt_nearest_points": (st, [vp, vp, fp, fp, i64, vp]),
+    "rt_winding_numbers_device": (st, [vp, vp, vp, i64, i32, vp, vp, vp]),
+    "rt_winding_numbers": (st, [vp, vp, fp, i64, i32, fp, vp]),
+    "rt_signed_distance_device": (st, [vp, vp, vp, vp, i64, vp, vp, vp]),
+    "rt_signed_distance": (st, [vp, vp, fp, fp, i64, vp, fp]),
     "rt_trace_rays_multi_device": (st, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
     "rt_trace_rays_multi": (st, [vp, vp, fp, fp, fp, i64, i32, vp, i32p]),
     "rt_occluded_rays_device": (st, [vp, vp, vp, vp, vp, i64, vp, vp]),

@@ -186,7 +186,8 @@ struct BvhBuilder {
     }
 };
 
-rt_status add_mesh_tris(rt_scene_builder *b, const std::vector<HostTri> &tris, const std::vector<std::array<F3, 3>> &pts, const rt_material *m)
+/* flip: one byte per triangle as given, 1 where the record is oriented against its face (empty: none is) */
+rt_status add_mesh_tris(rt_scene_builder *b, const std::vector<HostTri> &tris, const std::vector<std::array<F3, 3>> &pts, const rt_material *m, std::vector<uint8_t> flip = {})
 {
     HostObject o;
     o.type = RT_OBJ_MESH;
@@ -203,6 +204,8 @@ rt_status add_mesh_tris(rt_scene_builder *b, const std::vector<HostTri> &tris, c
     o.tris.reserve(tris.size());
     for (int i : bb.order) o.tris.push_back(tris[i]);
     o.order = std::move(bb.order);
+    flip.resize(tris.size(), 0);
+    o.flip = std::move(flip);
     keep_texels(o);
     b->objs.push_back(std::move(o));
     return RT_OK;
@@ -477,6 +480,7 @@ extern "C" rt_status rt_scene_add_obj_mesh(rt_scene_builder *b, const rt_obj *o,
     /* SceneObjects::create_mesh src/main.cu:127-148 */
     std::vector<HostTri> tris;
     std::vector<std::array<F3, 3>> pts;
+    std::vector<uint8_t> flip;           /* make_quad's second triangle (p1, p4, p3) turns the other way than its first */
     auto vert = [&](int vi) { return f3(o->vx[(size_t)vi], o->vy[(size_t)vi], o->vz[(size_t)vi]); };
     for (const auto &face : o->faces) {
         for (int vi : face)
@@ -485,16 +489,19 @@ extern "C" rt_status rt_scene_add_obj_mesh(rt_scene_builder *b, const rt_obj *o,
             F3 a = vert(face[0]), bb = vert(face[1]), c = vert(face[2]);
             tris.push_back(make_tri(a, bb, c));
             pts.push_back({a, bb, c});
+            flip.push_back(0);
         } else if (face.size() == 4) {
             F3 p1 = vert(face[0]), p2 = vert(face[1]), p3 = vert(face[2]), p4 = vert(face[3]);
             make_quad(tris, p1, p2, p3, p4);
             pts.push_back({p1, p2, p3});
             pts.push_back({p1, p4, p3});
+            flip.push_back(0);
+            flip.push_back(1);
         } else {
             return fail(b, RT_ERR_UNSUPPORTED, "Only triangle or quad meshes are supported.\n");
         }
     }
-    return add_mesh_tris(b, tris, pts, m);
+    return add_mesh_tris(b, tris, pts, m, std::move(flip));
 }
 
 /* ================================ C ABI: .obj loader ======================================= */
@@ -721,6 +728,8 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
     out.num_tris = (int)n_tris;
     if (any_uv) out.tri_uv.resize(n_tris * 6, 0.0f);
     out.tri_order.assign(n_tris, 0);
+    out.tri_flip.assign(n_tris, 0);
+    out.tri_flip_commit.assign(n_tris, 0);
 
     size_t node_base = 0, tri_base = 0, mesh_i = 0;
     for (size_t oi = 0; oi < b.objs.size(); oi++) {
@@ -766,6 +775,8 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
             q[2] = rt_f4{t.s2[2], t.n[0], t.n[1], t.n[2]};
             if (any_uv) std::memcpy(&out.tri_uv[(tri_base + k) * 6], t.uv, 24);
             if (k < o.order.size()) out.tri_order[tri_base + k] = (int32_t)o.order[k];
+            if (k < o.order.size() && (size_t)o.order[k] < o.flip.size()) out.tri_flip[tri_base + k] = o.flip[(size_t)o.order[k]];
+            if (o.type == RT_OBJ_MESH && k < o.flip.size()) out.tri_flip_commit[tri_base + k] = o.flip[k];
         }
         /* per-object shading record */
         const rt_material &m = o.mat;
@@ -816,5 +827,6 @@ extern "C" rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out)
     out->has_mesh = f.has_mesh ? 1 : 0;
     out->traits = (int32_t)f.traits;
     out->kernel_variant = rt_sched::choose_variant(f.traits, rt_sched::variant_forced_generic(getenv("RT_AMD_KERNEL_VARIANT")));
+    out->tri_flip = f.tri_flip.empty() ? nullptr : f.tri_flip.data();
     return RT_OK;
 }

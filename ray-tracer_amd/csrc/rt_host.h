@@ -23,6 +23,7 @@ struct HostObject {
     std::vector<HostTri> tris;           /* top-level shapes: 1 / 2 / 12; meshes: leaf order */
     std::vector<rt_node> nodes;          /* meshes: child refs relative to this object */
     std::vector<int> order;              /* meshes: order[k] = the index, in the order the triangles were given, of the one at leaf position k */
+    std::vector<uint8_t> flip;           /* meshes, in the order the triangles were given: 1 where the record's orientation is opposite to its face's (make_quad's second triangle) */
     std::vector<float> texels;           /* IMAGE texture: a copy of the caller's rgb data */
     uint32_t root_ref = RT_REF_EMPTY_LEAF;
     int stack_need = 0;
@@ -51,6 +52,8 @@ struct FlatScene {
     std::vector<rt_object> objects;
     std::vector<float> tri_uv;                   /* empty unless some material needs UVs */
     std::vector<int32_t> tri_order;              /* per triangle of a mesh: its index in the mesh's commit order (HostObject::order); others: 0 */
+    std::vector<uint8_t> tri_flip;               /* per triangle record: HostObject::flip of the one at that position (a mesh's), others: 0 */
+    std::vector<uint8_t> tri_flip_commit;        /* the same bytes with every mesh's range in its commit order: [prim_start + commit index] (what the device is handed, rt_winding_capi.cpp) */
     std::vector<float> tex_data;                 /* IMAGE texels of all objects, back to back */
     int num_tris = 0, num_nodes = 0;
     bool has_mesh = false;

@@ -267,6 +267,7 @@ struct rt_scene {
     rt_ctx *ctx = nullptr;
     std::map<int32_t, MeshUpdate> updates;   /* by object index */
     DevBuf<int32_t> d_perm;              /* per triangle of a mesh: the commit index of the one at that leaf position, as of the last update */
+    DevBuf<uint32_t> d_flip;             /* flat.tri_flip_commit, four bytes to a word: made at the scene's first winding-number query (rt_winding_capi.cpp) */
     FlatScene debug_read;                /* rt_debug_scene_read's copy of what is on the device */
     /* (members go in reverse order: the blob is freed first, the texels last) */
     DevBuf<float> d_tex;
@@ -385,6 +386,22 @@ inline rt_status check_rays(rt_ctx *ctx, const rt_scene *scene, const void *orig
     if (st != RT_OK) return st;
     if (n < 0 || n > RT_QUERY_MAX_RAYS) return set_err(ctx, RT_ERR_INVALID, "bad ray count (0 .. 2^30)");
     if (n > 0 && (!origins || !directions || !answers)) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    return RT_OK;
+}
+
+/* The scene's "leaf position -> commit index" list on the device, made by whoever needs it first: a mesh's first update (rt_update_capi.cpp:
+ * the rebuild kernels keep it current from then on) or the scene's first winding-number query (rt_winding_capi.cpp reads it).  It starts as
+ * the flattener's tri_order.  A failure leaves the scene without the list, as it was. */
+inline rt_status ensure_scene_perm(rt_ctx *ctx, rt_scene *scene)
+{
+    if (scene->d_perm.p) return RT_OK;
+    const std::vector<int32_t> &order = scene->flat.tri_order;
+    RT_HIP(ctx, scene->d_perm.grow(order.size()), "allocating the scene's triangle order");
+    const hipError_t e = order.empty() ? hipSuccess : hipMemcpy(scene->d_perm.p, order.data(), order.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        scene->d_perm.release();
+        return hip_fail(ctx, e, "uploading the scene's triangle order");
+    }
     return RT_OK;
 }
 

@@ -96,11 +96,7 @@ rt_status fill_mesh(rt_ctx *ctx, rt_scene *scene, int32_t object_index, MeshUpda
         RT_HIP(ctx, m.d_uv0.grow(uv0.size()), "allocating the mesh's texture coordinates");
         RT_HIP(ctx, hipMemcpy(m.d_uv0.p, uv0.data(), uv0.size() * 4, hipMemcpyHostToDevice), "uploading the mesh's texture coordinates");
     }
-    if (!scene->d_perm.p) {
-        RT_HIP(ctx, scene->d_perm.grow(f.tri_order.size()), "allocating the scene's triangle order");
-        RT_HIP(ctx, hipMemcpy(scene->d_perm.p, f.tri_order.data(), f.tri_order.size() * 4, hipMemcpyHostToDevice), "uploading the scene's triangle order");
-    }
-    return RT_OK;
+    return ensure_scene_perm(ctx, scene);
 }
 
 /* ... made at the mesh's first update and kept with the scene */
@@ -199,6 +195,21 @@ extern "C" rt_status rt_debug_scene_read(rt_ctx *ctx, rt_scene *scene, rt_flat_v
     if (!r.blob.empty()) RT_HIP(ctx, hipMemcpy(r.blob.data(), scene->d_blob.p, r.blob.size() * sizeof(rt_f4), hipMemcpyDeviceToHost), "reading the scene");
     if (!r.objects.empty()) RT_HIP(ctx, hipMemcpy(r.objects.data(), scene->d_objects.p, r.objects.size() * sizeof(rt_object), hipMemcpyDeviceToHost), "reading the scene");
     if (!r.tri_uv.empty()) RT_HIP(ctx, hipMemcpy(r.tri_uv.data(), scene->d_tri_uv.p, r.tri_uv.size() * 4, hipMemcpyDeviceToHost), "reading the scene");
+    /* the flip bytes as a winding-number query finds them: the commit-order bytes through the device's list of who sits where */
+    r.tri_flip = f.tri_flip;
+    if (scene->d_perm.p && !f.tri_order.empty()) {
+        std::vector<int32_t> perm(f.tri_order.size());
+        RT_HIP(ctx, hipMemcpy(perm.data(), scene->d_perm.p, perm.size() * 4, hipMemcpyDeviceToHost), "reading the scene");
+        for (size_t oi = 0; oi < f.objects.size(); oi++) {
+            if (f.objects[oi].type != RT_OBJ_MESH) continue;
+            const size_t base = (size_t)f.objects[oi].prim_start, n = (size_t)mesh_count(f, oi);
+            for (size_t k = 0; k < n; k++) {
+                const size_t from = (size_t)perm[base + k];
+                r.tri_flip[base + k] = from < n ? f.tri_flip_commit[base + from] : 0xFF;    /* (0xFF: a list entry outside its mesh) */
+            }
+        }
+    }
+    out->tri_flip = r.tri_flip.empty() ? nullptr : r.tri_flip.data();
     out->blob = reinterpret_cast<const float *>(r.blob.data());
     out->blob_f4 = (int32_t)r.blob.size();
     out->off_nodes = f.off_nodes;

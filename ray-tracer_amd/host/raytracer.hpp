@@ -508,6 +508,35 @@ public:
         check(rt_nearest_points(ctx_, scene_, point.data(), &max_dist, 1, &r));
         return r;
     }
+    /* The generalized winding number of every point (rt_winding_numbers): points holds n x 3 floats; object an index of the scene's object
+     * list, or RT_WINDING_SOLIDS for the sum over its spheres, cuboids and meshes.  1 (or -1) inside a closed surface, 0 outside. */
+    std::vector<float> winding_numbers(const std::vector<float> &points, int32_t object = RT_WINDING_SOLIDS)
+    {
+        if (points.size() % 3 != 0) throw std::invalid_argument("points must hold n x 3 floats");
+        std::vector<float> w(points.size() / 3);
+        check(rt_winding_numbers(ctx_, scene_, points.data(), (int64_t)w.size(), object, w.data(), nullptr));
+        return w;
+    }
+    /* Which points lie inside: 1 where |winding number| >= 0.5 */
+    std::vector<uint8_t> contains(const std::vector<float> &points, int32_t object = RT_WINDING_SOLIDS)
+    {
+        if (points.size() % 3 != 0) throw std::invalid_argument("points must hold n x 3 floats");
+        std::vector<uint8_t> in(points.size() / 3);
+        check(rt_winding_numbers(ctx_, scene_, points.data(), (int64_t)in.size(), object, nullptr, in.data()));
+        return in;
+    }
+    /* The signed distance of every point (rt_signed_distance): negative inside the scene's solids; max_dist n limits, or none.  `records`,
+     * if given, receives the nearest-surface records the magnitudes come from. */
+    std::vector<float> signed_distance(const std::vector<float> &points, const std::vector<float> &max_dist = {}, std::vector<rt_nearest> *records = nullptr)
+    {
+        if (points.size() % 3 != 0) throw std::invalid_argument("points must hold n x 3 floats");
+        std::vector<float> sdf(points.size() / 3);
+        if (!max_dist.empty() && max_dist.size() != sdf.size()) throw std::invalid_argument("max_dist must hold n floats, or none");
+        if (records) records->resize(sdf.size());
+        check(rt_signed_distance(ctx_, scene_, points.data(), max_dist.empty() ? nullptr : max_dist.data(), (int64_t)sdf.size(), records ? records->data() : nullptr,
+                                 sdf.data()));
+        return sdf;
+    }
     /* The first k hits of every ray in order along it (rt_trace_rays_multi): origins, directions hold n x 3 floats, tmax n limits or none;
      * k from 1 to RT_MULTIHIT_MAX.  hits holds n * k records, [ray][rank], the ones behind a ray's last hit being misses; counts the records
      * each ray has. */

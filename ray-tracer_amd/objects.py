@@ -166,7 +166,8 @@ def _flat_view_arrays(v):
     raw = C.string_at(v.objects, v.num_objects * v.object_stride) if v.num_objects else b""
     objs = np.frombuffer(raw, dtype=np.dtype([("type", "<i4"), ("prim_start", "<i4"), ("need_uv", "<i4"), ("root_ref", "<u4"), ("v", "<f4", (8,))]))
     uv = np.ctypeslib.as_array(v.tri_uv, shape=(v.num_triangles, 6)).copy() if v.tri_uv else None
-    return {"blob": blob, "off_nodes": v.off_nodes, "off_tris": v.off_tris, "off_objlds": v.off_objlds,
+    flip = np.ctypeslib.as_array(v.tri_flip, shape=(v.num_triangles,)).copy() if v.tri_flip and v.num_triangles else np.zeros(0, np.uint8)
+    return {"blob": blob, "tri_flip": flip, "off_nodes": v.off_nodes, "off_tris": v.off_tris, "off_objlds": v.off_objlds,
             "off_meshes": v.off_meshes, "num_meshes": v.num_meshes, "stack_entries": v.stack_entries,
             "objects": objs, "tri_uv": uv, "num_triangles": v.num_triangles, "num_nodes": v.num_nodes,
             "has_mesh": bool(v.has_mesh),

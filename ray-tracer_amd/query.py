@@ -1,10 +1,11 @@
 """Queries: closest hits and first-hit planes, multi-hit queries (the first k hits of a ray, hit counts), occlusion (any-hit), the
-light-visibility plane, the ambient-occlusion plane, and the nearest-surface queries (closest point and distance, which are no ray questions)."""
+light-visibility plane, the ambient-occlusion plane, the nearest-surface queries (closest point and distance, which are no ray questions), and
+the winding-number queries (point containment, the signed distance)."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -258,3 +259,120 @@ def distance_grid(scene, lo, hi, shape, max_dist=None, stream=None):
     rec = nearest_points_device(ctx, scene, pts, lim, stream=stream)
     dist = rec.view(torch.float32).reshape(-1, 8)[:, 0].reshape(int(shape[0]), int(shape[1]), int(shape[2]))
     return dist, rec
+
+
+def _lattice(scene, lo, hi, shape):
+    """shape = (nx, ny, nz) points from corner lo to corner hi inclusive as a float32 tensor [nx * ny * nz, 3] on the scene's GPU, x slowest"""
+    import torch
+    dev = torch.device("cuda", scene.ctx.device)
+    axes = []
+    for k in range(3):
+        m = int(shape[k])
+        if m < 1:
+            raise ValueError("shape must be at least 1 along every axis")
+        axes.append(torch.linspace(float(lo[k]), float(hi[k]), m, dtype=torch.float32, device=dev) if m > 1
+                    else torch.full((1,), float(lo[k]), dtype=torch.float32, device=dev))
+    gx, gy, gz = torch.meshgrid(axes[0], axes[1], axes[2], indexing="ij")
+    return torch.stack((gx, gy, gz), dim=-1).reshape(-1, 3).contiguous()
+
+
+def winding_numbers(ctx, scene, points, object=WINDING_SOLIDS, inside=False):
+    """The generalized winding number of every point (rt_winding_numbers): points [n, 3] float32; object an index of the scene's object list,
+    or WINDING_SOLIDS for the sum over its spheres, cuboids and meshes.  Returns n float32 - 1 (or -1 for an inverted mesh) inside a closed
+    surface, 0 outside, a fraction near a hole or for an open surface, NaN for a point that is not finite - and with inside=True the pair
+    (winding, inside): inside n uint8, 1 where |w| >= 0.5."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    w = np.zeros(n, np.float32)
+    flags = np.zeros(n, np.uint8) if inside else None
+    ctx._check(lib().rt_winding_numbers(ctx._h, scene._h, _fp(p)[1], n, int(object), _fp(w)[1], C.c_void_p(flags.ctypes.data) if inside else None))
+    return (w, flags) if inside else w
+
+
+def contains_points(ctx, scene, points, object=WINDING_SOLIDS):
+    """Which points lie inside (rt_winding_numbers, the containment bytes alone): n bool, True where |w| >= 0.5."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    flags = np.zeros(p.shape[0], np.uint8)
+    ctx._check(lib().rt_winding_numbers(ctx._h, scene._h, _fp(p)[1], p.shape[0], int(object), None, C.c_void_p(flags.ctypes.data)))
+    return flags.astype(bool)
+
+
+def winding_numbers_device(ctx, scene, points, object=WINDING_SOLIDS, winding=None, inside=None, n=None, stream=None):
+    """Device-buffer form (rt_winding_numbers_device), asynchronous on `stream` (a hipStream_t as an int; None: the default stream) and in the
+    context's launch order.  `points` is a float32 torch tensor of 3 n elements on the scene's GPU, `winding` None or a float32 tensor of
+    n, `inside` None or a uint8 tensor of n: returns (winding, inside), with a new winding tensor where neither was passed.  Or all three
+    are device pointers as ints (one of the outputs may be None) together with n."""
+    if isinstance(points, int):
+        if n is None:
+            raise ValueError("device pointers need n, the number of points")
+        ctx._check(lib().rt_winding_numbers_device(ctx._h, scene._h, _dptr(points), int(n), int(object), _dptr(winding), _dptr(inside), _dptr(stream)))
+        return winding, inside
+    import torch
+    ptr, count = _device_floats(points, 3, "points")
+    if n is not None and int(n) != count:
+        raise ValueError("n differs from the points given")
+    if winding is None and inside is None:
+        winding = torch.empty((count,), dtype=torch.float32, device=points.device)
+    if winding is not None and (str(winding.dtype) != "torch.float32" or not winding.is_contiguous() or not winding.is_cuda or winding.numel() != count):
+        raise ValueError("winding must be a contiguous float32 tensor on the GPU, one per point")
+    if inside is not None and (str(inside.dtype) != "torch.uint8" or not inside.is_contiguous() or not inside.is_cuda or inside.numel() != count):
+        raise ValueError("inside must be a contiguous uint8 tensor on the GPU, one per point")
+    ctx._check(lib().rt_winding_numbers_device(ctx._h, scene._h, _dptr(ptr), count, int(object), _dptr(winding.data_ptr() if winding is not None else None),
+                                               _dptr(inside.data_ptr() if inside is not None else None), _dptr(stream)))
+    return winding, inside
+
+
+def signed_distance(ctx, scene, points, max_dist=None):
+    """The signed distance of every point (rt_signed_distance): negative inside the scene's solids (|winding number| >= 0.5), positive
+    outside; max_dist as for nearest_points.  Returns (sdf, records): n float32 and the n NearestRecord the magnitudes come from; a miss
+    under a limit is -HIT_MISS_T or HIT_MISS_T."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    lim = _limits(max_dist, n)
+    rec = np.zeros(n, NEAREST_DTYPE)
+    sdf = np.zeros(n, np.float32)
+    ctx._check(lib().rt_signed_distance(ctx._h, scene._h, _fp(p)[1], _fp(lim)[1] if lim is not None else None, n, C.c_void_p(rec.ctypes.data), _fp(sdf)[1]))
+    return sdf, rec
+
+
+def signed_distance_device(ctx, scene, points, max_dist=None, sdf=None, records=None, n=None, stream=None):
+    """Device-buffer form (rt_signed_distance_device), asynchronous on `stream` and in the context's launch order.  `points` is a float32 torch
+    tensor of 3 n elements on the scene's GPU, `max_dist` None or one of n, `sdf` None or a float32 tensor of n, `records` None (the
+    context keeps them) or a uint8 tensor of 32 n bytes: returns (sdf, records).  Or all are device pointers as ints together with n."""
+    if isinstance(points, int):
+        if n is None or sdf is None:
+            raise ValueError("device pointers need n, the number of points, and sdf")
+        ctx._check(lib().rt_signed_distance_device(ctx._h, scene._h, _dptr(points), _dptr(max_dist), int(n), _dptr(records), _dptr(sdf), _dptr(stream)))
+        return sdf, records
+    import torch
+    ptr, count = _device_floats(points, 3, "points")
+    if n is not None and int(n) != count:
+        raise ValueError("n differs from the points given")
+    lim_ptr = None
+    if max_dist is not None:
+        lim_ptr, n_lim = _device_floats(max_dist, 1, "max_dist")
+        if n_lim != count:
+            raise ValueError("max_dist must hold one limit per point")
+    if sdf is None:
+        sdf = torch.empty((count,), dtype=torch.float32, device=points.device)
+    elif str(sdf.dtype) != "torch.float32" or not sdf.is_contiguous() or not sdf.is_cuda or sdf.numel() != count:
+        raise ValueError("sdf must be a contiguous float32 tensor on the GPU, one per point")
+    if records is not None and (str(records.dtype) != "torch.uint8" or not records.is_contiguous() or not records.is_cuda or records.numel() != count * NEAREST_DTYPE.itemsize):
+        raise ValueError("records must be a contiguous uint8 tensor on the GPU of 32 bytes per point")
+    ctx._check(lib().rt_signed_distance_device(ctx._h, scene._h, _dptr(ptr), _dptr(lim_ptr), count, _dptr(records.data_ptr() if records is not None else None),
+                                               _dptr(sdf.data_ptr()), _dptr(stream)))
+    return sdf, records
+
+
+def signed_distance_grid(scene, lo, hi, shape, max_dist=None, stream=None):
+    """The scene's SIGNED distance field on distance_grid's lattice, answered by signed_distance_device without a host round trip.  Returns
+    (sdf, records): a float32 tensor [nx, ny, nz], negative inside, and the uint8 records [nx * ny * nz, 32], x slowest."""
+    import torch
+    ctx = scene.ctx
+    pts = _lattice(scene, lo, hi, shape)
+    lim = None if max_dist is None else torch.full((pts.shape[0],), float(max_dist), dtype=torch.float32, device=pts.device)
+    if stream is None:
+        stream = torch.cuda.current_stream(pts.device).cuda_stream      # the lattice was produced on it: the query is queued behind
+    rec = torch.empty((pts.shape[0], NEAREST_DTYPE.itemsize), dtype=torch.uint8, device=pts.device)
+    sdf, _ = signed_distance_device(ctx, scene, pts, lim, records=rec, stream=stream)
+    return sdf.reshape(int(shape[0]), int(shape[1]), int(shape[2])), rec
