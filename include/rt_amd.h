@@ -948,9 +948,6 @@ rt_status rt_debug_scene_read(rt_ctx *ctx, rt_scene *scene, rt_flat_view *out);
  * was handed a plane else 0, the plane's image width, its height, its 32-bit words: pixel py * width + px is bit (pixel & 31) of word
  * pixel >> 5}; words may be NULL or capacity_words too small: then only info4 is written. */
 rt_status rt_debug_primary_cull(rt_ctx *ctx, uint32_t *words, int32_t capacity_words, int32_t *info4);
-/* 1 if the library holds the pre-pass kernel's launcher - every build of the library does, tests/test_primary_cull.py checks it -, 0 in a host
- * program that links the C ABI's translation units without the kernels (its launches render without a plane) */
-int32_t rt_debug_primary_cull_linked(void);
 /* the same plane computed on the HOST (no device is touched) from a flattened scene - rt_debug_flatten's view or rt_debug_scene_read's - with the
  * same predicate.  words: ((width * height + 63) / 64) * 2 of them, or NULL.  stats6, or NULL: {pixels whose jitter cone may enter some mesh's
  * root box, those of them that are flagged, nodes the centre direction visits in the flagged ones, ... in all root-entering pixels, flagged

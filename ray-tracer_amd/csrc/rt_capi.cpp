@@ -27,12 +27,6 @@
 
 #include "rt_internal.h"
 
-/* The pre-pass's launcher is referenced weakly: the host programs that link this file without rt_kernel.hip (tests/sanitize/: some of them
- * create contexts over a stand-in for the HIP runtime) go on linking without a stub for it, and render without a plane.  In the library the
- * kernel is always there: rt_debug_primary_cull_linked says so and tests/test_primary_cull.py holds every build to it, so that a library which
- * lost the kernel fails a CPU test instead of quietly rendering every launch without a plane */
-#pragma weak rt_cull_enqueue
-
 std::mutex rt_detail::g_ctx_mutex;
 
 namespace {
@@ -684,7 +678,7 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
 {
     CullPlane &cp = ctx->cull;
     const rt_shape &sh = scene->kernel.shape;
-    const bool enabled = cp.enabled && rt_cull_enqueue != nullptr && scene->flat.num_meshes > 0 && rt_loop_culls(sh.has_mesh, sh.mode, sh.threads, sh.variant);
+    const bool enabled = cp.enabled && scene->flat.num_meshes > 0 && rt_loop_culls(sh.has_mesh, sh.mode, sh.threads, sh.variant);
     rt_cull_host::Key k;
     k.scene_uid = scene->uid;
     camera_floats(*cam, k.cam);
@@ -704,8 +698,8 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
             for (FrameSlot &fs : ctx->pipe.slots)
                 if (fs.used && &fs != slot) ok = ok && hipEventSynchronize(fs.ev_done) == hipSuccess;
         if (ok && !cp.ev.e) ok = hipEventCreateWithFlags(&cp.ev.e, hipEventDisableTiming) == hipSuccess;
-        ok = ok && rt_cull_enqueue(k.cam, k.width, k.height, k.antialias, scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
-                                   scene->flat.num_meshes, cp.d.p, stream) == hipSuccess;
+        ok = ok && rt_launch_cull(k.cam, k.width, k.height, k.antialias, scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
+                                  scene->flat.num_meshes, cp.d.p, stream) == hipSuccess;
         ok = ok && hipEventRecord(cp.ev, stream) == hipSuccess;
         cp.stream = stream;
         cp.plan.ran(k, ok);
@@ -901,8 +895,6 @@ extern "C" rt_status rt_debug_primary_cull(rt_ctx *ctx, uint32_t *words, int32_t
     RT_HIP(ctx, hipMemcpy(words, cp.d.p, n * 4, hipMemcpyDeviceToHost), "reading the cull plane");
     return RT_OK;
 }
-
-extern "C" int32_t rt_debug_primary_cull_linked(void) { return rt_cull_enqueue != nullptr ? 1 : 0; }
 
 /* test / development hook, host only (no device is touched): the predicate of rt_cull.h evaluated per pixel of `cam`'s image on a flattened
  * scene (rt_debug_flatten's view, or rt_debug_scene_read's).  words: rt_cull_words-many, or NULL.  stats6, or NULL: {pixels whose cone may

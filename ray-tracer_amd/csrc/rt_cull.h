@@ -1,8 +1,8 @@
 /*
  * rt_cull.h — the primary-ray cull: one bit per pixel of a view, "no primary ray of this pixel can reach a leaf of any mesh".  Host and
  * device: the predicate (rt_cull_cone, rt_cull_box_missed), the walk over a flattened scene (rt_cull_no_leaf), the slab test's three forms
- * restated for the host (rt_cull_slab_*: rt_intersect.h is device code), the host's bookkeeping of the plane (rt_cull_host) and the
- * pre-pass kernel's launcher (defined in rt_cull_kernel.h).  DESIGN.md section 24 has the argument and the figures.
+ * restated for the host (rt_cull_slab_*: rt_intersect.h is device code) and the host's bookkeeping of the plane (rt_cull_host); the
+ * pre-pass kernel's launcher is rt_launch.h's rt_launch_cull (defined in rt_cull_kernel.h).  DESIGN.md section 24 has the argument and the figures.
  *
  * WHY THE FRAMES STAY BIT-IDENTICAL.  A primary ray of a flagged pixel fails the float slab test of at least one box on every root-to-leaf
  * path of every mesh, so the traversal that the render kernel would run for it tests no triangle and ends with w_prim == -1: its merge is
@@ -263,15 +263,5 @@ struct Plan {
 };
 
 }  // namespace rt_cull_host
-
-#if defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
-#include <hip/hip_runtime_api.h>
-extern "C" {
-/* rt_cull_kernel.h: the pre-pass on `stream` - one thread per pixel of the width x height image of camera `cam`, the scene's blob walked
- * in global memory; writes rt_cull_words(width, height) words of `plane`, a set bit: the pixel's primary rays reach no leaf of any mesh */
-hipError_t rt_cull_enqueue(const float *cam, int32_t width, int32_t height, int32_t antialias, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
-                           int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream);
-}
-#endif
 
 #endif

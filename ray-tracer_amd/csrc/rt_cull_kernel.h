@@ -11,6 +11,7 @@
 
 #include "rt_cull.h"
 #include "rt_device_scene.h"
+#include "rt_launch.h"
 
 #define RT_CULL_THREADS 256
 
@@ -52,8 +53,8 @@ __global__ __launch_bounds__(RT_CULL_THREADS) void rt_cull_kernel(const rt_cull_
     }
 }
 
-extern "C" hipError_t rt_cull_enqueue(const float *cam, int32_t width, int32_t height, int32_t antialias, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
-                                      int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream)
+extern "C" hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t height, int32_t antialias, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
+                                     int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream)
 {
     if (!cam || !blob || !plane || width <= 0 || height <= 0 || num_nodes < 0 || num_meshes < 0) return hipErrorInvalidValue;
     rt_cull_args a;

@@ -3,7 +3,8 @@
  * Stream), the context and its parts (rt_ctx: the tile-list cache, the view, the frame pipeline, the multi-GPU rank state, the knobs), the
  * committed scene (rt_scene), the error helpers, the functions of rt_capi.cpp that the other translation units call, the host-buffer round
  * trip and, at the end, what the entry points beside the renderer (rt_query_capi.cpp, rt_occlusion_capi.cpp, rt_ao_capi.cpp,
- * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp, rt_sky_capi.cpp, rt_update_capi.cpp) have in common: the argument checks, the context's launch bracket and the
+ * rt_denoise_capi.cpp, rt_adaptive_capi.cpp, rt_views_capi.cpp, rt_sky_capi.cpp, rt_update_capi.cpp, rt_nearest_capi.cpp, rt_multihit_capi.cpp,
+ * rt_winding_capi.cpp) have in common: the argument checks, the context's launch bracket and the
  * ray kernels' argument block and launch.  It includes rt_launch.h, the kernel launchers' declarations: no translation unit declares one
  * itself.  rt_capi.cpp owns the life cycle (rt_ctx_create / rt_ctx_destroy, rt_scene_commit).  Not installed: include/rt_amd.h is the interface.
  */
@@ -19,11 +20,11 @@
 #include <string>
 #include <vector>
 
-#include "rt_cull.h"           /* the primary-ray cull: its plane's bookkeeping, and its pre-pass's launcher (apart from rt_launch.h's, like rt_sky.h's) */
+#include "rt_cull.h"           /* the primary-ray cull: its plane's bookkeeping */
 #include "rt_host.h"
 #include "rt_launch.h"         /* the kernel launchers: the seam to rt_kernel.hip */
 #include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
-#include "rt_rebuild.h"        /* the per-mesh plan of rt_scene_update_mesh, and its kernels' launcher */
+#include "rt_rebuild.h"        /* the per-mesh plan of rt_scene_update_mesh */
 #include "rt_schedule.h"
 
 /* what crosses the library's translation units without being part of its interface: not in the dynamic symbol table */
@@ -389,6 +390,17 @@ inline rt_status check_rays(rt_ctx *ctx, const rt_scene *scene, const void *orig
     return RT_OK;
 }
 
+/* n points on a scene (rt_nearest_capi.cpp, rt_winding_capi.cpp; where the answers go is the caller's to check) */
+static_assert(RT_NEAREST_MAX_POINTS == RT_WINDING_MAX_POINTS, "one check serves both families");
+inline rt_status check_points(rt_ctx *ctx, const rt_scene *scene, const void *points, int64_t n)
+{
+    rt_status st = check_scene(ctx, scene);
+    if (st != RT_OK) return st;
+    if (n < 0 || n > RT_NEAREST_MAX_POINTS) return set_err(ctx, RT_ERR_INVALID, "bad point count (0 .. 2^30)");
+    if (n > 0 && !points) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    return RT_OK;
+}
+
 /* The scene's "leaf position -> commit index" list on the device, made by whoever needs it first: a mesh's first update (rt_update_capi.cpp:
  * the rebuild kernels keep it current from then on) or the scene's first winding-number query (rt_winding_capi.cpp reads it).  It starts as
  * the flattener's tri_order.  A failure leaves the scene without the list, as it was. */
@@ -473,15 +485,21 @@ Args ray_args_view(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *ca
     return a;
 }
 
-/* One launch of a ray kernel (`launcher`: rt_launch_query, rt_launch_occlusion or rt_launch_ao, with its `front`) on `stream`, in the launch bracket: the
- * ticket counter is shared with the render launches. */
+/* A ray kernel of the scene's shape queued on `stream` behind the clearing of its ticket counter (`launcher`: rt_launch_query, rt_launch_occlusion,
+ * rt_launch_ao, rt_launch_nearest or rt_launch_multihit, with its `front`).  Without the bracket: for the work of a caller that is inside one. */
+template <class Args>
+rt_status enqueue_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), bool front,
+                       const char *what_clear, const char *what, hipStream_t stream)
+{
+    RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), what_clear);
+    RT_HIP(ctx, launcher(&a, scene->kernel.shape, front ? 1 : 0, ctx->num_cus, scene->kernel.lds_bytes, stream), what);
+    return RT_OK;
+}
+
+/* One launch of a ray kernel in the launch bracket: the ticket counter is shared with the render launches. */
 template <class Args>
 rt_status launch_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), bool front,
                       const char *what, hipStream_t stream)
 {
-    return launch_bracket(ctx, stream, [&]() -> rt_status {
-        RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), "clearing the ray counter");
-        RT_HIP(ctx, launcher(&a, scene->kernel.shape, front ? 1 : 0, ctx->num_cus, scene->kernel.lds_bytes, stream), what);
-        return RT_OK;
-    });
+    return launch_bracket(ctx, stream, [&]() -> rt_status { return enqueue_rays(ctx, scene, a, launcher, front, "clearing the ray counter", what, stream); });
 }

@@ -3,7 +3,8 @@
  * its kernel family) and the translation units behind the C ABI call.  The functions have C linkage, so the linker ties nothing to a
  * signature; the compilers do, because every side includes this header: a kernel header whose definition differs, a caller's leftover
  * declaration, or a stub of the host tests (tests/sanitize/launcher_stubs.h) is a conflicting declaration, an error.
- * tests/test_launch_seam.py keeps declarations out of every other file.  Host code: the HIP runtime's API types and the argument blocks.
+ * tests/test_launch_seam.py keeps declarations out of every other file, and every file that defines a launcher includes this one.
+ * Host code: the HIP runtime's API types and the argument blocks.
  */
 #ifndef RT_LAUNCH_H
 #define RT_LAUNCH_H
@@ -16,8 +17,12 @@
 #include "rt_ao.h"
 #include "rt_denoise.h"
 #include "rt_device_scene.h"
+#include "rt_multihit.h"
+#include "rt_nearest.h"
 #include "rt_occlusion.h"
 #include "rt_query.h"
+#include "rt_rebuild.h"
+#include "rt_winding.h"
 
 extern "C" {
 
@@ -29,6 +34,9 @@ hipError_t rt_launch_render(const rt_kernel_args *args, rt_shape shape, int bloc
 hipError_t rt_launch_budget(const rt_kernel_args *args, const uint16_t *budget, uint32_t *count, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
 /* the views variant: cams is the device table of args->num_frames x 12 camera floats; the grid is sized as for the render kernel */
 hipError_t rt_launch_views(const rt_kernel_args *args, const float *cams, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream);
+/* the sky variant of the views kernel: texels is the map's device copy (RT_SKY_TEXEL_FLOATS per texel, rt_sky.h), face_size its n */
+hipError_t rt_launch_sky(const rt_kernel_args *args, const float *cams, const float *texels, int32_t face_size, rt_shape shape, int blocks, size_t lds_bytes,
+                         hipStream_t stream);
 
 /* ---- rt_frame_kernels.h ---- */
 /* folds num_frames planes of per-pixel means into `frame` in place, in frame order */
@@ -45,6 +53,10 @@ hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *out, hipStre
 hipError_t rt_launch_query(const rt_query_args *args, rt_shape shape, int aov, int num_cus, size_t lds_bytes, hipStream_t stream);
 hipError_t rt_launch_occlusion(const rt_occlusion_args *args, rt_shape shape, int vis, int num_cus, size_t lds_bytes, hipStream_t stream);
 hipError_t rt_launch_ao(const rt_ao_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
+/* rt_multihit_kernel.h, with them: the signature is the ray kernels' (rt_internal.h's enqueue_rays calls it); `front` is not read */
+hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
+/* ... and its second pass over the records: the texture coordinates of those on a sphere whose material needs them */
+hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *args, int num_cus, hipStream_t stream);
 
 /* ---- rt_denoise_kernel.h ---- */
 hipError_t rt_launch_denoise_pack(const rt_denoise_args *args, hipStream_t stream);
@@ -53,6 +65,25 @@ hipError_t rt_launch_denoise_level(const rt_denoise_args *args, int last, hipStr
 /* ---- rt_adaptive_kernel.h ---- */
 hipError_t rt_launch_adaptive_plan(const rt_plan_args *args, hipStream_t stream);
 hipError_t rt_launch_adaptive_combine(const float *a, const float *b, const uint32_t *count, float *frame, uint32_t *count_out, long long n_pixels, hipStream_t stream);
+
+/* ---- rt_rebuild_kernel.h ---- */
+/* queues the whole rebuild on `stream`: the global levels (box and keys per segment, the sort's passes, the new list), the workgroup-local
+ * levels, the node and root boxes.  Nothing waits; every kernel's loops are bounded by n and the level count. */
+hipError_t rt_launch_rebuild(const rt_rebuild_args *args, hipStream_t stream);
+
+/* ---- rt_cull_kernel.h ---- */
+/* the pre-pass on `stream` - one thread per pixel of the width x height image of camera `cam`, the scene's blob walked in global memory;
+ * writes rt_cull_words(width, height) words of `plane`, a set bit: the pixel's primary rays reach no leaf of any mesh */
+hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t height, int32_t antialias, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
+                          int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream);
+
+/* ---- rt_nearest_kernel.h (in every build) ---- */
+/* the signature is the ray kernels'; `front` is not read: the kernel has the one front */
+hipError_t rt_launch_nearest(const rt_nearest_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
+
+/* ---- rt_winding_kernel.h (in every build) ---- */
+/* the kernel stages nothing in LDS and is the same for every scene placement: no shape */
+hipError_t rt_launch_winding(const rt_winding_args *args, int num_cus, hipStream_t stream);
 
 /* ---- rt_debug_kernels.h: the test hooks ---- */
 hipError_t rt_launch_eval(int op, const uint32_t *in, uint32_t *out, int n, hipStream_t stream);

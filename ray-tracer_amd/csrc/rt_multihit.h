@@ -9,7 +9,7 @@
  *  - the traversal of one mesh as steps over a small state (rt_mh_walk): nearer child first by key, the other pushed with its key when
  *    that is not greater than the threshold, a popped entry checked against the threshold of that moment.  The kernel runs one step per
  *    lane and round of its wave loop, the host test runs the same steps in a plain loop;
- *  - the argument block and the launcher's declaration.
+ *  - the argument blocks (the launchers are rt_launch.h's rt_launch_multihit and rt_launch_multihit_uv).
  *
  * The definition - candidates, key, limit, order, and why the key makes pruning exact - is include/rt_amd.h's.
  */
@@ -300,7 +300,7 @@ RT_MH_HD bool rt_mh_step(const rt_mh_scene<F4> &S, rt_mh_entry *stack, int32_t o
     return false;
 }
 
-/* ---- the argument block and the launcher ---------------------------------------------------------------------------------------- */
+/* ---- the argument blocks ------------------------------------------------------------------------------------------------------ */
 /* The scene and work fields carry the names rt_query_args gives them: rt_internal.h's ray_args_scene fills them, rt_stage_scene reads them. */
 typedef struct {
     const rt_f4 *blob;
@@ -325,13 +325,5 @@ typedef struct {
     rt_hit *hits;                      /* records of them */
     int64_t records;
 } rt_multihit_uv_args;
-
-/* The launcher of the multi-hit kernel, declared here like rt_nearest.h's: rt_multihit_kernel.h defines it, rt_multihit_capi.cpp calls
- * it, tests/sanitize/multihit_stubs.h defines its stand-in, and all three include this header.  The signature is the ray kernels'
- * (rt_internal.h's launch_rays calls it); `front` is not read: the kernel has the one front. */
-extern "C" {
-hipError_t rt_multihit_launch(const rt_multihit_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
-hipError_t rt_multihit_uv_launch(const rt_multihit_uv_args *args, int num_cus, hipStream_t stream);
-}
 
 #endif

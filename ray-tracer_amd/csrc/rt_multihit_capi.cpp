@@ -2,7 +2,6 @@
  * rt_multihit_capi.cpp — the multi-hit ray queries of the C ABI (include/rt_amd.h): argument checks, the host-buffer form.  The kernel is
  * rt_multihit_kernel.h, the candidate tests, the buffer and the walk rt_multihit.h; the context and the scene are rt_capi.cpp's, and the
  * checks, the argument block's shared part and the launch (in the context's launch order, between its timing events) are rt_internal.h's.
- * A translation unit of its own so that the others link without the launcher.
  */
 #include <cstdint>
 
@@ -52,9 +51,9 @@ extern "C" rt_status rt_trace_rays_multi_device(rt_ctx *ctx, const rt_scene *sce
     uv.records = n * (int64_t)k;
     const hipStream_t stream = (hipStream_t)hip_stream;
     return launch_bracket(ctx, stream, [&]() -> rt_status {
-        RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), "clearing the ray counter");
-        RT_HIP(ctx, rt_multihit_launch(&a, scene->kernel.shape, 0, ctx->num_cus, scene->kernel.lds_bytes, stream), "launching multi-hit kernel");
-        if (sphere_uv && k > 0) RT_HIP(ctx, rt_multihit_uv_launch(&uv, ctx->num_cus, stream), "launching multi-hit texture-coordinate kernel");
+        const rt_status queued = enqueue_rays(ctx, scene, a, rt_launch_multihit, false, "clearing the ray counter", "launching multi-hit kernel", stream);
+        if (queued != RT_OK) return queued;
+        if (sphere_uv && k > 0) RT_HIP(ctx, rt_launch_multihit_uv(&uv, ctx->num_cus, stream), "launching multi-hit texture-coordinate kernel");
         return RT_OK;
     });
 }

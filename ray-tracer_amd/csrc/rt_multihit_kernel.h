@@ -2,7 +2,7 @@
  * rt_multihit_kernel.h — multi-hit ray queries: one ray per lane through the scene the render kernel stages, the first k candidates along
  * it (or only their number) written out.  The candidate tests, the buffer and the walk of a mesh are rt_multihit.h's (one text for the
  * device and the host tests); the scene staging is rt_traverse.h's, a record's surface is rt_surface.h's, the launcher at the end
- * (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_multihit.h.
+ * (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_launch.h.
  *
  * What is found is the first k of include/rt_amd.h's ordered candidates: the objects that are not meshes in list order from their LDS
  * records (rt_mh_simple), each accepted one offered to the buffer, then every mesh whose root box the ray enters no later than the
@@ -34,6 +34,7 @@
 #if RT_RAY_KERNELS_BUILT
 #include "rt_device_scene.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
 #include "rt_math.h"
 #include "rt_ray_kernel.h"
 #include "rt_surface.h"
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256) void rt_multihit_uv_kernel(const rt_multihit_u
     }
 }
 
-extern "C" hipError_t rt_multihit_uv_launch(const rt_multihit_uv_args *args, int num_cus, hipStream_t stream)
+extern "C" hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *args, int num_cus, hipStream_t stream)
 {
     if (args->records <= 0) return hipSuccess;
     long long blocks = (args->records + 255) / 256;
@@ -225,20 +226,17 @@ extern "C" hipError_t rt_multihit_uv_launch(const rt_multihit_uv_args *args, int
     return hipGetLastError();
 }
 
-/* ---- launcher (rt_multihit.h) --------------------------------------------------------------- */
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
 /* rt_ray_kernel.h's table has two fronts per shape; this kernel has one, entered under both */
 struct rt_multihit_kernels {
     typedef rt_multihit_args args;
     template <int NT, bool HAS_MESH, int MODE, bool FRONT> static constexpr auto kernel = &rt_multihit_kernel<NT, HAS_MESH, MODE>;
 };
 
-extern "C" hipError_t rt_multihit_launch(const rt_multihit_args *args, rt_shape shape, int, int num_cus, size_t lds_bytes, hipStream_t stream)
+extern "C" hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int, int num_cus, size_t lds_bytes, hipStream_t stream)
 {
     return rt_ray_launch<rt_multihit_kernels>(args, shape, 0, num_cus, lds_bytes, stream);
 }
-#else
-extern "C" hipError_t rt_multihit_launch(const rt_multihit_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
-extern "C" hipError_t rt_multihit_uv_launch(const rt_multihit_uv_args *, int, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 #endif

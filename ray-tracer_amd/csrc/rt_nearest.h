@@ -7,7 +7,7 @@
  *  - the traversal of one mesh as steps over a small state (rt_nr_walk): nearest child first by path value, the farther child pushed
  *    with its path value, a popped entry skipped when its key is greater than the best so far.  The kernel runs one step per lane and
  *    round of its wave loop, the host test runs the same steps in a plain loop;
- *  - the argument block and the launcher's declaration.
+ *  - the argument block (the launcher is rt_launch.h's rt_launch_nearest).
  *
  * The definition - every formula in the order it is evaluated, and why the path value makes pruning exact - is include/rt_amd.h's.
  */
@@ -227,7 +227,7 @@ RT_NR_HD void rt_nr_record(const rt_nr_scene<F4> &S, float px, float py, float p
     out.triangle = best.triangle;
 }
 
-/* ---- the argument block and the launcher ---------------------------------------------------------------------------------------- */
+/* ---- the argument block ------------------------------------------------------------------------------------------------------- */
 /* The scene and work fields carry the names rt_query_args gives them: rt_internal.h's ray_args_scene fills them, rt_stage_scene reads them. */
 typedef struct {
     const rt_f4 *blob;
@@ -242,13 +242,5 @@ typedef struct {
     const float *max_dist;             /* n floats, or NULL: unbounded */
     rt_nearest *out;                   /* n records, 16-byte aligned */
 } rt_nearest_args;
-
-/* The launcher of the nearest-surface kernel.  It is declared here, not in rt_launch.h, whose list tests/test_launch_seam.py ties to
- * tests/sanitize/launcher_stubs.h; the discipline is the same: rt_nearest_kernel.h defines it, rt_nearest_capi.cpp calls it,
- * tests/sanitize/nearest_stubs.h defines its stand-in, and all three include this header.  The signature is the ray kernels'
- * (rt_internal.h's launch_rays calls it); `front` is not read: the kernel has the one front. */
-extern "C" {
-hipError_t rt_nearest_launch(const rt_nearest_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
-}
 
 #endif

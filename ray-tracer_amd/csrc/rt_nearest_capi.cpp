@@ -1,8 +1,7 @@
 /*
  * rt_nearest_capi.cpp — the nearest-surface queries of the C ABI (include/rt_amd.h): argument checks, the host-buffer form.  The kernel is
  * rt_nearest_kernel.h, the arithmetic rt_nearest.h; the context and the scene are rt_capi.cpp's, and the checks, the argument block's
- * shared part and the launch (in the context's launch order, between its timing events) are rt_internal.h's.  A translation unit of its
- * own so that the others link without the launcher.
+ * shared part and the launch (in the context's launch order, between its timing events) are rt_internal.h's.
  */
 #include <cstdint>
 
@@ -12,12 +11,11 @@
 namespace {
 
 /* n points on a scene and where the answers go (the limits may be missing) */
-rt_status check_points(rt_ctx *ctx, const rt_scene *scene, const void *points, int64_t n, const void *out)
+rt_status check_nearest(rt_ctx *ctx, const rt_scene *scene, const void *points, int64_t n, const void *out)
 {
-    rt_status st = check_scene(ctx, scene);
+    const rt_status st = check_points(ctx, scene, points, n);
     if (st != RT_OK) return st;
-    if (n < 0 || n > RT_NEAREST_MAX_POINTS) return set_err(ctx, RT_ERR_INVALID, "bad point count (0 .. 2^30)");
-    if (n > 0 && (!points || !out)) return set_err(ctx, RT_ERR_INVALID, "null argument");
+    if (n > 0 && !out) return set_err(ctx, RT_ERR_INVALID, "null argument");
     return RT_OK;
 }
 
@@ -26,7 +24,7 @@ rt_status check_points(rt_ctx *ctx, const rt_scene *scene, const void *points, i
 extern "C" rt_status rt_nearest_points_device(rt_ctx *ctx, const rt_scene *scene, const float *d_points, const float *d_max_dist, int64_t n,
                                               rt_nearest *d_out, void *hip_stream)
 {
-    rt_status st = check_points(ctx, scene, d_points, n, d_out);
+    rt_status st = check_nearest(ctx, scene, d_points, n, d_out);
     if (st != RT_OK) return st;
     if (n == 0) return RT_OK;
     if ((uintptr_t)d_out & 15u) return set_err(ctx, RT_ERR_INVALID, "d_out must be 16-byte aligned");
@@ -34,12 +32,12 @@ extern "C" rt_status rt_nearest_points_device(rt_ctx *ctx, const rt_scene *scene
     a.points = d_points;
     a.max_dist = d_max_dist;
     a.out = d_out;
-    return launch_rays(ctx, scene, a, rt_nearest_launch, false, "launching nearest-surface kernel", (hipStream_t)hip_stream);
+    return launch_rays(ctx, scene, a, rt_launch_nearest, false, "launching nearest-surface kernel", (hipStream_t)hip_stream);
 }
 
 extern "C" rt_status rt_nearest_points(rt_ctx *ctx, const rt_scene *scene, const float *points, const float *max_dist, int64_t n, rt_nearest *out)
 {
-    rt_status st = check_points(ctx, scene, points, n, out);
+    rt_status st = check_nearest(ctx, scene, points, n, out);
     if (st != RT_OK) return st;
     if (n == 0) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");

@@ -1,7 +1,7 @@
 /*
  * rt_nearest_kernel.h — nearest-surface queries: one point per lane through the scene the render kernel stages, the closest surface point
  * and its distance written out.  The arithmetic and the walk of a mesh are rt_nearest.h's (one text for the device and the host tests);
- * the scene staging is rt_traverse.h's, the launcher at the end (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_nearest.h.
+ * the scene staging is rt_traverse.h's, the launcher at the end (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_launch.h.
  *
  * What is found is the minimum of include/rt_amd.h's definition over every candidate of the scene: the objects that are not meshes in
  * list order from their LDS records (rt_nr_simple), then every mesh whose root box is not farther than the best so far, walked nearest
@@ -22,6 +22,7 @@
 
 #include "rt_device_scene.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
 #include "rt_nearest.h"
 #include "rt_ray_kernel.h"
 #include "rt_traverse.h"
@@ -141,14 +142,14 @@ __global__ __launch_bounds__(NT, 4) void rt_nearest_kernel(const rt_nearest_args
     }
 }
 
-/* ---- launcher (rt_nearest.h) ---------------------------------------------------------------- */
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
 /* rt_ray_kernel.h's table has two fronts per shape; this kernel has one, entered under both */
 struct rt_nearest_kernels {
     typedef rt_nearest_args args;
     template <int NT, bool HAS_MESH, int MODE, bool FRONT> static constexpr auto kernel = &rt_nearest_kernel<NT, HAS_MESH, MODE>;
 };
 
-extern "C" hipError_t rt_nearest_launch(const rt_nearest_args *args, rt_shape shape, int, int num_cus, size_t lds_bytes, hipStream_t stream)
+extern "C" hipError_t rt_launch_nearest(const rt_nearest_args *args, rt_shape shape, int, int num_cus, size_t lds_bytes, hipStream_t stream)
 {
     return rt_ray_launch<rt_nearest_kernels>(args, shape, 0, num_cus, lds_bytes, stream);
 }

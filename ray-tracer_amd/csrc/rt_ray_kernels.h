@@ -1,6 +1,6 @@
 /*
- * rt_ray_kernels.h — the three ray kernels with their launchers or, in the development builds, three launchers that refuse.  This is the
- * one place that decides it.
+ * rt_ray_kernels.h — the three ray kernels with their launchers or, in the development builds, launchers that refuse: theirs and the
+ * multi-hit kernel's two, which rt_multihit_kernel.h then leaves out.  This is the one place that decides it.
  *
  * The development builds (-DRT_STATS, -DRT_COSTMAP, -DRT_MARK) instrument the render kernel alone.  The ray kernels call rt_descend
  * (rt_traverse.h), which in those builds takes the render kernel's counters (RT_STAT_PARAMS, rt_instrument.h) and counts into them.  To
@@ -26,6 +26,8 @@
 extern "C" hipError_t rt_launch_query(const rt_query_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t rt_launch_occlusion(const rt_occlusion_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
 extern "C" hipError_t rt_launch_ao(const rt_ao_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+extern "C" hipError_t rt_launch_multihit(const rt_multihit_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }
+extern "C" hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *, int, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 #endif

@@ -172,7 +172,7 @@ inline bool rt_rb_make_plan(int32_t n, rt_rb_plan &p)
     return ok;
 }
 
-/* ---- the argument block and the launcher ---------------------------------------------------------------------------------------- */
+/* ---- the argument block (the launcher is rt_launch.h's rt_launch_rebuild) -------------------------------------------------------- */
 typedef struct {
     const float *pts;              /* n x 9: the mesh's new triangles in commit order */
     int32_t n;
@@ -194,14 +194,5 @@ typedef struct {
     int32_t tri_base, node_base;   /* the mesh's first triangle and first node in the scene */
     int32_t mesh_index, object_index;
 } rt_rebuild_args;
-
-/* The launchers of the rebuild kernels.  They are declared here, not in rt_launch.h, whose list tests/test_launch_seam.py ties to
- * tests/sanitize/launcher_stubs.h; the discipline is the same: rt_rebuild_kernel.h defines them, rt_update_capi.cpp calls them,
- * tests/sanitize/update_stubs.h defines their stand-ins, and all three include this header. */
-extern "C" {
-/* queues the whole rebuild on `stream`: the global levels (box and keys per segment, the sort's passes, the new list), the workgroup-local
- * levels, the node and root boxes.  Nothing waits; every kernel's loops are bounded by n and the level count. */
-hipError_t rt_rebuild_enqueue(const rt_rebuild_args *args, hipStream_t stream);
-}
 
 #endif

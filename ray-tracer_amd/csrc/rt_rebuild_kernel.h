@@ -1,6 +1,6 @@
 /*
  * rt_rebuild_kernel.h — the kernels that rebuild one mesh's BVH on the device (rt_scene_update_mesh_device) and their launcher (declared in
- * rt_rebuild.h).  The arithmetic is rt_rebuild.h's, the same text the host tests run.
+ * rt_launch.h).  The arithmetic is rt_rebuild.h's, the same text the host tests run.
  *
  * Shape.  A level of the tree is "per segment: box in list order, reference point, keys, sort".  Levels whose segments fit a workgroup's LDS
  * (RT_REBUILD_LDS_TRIS) are all done by rt_rb_local_kernel, one workgroup per segment of the first such level, without leaving the CU: a mesh
@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_rebuild.h"
 
 #define RT_RB_TILE RT_REBUILD_LDS_TRIS      /* words of one LDS tile of the sort */
@@ -263,7 +264,7 @@ __global__ void __launch_bounds__(256) rt_rb_finish_kernel(rt_rebuild_args a)
     }
 }
 
-extern "C" hipError_t rt_rebuild_enqueue(const rt_rebuild_args *args, hipStream_t stream)
+extern "C" hipError_t rt_launch_rebuild(const rt_rebuild_args *args, hipStream_t stream)
 {
     const rt_rebuild_args &a = *args;
     if (a.n <= 0 || a.local_level < 0 || a.local_level > RT_BVH_DEPTH) return hipErrorInvalidValue;

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 4 : (HAS_MESH ? RT_SMALL_WG_WAVES 
     rt_sky_loop<NT, HAS_MESH, MODE>(a);
 }
 
-/* ---- launchers (rt_launch.h; the sky variant's: rt_sky.h) -------------------------------------------------------------- */
+/* ---- launchers (rt_launch.h) ------------------------------------------------------------------------------------------- */
 template <int NT, class Args, void (*KERNEL)(Args)>
 static int rt_blocks_one(size_t lds_bytes)
 {
@@ -257,9 +257,9 @@ extern "C" hipError_t rt_launch_views(const rt_kernel_args *args, const float *c
     return hipGetLastError();
 }
 
-/* the sky variant on the same shape (declared in rt_sky.h): the views launch and the cube map's texels */
-extern "C" hipError_t rt_sky_enqueue(const rt_kernel_args *args, const float *cams, const float *texels, int32_t face_size, rt_shape shape, int blocks, size_t lds_bytes,
-                                     hipStream_t stream)
+/* the sky variant on the same shape (rt_launch.h): the views launch and the cube map's texels */
+extern "C" hipError_t rt_launch_sky(const rt_kernel_args *args, const float *cams, const float *texels, int32_t face_size, rt_shape shape, int blocks, size_t lds_bytes,
+                                    hipStream_t stream)
 {
     const int i = rt_shape_index(shape);
     if (i < 0) return hipErrorInvalidValue;

@@ -2,11 +2,8 @@
  * rt_sky.h — the cube-map sky (include/rt_amd.h: rt_sky_create, rt_sky_texel_direction, rt_render_sky[_device]): what the kernel
  * (rt_pixel.h, px_shade_miss under SKY), the entry points (rt_sky_capi.cpp) and the host-only sanitizer program
  * (tests/sanitize/sky_host_fuzz.cpp) share.  The lookup and its inverse as the one text every side compiles (binary32, nothing fused: the
- * library and the tests build with contraction off), the argument checks, and the sky kernel's launcher.  Host code; self-contained.
- *
- * The launcher is declared here and not in rt_launch.h: no translation unit but rt_sky_capi.cpp references it, so the host programs that
- * link the other translation units with tests/sanitize/launcher_stubs.h go on linking; tests/sanitize/sky_stubs.h is its stub
- * (like rt_rebuild.h's launcher and tests/sanitize/update_stubs.h: DESIGN.md section 21, 22).
+ * library and the tests build with contraction off) and the argument checks; the sky kernel's launcher is rt_launch.h's rt_launch_sky.
+ * Host code; self-contained.
  */
 #ifndef RT_SKY_H
 #define RT_SKY_H
@@ -99,13 +96,5 @@ inline void pack(const float *faces_rgb, int32_t n, float *out)
 }
 
 }  // namespace rt_sky_host
-
-extern "C" {
-/* rt_render_kernel.h: the sky variant of the render kernel on `shape` - cams is the device table of args->num_frames x 12 camera floats,
- * texels the map's device copy (RT_SKY_TEXEL_FLOATS per texel), face_size its n; the grid is sized as for the render kernel.
- * hipErrorInvalidValue: the shape is not built. */
-hipError_t rt_sky_enqueue(const rt_kernel_args *args, const float *cams, const float *texels, int32_t face_size, rt_shape shape, int blocks, size_t lds_bytes,
-                          hipStream_t stream);
-}
 
 #endif

@@ -3,7 +3,7 @@
  * kernel is rt_render_kernel.h's rt_sky_kernel (the views kernel whose rays that leave the scene look their light up in the map); the
  * checks, the camera table, the schedule, the launch bracket, the fold and the host form's loop are rt_views_capi.cpp's, called with the sky
  * kernel's launcher; the lookup, its inverse and the map's own checks are rt_sky.h (no HIP: tests/sanitize/sky_host_fuzz.cpp drives them on
- * the host).  The only translation unit that references that launcher.
+ * the host).
  */
 #include <cstdint>
 #include <vector>
@@ -64,7 +64,7 @@ extern "C" rt_status rt_render_sky_device(rt_ctx *ctx, const rt_scene *scene, co
     if (st != RT_OK || (st = check_sky(ctx, sky)) != RT_OK) return st;
     return views_launch(ctx, scene, cams, times_ms, n_views, rs, accumulate, frame_num, d_frames, (hipStream_t)hip_stream,
                         [sky](const rt_kernel_args &a, const float *d_cams, rt_shape shape, int blocks, size_t lds_bytes, hipStream_t stream) {
-                            return rt_sky_enqueue(&a, d_cams, sky->d_texels.p, sky->face_size, shape, blocks, lds_bytes, stream);
+                            return rt_launch_sky(&a, d_cams, sky->d_texels.p, sky->face_size, shape, blocks, lds_bytes, stream);
                         });
 }
 

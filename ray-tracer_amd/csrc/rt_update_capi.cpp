@@ -155,7 +155,7 @@ extern "C" rt_status rt_scene_update_mesh_device(rt_ctx *ctx, rt_scene *scene, i
     a.object_index = object_index;
     hipStream_t stream = (hipStream_t)hip_stream;
     st = launch_bracket(ctx, stream, [&]() -> rt_status {
-        RT_HIP(ctx, rt_rebuild_enqueue(&a, stream), "launching the rebuild kernels");
+        RT_HIP(ctx, rt_launch_rebuild(&a, stream), "launching the rebuild kernels");
         return RT_OK;
     });
     if (st != RT_OK) return st;

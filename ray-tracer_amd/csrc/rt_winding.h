@@ -5,7 +5,7 @@
  *
  *  - the arithmetic, as the one text both sides compile (binary32, nothing fused: the library and the tests build with contraction off):
  *    rt_wn_atan2, the term of a triangle record, the sphere and cuboid rules, an object's winding number, the sum over the solids;
- *  - the argument block and the launcher's declaration.
+ *  - the argument block (the launcher is rt_launch.h's rt_launch_winding).
  *
  * The definition - every formula in the order it is evaluated - is include/rt_amd.h's.  Nothing here depends on the point but the
  * arithmetic: every loop bound and every record address comes from the scene alone, so on the device all lanes of a wave are on the same
@@ -181,7 +181,7 @@ RT_WN_HD bool rt_wn_inside(float w) { return rt_wn_abs(w) >= 0.5f; }      /* (fa
 /* the signed distance from the point's nearest-surface record */
 RT_WN_HD float rt_wn_sdf(float w, float distance) { return rt_wn_inside(w) ? rt_wn_neg(distance) : distance; }
 
-/* ---- the argument block and the launcher ---------------------------------------------------------------------------------------- */
+/* ---- the argument block ------------------------------------------------------------------------------------------------------- */
 typedef struct {
     const rt_f4 *blob;
     int32_t off_tris, off_objtab;
@@ -198,12 +198,5 @@ typedef struct {
     const rt_nearest *nearest;         /* with sdf: the points' nearest-surface records */
     float *sdf;                        /* n floats, or NULL */
 } rt_winding_args;
-
-/* The launcher of the winding-number kernel, declared here as rt_nearest.h declares its own: rt_winding_kernel.h defines it,
- * rt_winding_capi.cpp calls it, tests/sanitize/winding_stubs.h defines its stand-in, and all three include this header.  The kernel
- * stages nothing in LDS and is the same for every scene placement: no shape. */
-extern "C" {
-hipError_t rt_winding_launch(const rt_winding_args *args, int num_cus, hipStream_t stream);
-}
 
 #endif

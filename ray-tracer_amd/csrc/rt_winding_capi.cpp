@@ -1,8 +1,8 @@
 /*
  * rt_winding_capi.cpp — the winding-number queries of the C ABI (include/rt_amd.h): argument checks, the scene's flip bytes on the device,
  * the host-buffer forms.  The kernel is rt_winding_kernel.h, the arithmetic rt_winding.h; rt_signed_distance_device also runs the
- * nearest-surface kernel (rt_nearest.h's launcher, as rt_nearest_capi.cpp runs it).  The context, the scene and the launch bracket are
- * rt_internal.h's.  A translation unit of its own so that the others link without the launcher.
+ * nearest-surface kernel (as rt_nearest_capi.cpp runs it).  The context, the scene, the launch bracket and the ray kernels' enqueue are
+ * rt_internal.h's.
  */
 #include <cstdint>
 #include <cstring>
@@ -13,16 +13,6 @@
 #include "rt_winding.h"
 
 namespace {
-
-/* n points on a scene */
-rt_status check_points(rt_ctx *ctx, const rt_scene *scene, const void *points, int64_t n)
-{
-    rt_status st = check_scene(ctx, scene);
-    if (st != RT_OK) return st;
-    if (n < 0 || n > RT_WINDING_MAX_POINTS) return set_err(ctx, RT_ERR_INVALID, "bad point count (0 .. 2^30)");
-    if (n > 0 && !points) return set_err(ctx, RT_ERR_INVALID, "null argument");
-    return RT_OK;
-}
 
 rt_status check_winding(rt_ctx *ctx, const rt_scene *scene, const void *points, int64_t n, int32_t object, const void *winding, const void *inside)
 {
@@ -76,7 +66,7 @@ rt_winding_args winding_args(const rt_ctx *ctx, const rt_scene *scene, const flo
 rt_status enqueue_winding(rt_ctx *ctx, const rt_winding_args &a, hipStream_t stream)
 {
     RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), "clearing the point counter");
-    RT_HIP(ctx, rt_winding_launch(&a, ctx->num_cus, stream), "launching winding-number kernel");
+    RT_HIP(ctx, rt_launch_winding(&a, ctx->num_cus, stream), "launching winding-number kernel");
     return RT_OK;
 }
 
@@ -143,9 +133,8 @@ extern "C" rt_status rt_signed_distance_device(rt_ctx *ctx, rt_scene *scene, con
     wa.sdf = d_sdf;
     hipStream_t stream = (hipStream_t)hip_stream;
     return launch_bracket(ctx, stream, [&]() -> rt_status {
-        RT_HIP(ctx, hipMemsetAsync(na.counter, 0, 512, stream), "clearing the point counter");
-        RT_HIP(ctx, rt_nearest_launch(&na, scene->kernel.shape, 0, ctx->num_cus, scene->kernel.lds_bytes, stream), "launching nearest-surface kernel");
-        return enqueue_winding(ctx, wa, stream);
+        const rt_status queued = enqueue_rays(ctx, scene, na, rt_launch_nearest, false, "clearing the point counter", "launching nearest-surface kernel", stream);
+        return queued != RT_OK ? queued : enqueue_winding(ctx, wa, stream);
     });
 }
 

@@ -1,7 +1,7 @@
 /*
  * rt_winding_kernel.h — winding-number queries: one point per lane, the generalized winding number of an object or of the scene's solids
  * written out, or the sign it gives a nearest-surface distance.  The arithmetic and the loops are rt_winding.h's (one text for the device
- * and the host tests); the launcher at the end is declared there.
+ * and the host tests); the launcher at the end is declared in rt_launch.h.
  *
  * A dense points x triangles reduction, unlike every other kernel here: no lane state machine, no stack, no LDS.  A wave takes point ids 64
  * at a time from a global counter, as the nearest-surface kernel does, and then every lane runs the SAME loop over objects and records -
@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_vec.h"
 #include "rt_winding.h"
 
@@ -54,8 +55,8 @@ __global__ __launch_bounds__(RT_WINDING_THREADS) void rt_winding_kernel(const v4
     }
 }
 
-/* ---- launcher (rt_winding.h) ---------------------------------------------------------------- */
-extern "C" hipError_t rt_winding_launch(const rt_winding_args *a, int num_cus, hipStream_t stream)
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
+extern "C" hipError_t rt_launch_winding(const rt_winding_args *a, int num_cus, hipStream_t stream)
 {
     const uint32_t waves = RT_WINDING_THREADS / RT_WAVE;
     uint32_t blocks = (a->num_chunks + waves - 1) / waves;

@@ -26,7 +26,6 @@
 #include "rt_multihit.h"
 
 #include "launcher_stubs.h"
-#include "multihit_stubs.h"
 
 #define CHECK(cond, what)                                                                             \
     do {                                                                                              \
@@ -362,7 +361,7 @@ static int refusals()
         CHECK(call(&ctx, &scene, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr) == RT_OK && call(&ctx, &scene, o, d, lim, 0, 3, hits, counts) == RT_OK, "no rays: nothing to do");
     }
     CHECK(rt_trace_rays_multi_device(&ctx, &scene, o, d, nullptr, 2, 2, misaligned, counts, nullptr) == RT_ERR_INVALID && said(ctx, "16-byte aligned"), "misaligned records");
-    CHECK(g_multihit_launches == 0 && g_launches == 0, "a refused call reached a launcher");
+    CHECK(g_launches == 0, "a refused call reached a launcher");
     CHECK(!ctx.launched && !ctx.have_timing && ctx.last_stream == nullptr, "a refused call touched the launch order");
     return 0;
 }

@@ -23,7 +23,6 @@
 #include "rt_nearest.h"
 
 #include "launcher_stubs.h"
-#include "nearest_stubs.h"
 
 #define CHECK(cond, what)                                                                             \
     do {                                                                                              \
@@ -238,7 +237,7 @@ static int refusals()
         CHECK(call(&ctx, &scene, nullptr, nullptr, 0, nullptr) == RT_OK && call(&ctx, &scene, pts, lim, 0, out) == RT_OK, "no points: nothing to do");
     }
     CHECK(rt_nearest_points_device(&ctx, &scene, pts, nullptr, 2, misaligned, nullptr) == RT_ERR_INVALID && said(ctx, "16-byte aligned"), "misaligned records");
-    CHECK(g_nearest_launches == 0 && g_launches == 0, "a refused call reached a launcher");
+    CHECK(g_launches == 0, "a refused call reached a launcher");
     CHECK(!ctx.launched && !ctx.have_timing && ctx.last_stream == nullptr, "a refused call touched the launch order");
     return 0;
 }

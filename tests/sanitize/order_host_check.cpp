@@ -10,7 +10,8 @@
 //   the device: DevBuf::grow relies on it)
 // and reports
 //   - two accesses to one allocation, at least one a write, that are not ordered (the context's scratch: ticket counter, per-frame planes,
-//     denoise records, camera table, tile lists, tile order and costs; the caller's buffers; the two timing events as one-word buffers);
+//     denoise records, camera table, tile lists, tile order and costs, the cull plane, the query records, an update's scratch; a scene's
+//     blob, objects and triangle order under an update; the caller's buffers; the two timing events as one-word buffers);
 //   - a range that leaves its allocation;
 //   - host memory handed to an asynchronous copy (ViewsState::host, the pinned tile lists, locals) that is rewritten or released before
 //     a host wait covers the copy: the copy's source is compared with a snapshot, and probed for poisoning, when the wait arrives;
@@ -30,6 +31,7 @@
 #include <cstring>
 #include <map>
 #include <random>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -93,9 +95,13 @@ long g_ops = 0, g_violations = 0, g_accesses = 0, g_frees_waited = 0, g_launch_c
 bool g_in_tile_list_call = false;                 // the driver is in a call that hands a tile list to the context's cache
 std::mt19937 g_plan_rng(99);
 
+std::set<std::string> g_named;                    // the buffers that reported violations have named
+bool g_first_of_its_buffer = false;
+
+// the first twelve are printed, and behind them the first one of every buffer not named yet
 void violation(const char *fmt, ...)
 {
-    if (++g_violations > 12) return;
+    if (++g_violations > 12 && !g_first_of_its_buffer) return;
     std::fprintf(stderr, "order violation: ");
     va_list ap;
     va_start(ap, fmt);
@@ -128,9 +134,12 @@ void note(std::vector<Access> &list, const Clock &now, int tl, size_t lo, size_t
         Access &p = list[i];
         if (host_has_waited_for(p.tl, p.c)) { list[i] = list.back(); list.pop_back(); continue; }      // before everything still to come
         const bool ordered = now[(size_t)p.tl] >= p.c;
-        if (p.lo < hi && lo < p.hi && (p.write || write) && !ordered)
+        if (p.lo < hi && lo < p.hi && (p.write || write) && !ordered) {
+            g_first_of_its_buffer = g_named.insert(what).second;
             violation("%s %s [%zu, %zu) by %s in %s (stream %d) is not ordered behind %s %s [%zu, %zu) by %s in %s (stream %d)", write ? "write of" : "read of", what, lo, hi,
                       op, g_call.c_str(), tl, p.write ? "the write of" : "the read of", p.what, p.lo, p.hi, p.op, p.call.c_str(), p.tl);
+            g_first_of_its_buffer = false;
+        }
         if (ordered && p.lo >= lo && p.hi <= hi && (write || !p.write)) { list[i] = list.back(); list.pop_back(); continue; }   // the new access stands for it
         i++;
     }
@@ -227,6 +236,13 @@ hipError_t rec::launch(const char *kernel, hipStream_t stream, std::initializer_
     g_launch_count++;
     for (const Use &u : uses) use(now, timeline(stream), u.p, u.bytes, u.write, kernel, u.what);
     return hipSuccess;
+}
+
+size_t rec::extent(const void *p)
+{
+    uintptr_t base = 0;
+    const Alloc *a = find_alloc(p, &base);
+    return a ? a->bytes - ((uintptr_t)p - base) : 0;
 }
 
 void rec::fill_plan(float *tile_error, uint32_t *tile_active, int num_tiles)
@@ -393,6 +409,7 @@ namespace {
     } while (0)
 
 constexpr int MAX_W = 96, MAX_H = 64, MAX_PX = MAX_W * MAX_H, MAX_VIEWS = 4, MAX_RAYS = 4096 + 17;
+constexpr int MESH_TRIS = 60, MAX_MULTI = 1024 + 17;       // the mesh scene's one mesh (object 0); rays of a multi-hit call (RT_MULTIHIT_MAX records each)
 
 template <class T> T *caller_alloc(size_t n)
 {
@@ -406,9 +423,12 @@ template <class T> T *caller_alloc(size_t n)
 // the buffers of a caller who works on one stream: whatever touches them is ordered through that stream
 struct CallerBuffers {
     float *frame, *prev, *frames, *compact, *origins, *directions, *tmax, *depth, *normal, *albedo, *ray, *ao, *tile_error, *half_a, *half_b, *denoised;
-    int32_t *object;
-    rt_hit *hits;
-    uint8_t *occluded, *visibility, *rgba;
+    float *triangles, *winding, *sdf;
+    int32_t *object, *counts;
+    rt_hit *hits, *multi_hits;
+    rt_nearest *nearest;
+    unsigned char *spare;         // where the caller copies an answer to (as large as the largest: the multi-hit records)
+    uint8_t *occluded, *visibility, *rgba, *inside;
     uint16_t *ao_count, *budget;
     uint32_t *count, *tile_active;
     std::vector<void *> all;
@@ -419,6 +439,10 @@ struct CallerBuffers {
         origins = f(3 * MAX_RAYS); directions = f(3 * MAX_RAYS); tmax = f(MAX_RAYS);
         depth = f(MAX_PX); normal = f(3 * MAX_PX); albedo = f(3 * MAX_PX); ray = f(3 * MAX_PX); ao = f(MAX_PX); tile_error = f(MAX_PX / 64 + 64);
         half_a = f(3 * MAX_PX); half_b = f(3 * MAX_PX); denoised = f(3 * MAX_PX);
+        triangles = f(9 * MESH_TRIS); winding = f(MAX_RAYS); sdf = f(MAX_RAYS);
+        counts = caller_alloc<int32_t>(MAX_RAYS); multi_hits = caller_alloc<rt_hit>((size_t)MAX_MULTI * RT_MULTIHIT_MAX); nearest = caller_alloc<rt_nearest>(MAX_RAYS);
+        spare = caller_alloc<unsigned char>((size_t)MAX_MULTI * RT_MULTIHIT_MAX * sizeof(rt_hit)); inside = caller_alloc<uint8_t>(MAX_RAYS);
+        for (void *p : {(void *)counts, (void *)multi_hits, (void *)nearest, (void *)spare, (void *)inside}) all.push_back(p);
         object = caller_alloc<int32_t>(MAX_PX); hits = caller_alloc<rt_hit>(MAX_RAYS);
         occluded = caller_alloc<uint8_t>(MAX_RAYS); visibility = caller_alloc<uint8_t>(MAX_PX); rgba = caller_alloc<uint8_t>(4 * MAX_PX);
         ao_count = caller_alloc<uint16_t>(MAX_PX); budget = caller_alloc<uint16_t>(MAX_PX);
@@ -434,9 +458,10 @@ struct World {
     CallerBuffers bufs[4];
     int n_streams = 1;
     rt_ctx *ctx[2] = {nullptr, nullptr};
-    rt_scene *plain[2] = {nullptr, nullptr}, *mesh[2] = {nullptr, nullptr};
+    rt_scene *plain[2] = {nullptr, nullptr}, *mesh[2] = {nullptr, nullptr}, *textured[2] = {nullptr, nullptr};
+    rt_sky *sky[2] = {nullptr, nullptr};
     int n_ctx = 1;
-    rt_scene_builder *b_plain = nullptr, *b_mesh = nullptr;
+    rt_scene_builder *b_plain = nullptr, *b_mesh = nullptr, *b_textured = nullptr;
     long calls = 0, refused = 0;
 
     int pick(int lo, int hi) { return lo + (int)(rng() % (unsigned)(hi - lo + 1)); }
@@ -456,6 +481,11 @@ struct World {
         REQUIRE(rt_scene_add_mesh(b_mesh, tris.data(), 60, &m) == RT_OK);
         const float c[3] = {0.0f, 1.0f, 2.0f};
         REQUIRE(rt_scene_add_sphere(b_mesh, c, 0.2f, &m) == RT_OK);
+        // a sphere whose material wants texture coordinates: a multi-hit query on it runs its second kernel
+        rt_material squares;
+        const float dark[3] = {0.1f, 0.1f, 0.1f};
+        rt_material_checkerboard(&squares, grey, dark, 8, 0.0f);
+        REQUIRE(rt_scene_builder_create(&b_textured) == RT_OK && rt_scene_add_sphere(b_textured, c, 0.5f, &squares) == RT_OK);
     }
 
     void create_ctx(int k)
@@ -464,6 +494,10 @@ struct World {
         REQUIRE(rt_ctx_create(0, &ctx[k]) == RT_OK);
         ctx[k]->tile_lists.cap = 3;         // (64 in the library: the driver has some 25 distinct lists, and recycling an entry under pending work is what is to be seen)
         REQUIRE(rt_scene_commit(ctx[k], b_plain, &plain[k]) == RT_OK && rt_scene_commit(ctx[k], b_mesh, &mesh[k]) == RT_OK);
+        REQUIRE(rt_scene_commit(ctx[k], b_textured, &textured[k]) == RT_OK && textured[k]->flat.objects[0].need_uv);
+        REQUIRE(mesh[k]->flat.objects[0].type == RT_OBJ_MESH && mesh[k]->flat.num_tris == MESH_TRIS);
+        const std::vector<float> faces(6 * 4 * 4 * 3, 0.5f);
+        REQUIRE(rt_sky_create(ctx[k], 4, faces.data(), &sky[k]) == RT_OK);
     }
 
     // with work pending: the context's members must go in an order that waits first
@@ -472,7 +506,10 @@ struct World {
         g_call = "rt_ctx_destroy";
         rt_scene_destroy(plain[k]);
         rt_scene_destroy(mesh[k]);
+        rt_scene_destroy(textured[k]);
+        sky[k]->ctx = nullptr;              // (detached: rt_sky_destroy would wait for the context first, and what is to be seen is the context going with work pending)
         rt_ctx_destroy(ctx[k]);
+        rt_sky_destroy(sky[k]);
         ctx[k] = nullptr;
     }
 
@@ -590,6 +627,15 @@ struct World {
         const rt_render_settings rs = settings(3);
         expect_ok(rt_render_views_device(ctx[c.k], scene_of(c), cams.data(), times, n, &rs, accumulate, accumulate ? pick(0, 2) : 0, bufs[c.s].frames, streams[c.s]), c);
     }
+    void render_sky(const Shape &c, int n, bool accumulate, float dx)
+    {
+        g_call = "rt_render_sky_device";
+        std::vector<rt_camera> cams;
+        for (int i = 0; i < n; i++) cams.push_back(cam_of(c, dx + 0.1f * (float)i));
+        const int32_t times[MAX_VIEWS] = {1, 2, 3, 4};
+        const rt_render_settings rs = settings(3);
+        expect_ok(rt_render_sky_device(ctx[c.k], scene_of(c), sky[c.k], cams.data(), times, n, &rs, accumulate, accumulate ? pick(0, 2) : 0, bufs[c.s].frames, streams[c.s]), c);
+    }
     void render_budget(const Shape &c, int list_kind, bool with_count)
     {
         g_call = "rt_render_budget_device";
@@ -616,6 +662,57 @@ struct World {
         g_call = "rt_trace_rays_device";
         CallerBuffers &b = bufs[c.s];
         expect_ok(rt_trace_rays_device(ctx[c.k], scene_of(c), b.origins, b.directions, n, b.hits, streams[c.s]), c);
+    }
+    // what the caller does around a query on its stream: write `in` ahead of it, copy `out` away behind it
+    void caller_writes(const Shape &c, void *in, size_t bytes) { REQUIRE(hipMemsetAsync(in, 0, bytes, streams[c.s]) == hipSuccess); }
+    void caller_reads(const Shape &c, const void *out, size_t bytes) { REQUIRE(hipMemcpyAsync(bufs[c.s].spare, out, bytes, hipMemcpyDeviceToDevice, streams[c.s]) == hipSuccess); }
+
+    // the mesh scene's mesh rebuilt from the caller's vertices: the scene blob is rewritten under whatever reads it, and the view's cull plane goes stale
+    void update_mesh(const Shape &c)
+    {
+        g_call = "rt_scene_update_mesh_device";
+        caller_writes(c, bufs[c.s].triangles, (size_t)MESH_TRIS * 36);
+        expect_ok(rt_scene_update_mesh_device(ctx[c.k], mesh[c.k], 0, bufs[c.s].triangles, MESH_TRIS, streams[c.s]), c);
+    }
+    void nearest_points(const Shape &c, int n, bool limits)
+    {
+        g_call = "rt_nearest_points_device";
+        CallerBuffers &b = bufs[c.s];
+        caller_writes(c, b.origins, (size_t)n * 12);
+        expect_ok(rt_nearest_points_device(ctx[c.k], scene_of(c), b.origins, limits ? b.tmax : nullptr, n, b.nearest, streams[c.s]), c);
+        caller_reads(c, b.nearest, (size_t)n * sizeof(rt_nearest));
+    }
+    // which: 0 the plain scene, 1 the mesh scene, 2 the one whose sphere wants texture coordinates (with k > 0: the second kernel)
+    void trace_multi(const Shape &c, int which, int n, int k, bool with_counts)
+    {
+        g_call = "rt_trace_rays_multi_device";
+        CallerBuffers &b = bufs[c.s];
+        rt_scene *sc = which == 2 ? textured[c.k] : which == 1 ? mesh[c.k] : plain[c.k];
+        caller_writes(c, b.directions, (size_t)n * 12);
+        expect_ok(rt_trace_rays_multi_device(ctx[c.k], sc, b.origins, b.directions, pick(0, 1) ? b.tmax : nullptr, n, k, k > 0 ? b.multi_hits : nullptr,
+                                             with_counts || k == 0 ? b.counts : nullptr, streams[c.s]), c);
+        if (k > 0) caller_reads(c, b.multi_hits, (size_t)n * (size_t)k * sizeof(rt_hit));
+        else caller_reads(c, b.counts, (size_t)n * 4);
+    }
+    void winding_numbers(const Shape &c, int n, bool solids, int outputs)
+    {
+        g_call = "rt_winding_numbers_device";
+        CallerBuffers &b = bufs[c.s];
+        caller_writes(c, b.origins, (size_t)n * 12);
+        expect_ok(rt_winding_numbers_device(ctx[c.k], scene_of(c), b.origins, n, solids ? RT_WINDING_SOLIDS : 0, outputs & 1 ? b.winding : nullptr, outputs & 2 ? b.inside : nullptr,
+                                            streams[c.s]), c);
+        if (outputs & 1) caller_reads(c, b.winding, (size_t)n * 4);
+        if (outputs & 2) caller_reads(c, b.inside, (size_t)n);
+    }
+    // own_records: the caller's record buffer; without it the records are the context's, grown behind a wait when n outgrows them
+    void signed_distance(const Shape &c, int n, bool own_records, bool limits)
+    {
+        g_call = "rt_signed_distance_device";
+        CallerBuffers &b = bufs[c.s];
+        caller_writes(c, b.origins, (size_t)n * 12);
+        expect_ok(rt_signed_distance_device(ctx[c.k], scene_of(c), b.origins, limits ? b.tmax : nullptr, n, own_records ? b.nearest : nullptr, b.sdf, streams[c.s]), c);
+        caller_reads(c, b.sdf, (size_t)n * 4);
+        if (own_records) caller_reads(c, b.nearest, (size_t)n * sizeof(rt_nearest));
     }
     void render_aov(const Shape &c)
     {
@@ -762,7 +859,7 @@ struct World {
         const int32_t t1[1] = {1};
         rt_status st = RT_OK;
         g_call = "a refused call";
-        switch (pick(0, 11)) {
+        switch (pick(0, 17)) {
             case 0: st = rt_render_device(x, scene_of(c), &bad, &rs, 1, 0, nullptr, nullptr, b.frame, streams[c.s]); break;
             case 1: st = rt_render_device(x, other, &cam, &rs, 1, 0, nullptr, nullptr, b.frame, streams[c.s]); break;
             case 2: st = rt_render_device_batch(x, scene_of(c), &cam, &rs, t1, 33, 0, nullptr, b.frame, streams[c.s]); break;
@@ -774,6 +871,12 @@ struct World {
             case 8: st = rt_render_budget_device(x, scene_of(c), &cam, &rs, 1, &bands, b.budget, nullptr, b.frame, streams[c.s]); break;
             case 9: st = rt_render_views_device(x, scene_of(c), &cam, t1, 0, &rs, 0, 0, b.frames, streams[c.s]); break;
             case 10: st = rt_render_visibility_device(x, scene_of(c), &cam, nullptr, 0.0f, b.visibility, streams[c.s]); break;
+            case 11: st = rt_render_sky_device(x, scene_of(c), nullptr, &cam, t1, 1, &rs, 0, 0, b.frames, streams[c.s]); break;
+            case 12: st = rt_scene_update_mesh_device(x, mesh[c.k], 0, b.triangles, MESH_TRIS + 1, streams[c.s]); break;
+            case 13: st = rt_nearest_points_device(x, scene_of(c), b.origins, nullptr, 5, nullptr, streams[c.s]); break;
+            case 14: st = rt_trace_rays_multi_device(x, scene_of(c), b.origins, b.directions, nullptr, 5, RT_MULTIHIT_MAX + 1, b.multi_hits, b.counts, streams[c.s]); break;
+            case 15: st = rt_winding_numbers_device(x, scene_of(c), b.origins, 5, 99, b.winding, nullptr, streams[c.s]); break;
+            case 16: st = rt_signed_distance_device(x, scene_of(c), b.origins, nullptr, 5, (rt_nearest *)((char *)b.nearest + 8), b.sdf, streams[c.s]); break;
             default: st = rt_tiles_copy_device(x, b.compact, b.frame, c.w, c.h, nullptr, 3, 1, streams[c.s]); break;
         }
         refused++;
@@ -801,6 +904,15 @@ struct World {
             tiles_copy(b, 0, false); tiles_copy(b, 2, true); tiles_copy(b, 4, true);                 // ... whose entries are recycled under the pending launches
             render_ao(a); occluded_rays(b, 777, true); render_visibility(a);
             adaptive_plan(a); render_budget(b, -1, false);
+            nearest_points(a, 900, true); trace_multi(b, m, 500, 3, true);                           // the ticket counter again, through the later families
+            trace_multi(a, 2, MAX_MULTI, RT_MULTIHIT_MAX, false); trace_multi(b, 2, 200, 0, true); winding_numbers(a, 700, true, 3);
+            signed_distance(b, 600, false, true); signed_distance(a, MAX_RAYS, false, false);        // the context's records, regrown under the pending pair
+            signed_distance(b, 100, true, true); winding_numbers(b, 50, false, 2);
+            render_sky(a, 3, true, 0.0f); render_sky(b, 2, false, 0.5f); render_views(a, 2, false, 0.0f);
+            // the cull plane of the mesh scene's view: computed, reused on its stream, reused on another, stale after an update; and the scene
+            // blob rewritten between launches that read it on other streams
+            render_device(a, 0, 2); render_device(a, 0, 2); render_device(b, 0, 2); update_mesh(a); render_device(b, 0, 2);
+            trace_rays(a, 300); update_mesh(b); nearest_points(a, 40, false); update_mesh(shape(0, 3, mm)); render_batch(b, 0, 2);
             render_aov(a); host_form(shape(0, 0, mm), 3);                                            // a device form, then the family's host form
             trace_rays(a, 100); host_form(shape(0, 0, mm), 2);
             render_views(a, 2, false, 0.0f); host_form(shape(0, 0, mm), 9);
@@ -811,6 +923,7 @@ struct World {
             REQUIRE(frame_submit(a, 4) && frame_submit(a, 4));
             const Shape third = shape(0, 3, mm);
             trace_rays(third, 500); denoise(third, false); render_budget(third, 0, true); render_views(third, 2, true, 0.0f); render_ao(third);
+            update_mesh(third); signed_distance(third, 2000, false, false); trace_multi(third, 2, 64, 2, true); render_sky(third, 2, true, 0.0f);
             REQUIRE(frame_collect(0, 1, false) && frame_collect(0, 1, false));
             REQUIRE(frame_submit(a, 4));
             render_device(shape(0, 2, mm, 40, 24), 0, 40);                                           // another view while a frame is in flight
@@ -832,7 +945,7 @@ struct World {
             const int z = pick(0, 4);
             const Shape c = shape(pick(0, n_ctx - 1), pick(0, n_streams - 1), pick(0, 1) != 0, sizes[z][0], sizes[z][1]);
             const int spp = pick(0, 9) == 0 ? 40 : pick(1, 4);
-            switch (pick(0, 23)) {
+            switch (pick(0, 29)) {
                 case 0: case 1: render_device(c, pick(0, 6), spp); break;
                 case 2: render_batch(c, pick(0, 1) ? 0 : pick(2, 6), spp); break;
                 case 3: case 4: frame_submit(shape(c.k, c.s, c.mesh), spp); break;      // (one image size: the view stays, so frames overlap)
@@ -850,7 +963,13 @@ struct World {
                 case 17: tiles_copy(c, pick(0, 4), pick(0, 1) != 0); break;
                 case 18: case 19: host_form(c, pick(0, 16)); break;
                 case 20: case 21: refused_call(c); break;
-                case 22:
+                case 22: render_sky(c, pick(1, MAX_VIEWS), pick(0, 1) != 0, 0.1f * (float)pick(0, 3)); break;
+                case 23: update_mesh(c); break;
+                case 24: nearest_points(c, pick(1, MAX_RAYS), pick(0, 1) != 0); break;
+                case 25: trace_multi(c, pick(0, 2), pick(1, MAX_MULTI), pick(0, 2) == 0 ? 0 : pick(1, RT_MULTIHIT_MAX), pick(0, 1) != 0); break;
+                case 26: winding_numbers(c, pick(1, MAX_RAYS), pick(0, 1) != 0, pick(1, 3)); break;
+                case 27: signed_distance(c, pick(1, MAX_RAYS), pick(0, 1) != 0, pick(0, 1) != 0); break;
+                case 28:
                     g_call = "(the caller waits for its stream)";
                     REQUIRE(hipStreamSynchronize(streams[c.s]) == hipSuccess);
                     break;
@@ -887,6 +1006,7 @@ int main(int argc, char **argv)
         refused = w.refused;
         rt_scene_builder_destroy(w.b_plain);
         rt_scene_builder_destroy(w.b_mesh);
+        rt_scene_builder_destroy(w.b_textured);
     }
     if (!g_allocs.empty()) violation("%zu allocations were never released", g_allocs.size());
     std::printf("launch order: %ld calls (%ld refused), %ld launches, %ld operations and %ld accesses logged, %ld buffers released on the strength of hipFree's wait, "

@@ -22,7 +22,6 @@
 #include "rt_math.h"
 
 #include "launcher_stubs.h"
-#include "update_stubs.h"
 
 #define CHECK(cond, what)                                                                             \
     do {                                                                                              \
@@ -277,7 +276,7 @@ static int refusals()
             t[at] = v;
             CHECK(rt_scene_update_mesh(&ctx, &scene, 1, t.data(), 5) == RT_ERR_INVALID && said(ctx, "not finite"), "a vertex that is not finite, or too large");
         }
-    CHECK(g_rebuild_launches == 0 && g_launches == 0, "a refused call reached a launcher");
+    CHECK(g_launches == 0, "a refused call reached a launcher");
     CHECK(!ctx.launched && !ctx.have_timing && ctx.last_stream == nullptr, "a refused call touched the launch order");
     CHECK(scene.uid == 41 && empty.uid == 42 && scene.updates.empty() && empty.updates.empty(), "a refused call touched the scene");
     return 0;

@@ -1,4 +1,4 @@
-"""The recipe the stand-alone host programs of tests/sanitize/ share: one program (its own main, kernel launchers from launcher_stubs.h) and
+"""The recipe the stand-alone host programs of tests/sanitize/ share: one program (its own main, every kernel launcher of rt_launch.h from launcher_stubs.h) and
 the library's host translation units it drives, compiled as host C++ with -fsanitize=address,undefined against the HIP runtime's API header,
 linked with the runtime library and run directly, once per seed, with nothing preloaded.  CPU only.
 

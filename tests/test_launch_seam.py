@@ -56,7 +56,7 @@ def test_every_launcher_is_defined_once_in_the_kernel_headers():
     # the development builds' fallbacks: ray-kernel launchers that the header declares, and behind its include
     ray = _text(os.path.join(CSRC, "rt_ray_kernels.h"))
     fallbacks = [m.group(1) for m in DEFINITION.finditer(ray)]
-    assert sorted(fallbacks) == ["rt_launch_ao", "rt_launch_occlusion", "rt_launch_query"], fallbacks
+    assert sorted(fallbacks) == ["rt_launch_ao", "rt_launch_multihit", "rt_launch_multihit_uv", "rt_launch_occlusion", "rt_launch_query"], fallbacks
     assert ray.index('#include "rt_launch.h"') < DEFINITION.search(ray).start()
 
 
@@ -75,13 +75,20 @@ def test_the_stubs_define_every_launcher_once_and_no_program_defines_one():
 
 
 def test_the_patterns_find_what_they_are_for():
-    """the forms the parent commit had, which must not come back unseen"""
+    """the forms the parent commits had, which must not come back unseen: a prototype in a caller, a stub in a program, and the launchers that
+    were declared in their family's header and fell back at the foot of their kernel header"""
     old = ('extern "C" hipError_t rt_launch_exhaustive(unsigned long long *out4, hipStream_t stream);\n'
            'extern "C" hipError_t rt_launch_blend_tiles(const float *partial, long long plane_floats,\n'
            '                                            const uint32_t *tile_list, hipStream_t stream);\n'
            'extern "C" int rt_kernel_blocks_per_cu(rt_shape, size_t) { return 1; }\n'
            'extern "C" hipError_t rt_launch_ao(const rt_ao_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }\n'
+           'extern "C" {\n'
+           'hipError_t rt_launch_nearest(const rt_nearest_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);\n'
+           '}\n'
+           '#else\n'
+           'extern "C" hipError_t rt_launch_multihit(const rt_multihit_args *, rt_shape, int, int, size_t, hipStream_t) { return hipErrorNotSupported; }\n'
+           '#endif\n'
            '    if (e == hipSuccess) e = rt_launch_exhaustive(d, nullptr);\n'
            '    RT_HIP(ctx, rt_launch_rgba8(d_rgb, width * height, d_rgba, (hipStream_t)hip_stream), "launching rgba8 kernel");\n')
-    assert [m.group(1) for m in PROTOTYPE.finditer(old)] == ["rt_launch_exhaustive", "rt_launch_blend_tiles"]
-    assert [m.group(1) for m in DEFINITION.finditer(old)] == ["rt_kernel_blocks_per_cu", "rt_launch_ao"]
+    assert [m.group(1) for m in PROTOTYPE.finditer(old)] == ["rt_launch_exhaustive", "rt_launch_blend_tiles", "rt_launch_nearest"]
+    assert [m.group(1) for m in DEFINITION.finditer(old)] == ["rt_kernel_blocks_per_cu", "rt_launch_ao", "rt_launch_multihit"]

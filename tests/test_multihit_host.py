@@ -1,6 +1,6 @@
 """The host side of rt_trace_rays_multi[_device] (ray-tracer_amd/csrc/rt_multihit.h, rt_multihit_capi.cpp) as host C++ under
 AddressSanitizer + UndefinedBehaviorSanitizer, driven by tests/sanitize/multihit_host_check.cpp - a stand-alone program with its own main,
-the kernel launchers of tests/sanitize/launcher_stubs.h and the multi-hit kernel's of multihit_stubs.h, nothing preloaded (CPU only).  It
+the kernel launchers of tests/sanitize/launcher_stubs.h, nothing preloaded (CPU only).  It
 runs the kernel's walk and insert - the text the kernel compiles - as plain host code against the exhaustive sort over every candidate,
 byte for byte, on seeded random and adversarial scenes, and drives every refusal of both entry points.  The second test sets the same host
 code against the NumPy yardstick (tests/multihit_ref.py) on scenes of the suite: two independent statements of the header's definition,

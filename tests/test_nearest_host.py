@@ -1,6 +1,6 @@
 """The host side of rt_nearest_points[_device] (ray-tracer_amd/csrc/rt_nearest.h, rt_nearest_capi.cpp) as host C++ under AddressSanitizer +
 UndefinedBehaviorSanitizer, driven by tests/sanitize/nearest_host_check.cpp - a stand-alone program with its own main, the kernel launchers of
-tests/sanitize/launcher_stubs.h and the nearest-surface kernel's of nearest_stubs.h, nothing preloaded (CPU only).  It runs the kernel's
+tests/sanitize/launcher_stubs.h, nothing preloaded (CPU only).  It runs the kernel's
 traversal - the text the kernel compiles - as plain host code against the exhaustive minimum over every candidate, byte for byte, on seeded
 random and adversarial scenes, and drives every refusal of both entry points.  The second test sets the same host code against the NumPy
 yardstick (tests/nearest_ref.py) on scenes of the suite: two independent statements of the header's definition, equal as bytes."""

@@ -48,11 +48,11 @@ def test_the_plane_bookkeeping_follows_the_view(tmp_path):
 
 
 def test_the_library_has_the_pre_pass_launcher(rt):
-    """rt_capi.cpp refers to rt_cull_enqueue weakly, so that the host programs of tests/sanitize/ link without rt_kernel.hip; a library built
-    without the kernel would load and render every launch without a plane.  The shipped library must define the launcher, and says so itself."""
+    """rt_capi.cpp calls rt_launch_cull like every other launcher of rt_launch.h: a library without the pre-pass kernel does not link, and
+    the host programs of tests/sanitize/ link launcher_stubs.h's stand-in, which fails, so that they render without a plane.  The shipped
+    library defines the launcher."""
     L = rt.lib()
-    assert hasattr(L, "rt_cull_enqueue"), "libraytracer_amd.so does not define rt_cull_enqueue"
-    assert L.rt_debug_primary_cull_linked() == 1
+    assert hasattr(L, "rt_launch_cull"), "libraytracer_amd.so does not define rt_launch_cull"
 
 
 def estimate_tool():

@@ -1,6 +1,6 @@
 """The host side of the cube-map sky (ray-tracer_amd/csrc/rt_sky.h, rt_sky_capi.cpp and the camera sequences' checks in rt_views_capi.cpp
 they share) as host C++ under AddressSanitizer + UndefinedBehaviorSanitizer, driven by tests/sanitize/sky_host_fuzz.cpp - a stand-alone
-program with the kernel launchers of tests/sanitize/launcher_stubs.h and sky_stubs.h (CPU only): the lookup on random and special directions,
+program with the kernel launchers of tests/sanitize/launcher_stubs.h (CPU only): the lookup on random and special directions,
 the round trip, the packing of a map, every refusal of the entry points."""
 from sanitizer_programs import build_and_run
 
