@@ -619,6 +619,54 @@ rt_status rt_signed_distance_device(rt_ctx *ctx, rt_scene *scene, const float *d
 rt_status rt_signed_distance(rt_ctx *ctx, rt_scene *scene, const float *points, const float *max_dist, int64_t n, rt_nearest *nearest,
                              float *sdf);
 
+/* ---- fast winding numbers: a dipole cluster tree per mesh ----------------------------------------
+ * The queries above visit every triangle record for every point.  These replace a far CLUSTER of a mesh's triangles by its dipole (Barill,
+ * Dickson, Schmidt, Levin, Jacobson 2018, first order): an approximation of the winding number, but again a function DEFINED to the bit -
+ * given the cluster tree (reported by rt_debug_winding_tree / rt_debug_scene_winding_tree; the topology is no part of the definition),
+ * binary32, nothing fused, in the order written here - so tests/winding_fast_ref.py gives the same bytes.  How far it lies from the exact
+ * answer is measured separately (tests/golden/winding_fast_meta.json).  Only an object of type mesh goes through its tree: spheres,
+ * cuboids, loose triangles and quads answer exactly as above, so a scene without a mesh answers the exact query's bytes.
+ *
+ * The tree of a mesh.  Topology: built on the host at the scene's first fast query from the commit-time records in commit order -
+ * recursively the axis with the longest extent of the triangle centroids, a stable sort along it, the first ceil(m / 2) triangles to the
+ * left, until a set holds at most RT_WINDING_LEAF_TRIS.  Clusters are stored in preorder, left child first (the left child of cluster i
+ * is i + 1, the right one skip[i + 1]); skip: the next cluster not in the subtree; a leaf has count > 0 and holds the triangles at
+ * positions first .. first + count - 1 of the CLUSTER ORDER, which the order list maps to commit indices.  It never changes afterwards.
+ * Moments: recomputed on the device, on the caller's stream ahead of the query, at the first fast query and after every
+ * rt_scene_update_mesh[_device] of the scene.
+ *   leaf, over its triangles in cluster order: n = (s1.y*s2.z - s1.z*s2.y, s1.z*s2.x - s1.x*s2.z, s1.x*s2.y - s1.y*s2.x), every component's
+ *     sign bit flipped where the flip bit is 1; a = sqrt(dot(n, n)); g = p0 + (s1 + s2) * RT_WN_THIRD per component;
+ *     Msum = Msum + n; Asum = Asum + a; Gsum = Gsum + a * g (all from 0.0f); lo, hi: from p0 of the first triangle, then over the corners
+ *     p0, p0 + s1, p0 + s2 of every triangle in that order lo = c < lo ? c : lo, hi = hi < c ? c : hi per component.
+ *   internal cluster: the left child's sums + the right child's, left operand first; lo = R.lo < L.lo ? R.lo : L.lo, hi = L.hi < R.hi ? R.hi : L.hi.
+ *   per cluster: c = Asum > 0 ? Gsum / Asum : lo (three divisions); M = 0.25f * Msum (a dipole term is then in the unit of atan2(det, den),
+ *     half a solid angle); e_k = (c_k - lo_k) > (hi_k - c_k) ? (c_k - lo_k) : (hi_k - c_k); r2 = dot(e, e).
+ * The answer of a mesh whose clusters are [c0, c1) for the point p, beta2 = beta * beta rounded once on the host:
+ *   i = c0; A = 0.0f
+ *   while i < c1:  d = c_i - p; d2 = dot(d, d)
+ *     if d2 > beta2 * r2_i:   A = A + dot(M_i, d) / (d2 * sqrt(d2)); i = skip_i
+ *     else if count_i > 0:    A = A + term (negated where the flip bit is 1) over the leaf's triangles in cluster order; i = skip_i
+ *     else:                   i = i + 1
+ *   w = A * RT_INV_2PI
+ * beta = +inf: nothing is far (inf * 0 is a NaN and the compare false), the answer is the exact terms summed in cluster order.  Everything
+ * else - the other object types, RT_WINDING_SOLIDS' sum in list order, points that are not finite, a NaN sum, inside, sdf - is as above.
+ * A smaller beta visits fewer clusters and errs more; RT_WINDING_BETA_DEFAULT is Barill's 2.  The fast path pays on large meshes; on a mesh
+ * of a few hundred triangles the exact query can be as quick (DESIGN.md section 28 has the measurements). */
+#define RT_WINDING_LEAF_TRIS 8
+#define RT_WINDING_BETA_DEFAULT 2.0f
+#define RT_WN_THIRD 0x1.555556p-2f      /* the binary32 nearest to 1 / 3 */
+/* As rt_winding_numbers[_device], with `beta` > 0 (+inf allowed; a NaN, zero or a negative beta is RT_ERR_INVALID).  The scene's first fast
+ * query also builds and uploads its cluster trees before it returns; a failed allocation leaves the scene as it was. */
+rt_status rt_winding_numbers_fast_device(rt_ctx *ctx, rt_scene *scene, const float *d_points, int64_t n, int32_t object, float beta,
+                                         float *d_winding, uint8_t *d_inside, void *hip_stream);
+rt_status rt_winding_numbers_fast(rt_ctx *ctx, rt_scene *scene, const float *points, int64_t n, int32_t object, float beta, float *winding,
+                                  uint8_t *inside);
+/* As rt_signed_distance[_device]: the nearest-surface launch, then the fast kernel over RT_WINDING_SOLIDS signing the distance. */
+rt_status rt_signed_distance_fast_device(rt_ctx *ctx, rt_scene *scene, const float *d_points, const float *d_max_dist, int64_t n, float beta,
+                                         rt_nearest *d_nearest, float *d_sdf, void *hip_stream);
+rt_status rt_signed_distance_fast(rt_ctx *ctx, rt_scene *scene, const float *points, const float *max_dist, int64_t n, float beta,
+                                  rt_nearest *nearest, float *sdf);
+
 /* ---- multi-hit ray queries: the first k hits of a ray, and hit counts ----------------------------
  * What lies BEHIND the first surface: transparency and x-ray views, the thickness of a part along a ray, "select through" picking,
  * the number of surfaces between two points, crossing counts.  One launch instead of k chained rt_trace_rays calls re-rooted at
@@ -941,6 +989,24 @@ rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out);
 /* the same view of a committed scene AS IT IS ON THE DEVICE (waits for the device first): what rt_scene_update_mesh[_device] is tested by.
  * Pointers stay valid until the next call on the same scene or its destruction. */
 rt_status rt_debug_scene_read(rt_ctx *ctx, rt_scene *scene, rt_flat_view *out);
+/* The cluster trees of the fast winding numbers (tests only).  Clusters of all meshes back to back; skip and first are indices into these
+ * arrays (first: into order); object_range: per object of the list (c0, c1), its clusters, (0, 0) for what is not a mesh; order: per
+ * flattened triangle index, for a mesh's range [prim_start + position in cluster order] = the commit index within the mesh, elsewhere 0;
+ * position: likewise, = the flattened index of the record that holds that triangle now (the BVH's leaf order, which an update changes);
+ * moments: per cluster 8 floats (c.xyz, r2, M.xyz, 0). */
+typedef struct rt_winding_tree_view {
+    const int32_t *skip, *first, *count; int32_t num_clusters;
+    const int32_t *object_range; int32_t num_objects;
+    const int32_t *order; int32_t num_triangles;
+    const int32_t *position;
+    const float *moments;
+} rt_winding_tree_view;
+/* from a builder, no device: the topology and the moments as the host text computes them from the commit-time records.  Pointers stay valid
+ * until the next call on the same builder or its destruction. */
+rt_status rt_debug_winding_tree(rt_scene_builder *b, rt_winding_tree_view *out);
+/* from a committed scene: the same as the device holds it now (builds and refits first if no fast query has; waits for the device).
+ * Pointers stay valid until the next call on the same scene or its destruction. */
+rt_status rt_debug_scene_winding_tree(rt_ctx *ctx, rt_scene *scene, rt_winding_tree_view *out);
 /* The primary-ray cull (ray-tracer_amd/csrc/rt_cull.h): render launches of a mesh scene that runs rt_traits_kernel on 1024 threads are handed one bit per
  * pixel of the view, "no primary ray of this pixel can reach a leaf of any mesh", computed on the device once per (scene revision, camera, image size,
  * antialias flag); RT_AMD_PRIMARY_CULL=0 (read by rt_ctx_create) renders without it.  Frames are bit-identical either way.

@@ -60,6 +60,12 @@ class rt_flat_view(C.Structure):
                 ("traits", C.c_int32), ("kernel_variant", C.c_int32), ("tri_flip", C.POINTER(C.c_uint8))]
 
 
+class rt_winding_tree_view(C.Structure):
+    _fields_ = [("skip", C.POINTER(C.c_int32)), ("first", C.POINTER(C.c_int32)), ("count", C.POINTER(C.c_int32)), ("num_clusters", C.c_int32),
+                ("object_range", C.POINTER(C.c_int32)), ("num_objects", C.c_int32), ("order", C.POINTER(C.c_int32)), ("num_triangles", C.c_int32),
+                ("position", C.POINTER(C.c_int32)), ("moments", C.POINTER(C.c_float))]
+
+
 class rt_denoise_params(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("sigma_colour", C.c_float), ("sigma_depth", C.c_float), ("normal_power_log2", C.c_int32),
                 ("albedo_floor", C.c_float), ("reserved", C.c_int32 * 3)]
@@ -89,6 +95,7 @@ HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
 NEAREST_DTYPE = np.dtype([("distance", np.float32), ("distance2", np.float32), ("point", np.float32, (3,)), ("object", np.int32),
                           ("triangle", np.int32), ("reserved", np.int32)])
 WINDING_SOLIDS = -1                                 # RT_WINDING_SOLIDS: the `object` that asks for the sum over the spheres, cuboids and meshes
+WINDING_BETA_DEFAULT, WINDING_LEAF_TRIS = 2.0, 8   # RT_WINDING_BETA_DEFAULT, RT_WINDING_LEAF_TRIS: the fast winding numbers' accuracy parameter and leaf size
 MULTIHIT_MAX = 8                                  # RT_MULTIHIT_MAX: the most records per ray of trace_rays_multi
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
 VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
@@ -183,6 +190,10 @@ ABI = {
     "rt_winding_numbers": (st, [vp, vp, fp, i64, i32, fp, vp]),
     "rt_signed_distance_device": (st, [vp, vp, vp, vp, i64, vp, vp, vp]),
     "rt_signed_distance": (st, [vp, vp, fp, fp, i64, vp, fp]),
+    "rt_winding_numbers_fast_device": (st, [vp, vp, vp, i64, i32, f32, vp, vp, vp]),
+    "rt_winding_numbers_fast": (st, [vp, vp, fp, i64, i32, f32, fp, vp]),
+    "rt_signed_distance_fast_device": (st, [vp, vp, vp, vp, i64, f32, vp, vp, vp]),
+    "rt_signed_distance_fast": (st, [vp, vp, fp, fp, i64, f32, vp, fp]),
     "rt_trace_rays_multi_device": (st, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
     "rt_trace_rays_multi": (st, [vp, vp, fp, fp, fp, i64, i32, vp, i32p]),
     "rt_occluded_rays_device": (st, [vp, vp, vp, vp, vp, i64, vp, vp]),
@@ -207,6 +218,8 @@ ABI = {
     "rt_to_rgba8_device": (st, [vp, vp, i32, i32, vp, vp]),
     "rt_debug_flatten": (st, [vp, C.POINTER(rt_flat_view)]),
     "rt_debug_scene_read": (st, [vp, vp, C.POINTER(rt_flat_view)]),
+    "rt_debug_winding_tree": (st, [vp, C.POINTER(rt_winding_tree_view)]),
+    "rt_debug_scene_winding_tree": (st, [vp, vp, C.POINTER(rt_winding_tree_view)]),
     "rt_debug_primary_cull": (st, [vp, u32p, i32, i32p]),
     "rt_debug_primary_cull_host": (st, [C.POINTER(rt_flat_view), cam, i32, u32p, C.POINTER(C.c_int64)]),
     "rt_debug_eval": (st, [vp, i32, u32p, u32p, i32]),

@@ -800,7 +800,11 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
     return "";
 }
 
-rt_scene_builder::~rt_scene_builder() { delete debug_flat; }
+rt_scene_builder::~rt_scene_builder()
+{
+    delete debug_flat;
+    if (debug_winding) debug_winding_free(debug_winding);
+}
 
 extern "C" rt_status rt_debug_flatten(rt_scene_builder *b, rt_flat_view *out)
 {

@@ -35,6 +35,8 @@ struct rt_scene_builder {
     std::vector<HostObject> objs;
     std::string err;
     FlatScene *debug_flat = nullptr;     /* owned; rt_debug_flatten */
+    void *debug_winding = nullptr;       /* owned, with how to free it; rt_debug_winding_tree (rt_winding_capi.cpp) */
+    void (*debug_winding_free)(void *) = nullptr;
     ~rt_scene_builder();
 };
 

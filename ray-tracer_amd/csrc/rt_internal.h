@@ -269,6 +269,15 @@ struct rt_scene {
     std::map<int32_t, MeshUpdate> updates;   /* by object index */
     DevBuf<int32_t> d_perm;              /* per triangle of a mesh: the commit index of the one at that leaf position, as of the last update */
     DevBuf<uint32_t> d_flip;             /* flat.tri_flip_commit, four bytes to a word: made at the scene's first winding-number query (rt_winding_capi.cpp) */
+    /* the fast winding numbers' cluster trees, made at the scene's first fast query (rt_winding_capi.cpp): the topology on the host and on the
+     * device (d_wn_ints: object_range, inv and levels back to back), the records gathered in cluster order, the clusters' sums and moments.
+     * wn_stale: the moments are not those of the vertices on the device - the refit runs ahead of the next fast query */
+    rt_wn_tree wn_tree;
+    bool wn_built = false, wn_stale = true;
+    DevBuf<rt_f4> d_wn_topo, d_wn_rec, d_wn_sums, d_wn_moments;
+    DevBuf<int32_t> d_wn_ints;
+    std::vector<float> wn_read;          /* rt_debug_scene_winding_tree's copy of the moments on the device ... */
+    std::vector<int32_t> wn_position;    /* ... and where the device's triangle list has every triangle of the cluster order now */
     FlatScene debug_read;                /* rt_debug_scene_read's copy of what is on the device */
     /* (members go in reverse order: the blob is freed first, the texels last) */
     DevBuf<float> d_tex;

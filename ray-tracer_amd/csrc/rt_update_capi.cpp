@@ -159,6 +159,7 @@ extern "C" rt_status rt_scene_update_mesh_device(rt_ctx *ctx, rt_scene *scene, i
         return RT_OK;
     });
     if (st != RT_OK) return st;
+    scene->wn_stale = true;              /* the fast winding numbers' moments are refitted ahead of the next fast query (rt_winding_capi.cpp) */
     scene->uid = next_scene_uid();       /* the view cached for the old geometry, its tile order and costs, is not found again */
     return RT_OK;
 }

@@ -2,7 +2,10 @@
  * example_sdf.cpp — the winding-number queries of raytracer.hpp: a slice of the monkey's SIGNED distance field written as a binary PGM
  * (8-bit: mid grey on the surface, darker inside, lighter outside, saturating `reach` away), and one point probed on its own.
  *
- *   example_sdf <models_dir> <width> <height> <out.pgm>
+ *   example_sdf <models_dir> <width> <height> <out.pgm> [beta]
+ *
+ * With a beta the slice is answered a second time by the fast winding numbers (Renderer::signed_distance_fast, the dipole cluster tree) and
+ * a third line says how many of its signs differ from the exact ones; without it nothing of that runs and the output is as it always was.
  *
  * The scene is the monkey alone (low_poly_monkey.obj as monkey_test_scene places it); the slice is the plane z = 1.6 through it, x and y
  * from -0.6 to 0.6.  Prints, each on a line of its own:
@@ -23,7 +26,7 @@ using namespace rtamd;
 int main(int argc, char **argv)
 {
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s <models_dir> <width> <height> <out.pgm>\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <models_dir> <width> <height> <out.pgm> [beta]\n", argv[0]);
         return 2;
     }
     const int W = std::atoi(argv[2]), H = std::atoi(argv[3]);
@@ -61,6 +64,13 @@ int main(int argc, char **argv)
             inside += field[i] < 0;
         }
         std::printf("slice: %zu points, %zu inside, sdf from %.9g to %.9g\n", field.size(), inside, lowest, highest);
+        if (argc > 5) {
+            const float beta = (float)std::atof(argv[5]);
+            const std::vector<float> fast = renderer.signed_distance_fast(points, beta);
+            size_t differ = 0;
+            for (size_t i = 0; i < field.size(); i++) differ += (fast[i] < 0) != (field[i] < 0);
+            std::printf("fast: beta %.9g, %zu of %zu signs differ from the exact ones\n", beta, differ, field.size());
+        }
         FILE *fp = std::fopen(argv[4], "wb");
         if (!fp) throw std::runtime_error("cannot open output file");
         std::fprintf(fp, "P5\n%d %d\n255\n", W, H);

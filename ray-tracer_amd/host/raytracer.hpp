@@ -537,6 +537,27 @@ public:
                                  sdf.data()));
         return sdf;
     }
+    /* winding_numbers through the meshes' dipole cluster trees (rt_winding_numbers_fast): far clusters of triangles answer with their dipole.
+     * beta > 0 (infinity allowed): the larger, the closer to the exact answer and the slower.  Pays on meshes of thousands of triangles. */
+    std::vector<float> winding_numbers_fast(const std::vector<float> &points, int32_t object = RT_WINDING_SOLIDS, float beta = RT_WINDING_BETA_DEFAULT)
+    {
+        if (points.size() % 3 != 0) throw std::invalid_argument("points must hold n x 3 floats");
+        std::vector<float> w(points.size() / 3);
+        check(rt_winding_numbers_fast(ctx_, scene_, points.data(), (int64_t)w.size(), object, beta, w.data(), nullptr));
+        return w;
+    }
+    /* signed_distance with the sign from the fast winding numbers (rt_signed_distance_fast) */
+    std::vector<float> signed_distance_fast(const std::vector<float> &points, float beta = RT_WINDING_BETA_DEFAULT, const std::vector<float> &max_dist = {},
+                                            std::vector<rt_nearest> *records = nullptr)
+    {
+        if (points.size() % 3 != 0) throw std::invalid_argument("points must hold n x 3 floats");
+        std::vector<float> sdf(points.size() / 3);
+        if (!max_dist.empty() && max_dist.size() != sdf.size()) throw std::invalid_argument("max_dist must hold n floats, or none");
+        if (records) records->resize(sdf.size());
+        check(rt_signed_distance_fast(ctx_, scene_, points.data(), max_dist.empty() ? nullptr : max_dist.data(), (int64_t)sdf.size(), beta,
+                                      records ? records->data() : nullptr, sdf.data()));
+        return sdf;
+    }
     /* The first k hits of every ray in order along it (rt_trace_rays_multi): origins, directions hold n x 3 floats, tmax n limits or none;
      * k from 1 to RT_MULTIHIT_MAX.  hits holds n * k records, [ray][rank], the ones behind a ray's last hit being misses; counts the records
      * each ray has. */

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import scenes
 from ._abi import (KERNEL_VARIANTS, SCENE_TRAITS, RT_ERR_BUSY, RT_ERR_INVALID, RT_ERR_IO, RT_ERR_NO_DEVICE, RT_ERR_UNSUPPORTED, RT_OK, PipelineFullError, RayTracerError,
-                   UnsupportedMeshError, _fp, lib, rt_camera, rt_flat_view, rt_material, rt_render_settings, rt_scene_info)
+                   UnsupportedMeshError, _fp, lib, rt_camera, rt_flat_view, rt_material, rt_render_settings, rt_scene_info, rt_winding_tree_view)
 
 
 class Material:
@@ -174,6 +174,16 @@ def _flat_view_arrays(v):
             "traits": {name for name, bit in SCENE_TRAITS.items() if v.traits & bit}, "kernel_variant": KERNEL_VARIANTS[v.kernel_variant]}
 
 
+def _winding_tree_arrays(v):
+    """an rt_winding_tree_view (rt_debug_winding_tree, rt_debug_scene_winding_tree) as a dict of copies"""
+    def ints(p, n):
+        return np.ctypeslib.as_array(p, shape=(n,)).copy() if p and n else np.zeros(0, np.int32)
+    nc = v.num_clusters
+    return {"skip": ints(v.skip, nc), "first": ints(v.first, nc), "count": ints(v.count, nc),
+            "object_range": ints(v.object_range, 2 * v.num_objects).reshape(-1, 2), "order": ints(v.order, v.num_triangles), "position": ints(v.position, v.num_triangles),
+            "moments": np.ctypeslib.as_array(v.moments, shape=(nc, 8)).copy() if v.moments and nc else np.zeros((0, 8), np.float32)}
+
+
 class SceneObjects(_Handle):
     """The object list of a scene: reference SceneObjects src/main.cu:94-296 with the
     Object::create_* factories of src/objects.cu:845-906 as methods."""
@@ -261,6 +271,13 @@ class SceneObjects(_Handle):
         v = rt_flat_view()
         self._check(lib().rt_debug_flatten(self._h, C.byref(v)))
         return _flat_view_arrays(v)
+
+    def debug_winding_tree(self):
+        """The fast winding numbers' cluster trees as the host computes them, no device (tests only): skip, first, count [clusters],
+        object_range [objects, 2], order and position [triangles], moments [clusters, 8] (c.xyz, r2, M.xyz, 0)."""
+        v = rt_winding_tree_view()
+        self._check(lib().rt_debug_winding_tree(self._h, C.byref(v)))
+        return _winding_tree_arrays(v)
 
 
 class Camera:

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -289,12 +289,29 @@ def winding_numbers(ctx, scene, points, object=WINDING_SOLIDS, inside=False):
     return (w, flags) if inside else w
 
 
-def contains_points(ctx, scene, points, object=WINDING_SOLIDS):
-    """Which points lie inside (rt_winding_numbers, the containment bytes alone): n bool, True where |w| >= 0.5."""
+def contains_points(ctx, scene, points, object=WINDING_SOLIDS, beta=None):
+    """Which points lie inside (rt_winding_numbers, the containment bytes alone): n bool, True where |w| >= 0.5.  beta None: the exact
+    query; a number: the fast one (rt_winding_numbers_fast) with that beta."""
     p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
     flags = np.zeros(p.shape[0], np.uint8)
-    ctx._check(lib().rt_winding_numbers(ctx._h, scene._h, _fp(p)[1], p.shape[0], int(object), None, C.c_void_p(flags.ctypes.data)))
+    if beta is None:
+        ctx._check(lib().rt_winding_numbers(ctx._h, scene._h, _fp(p)[1], p.shape[0], int(object), None, C.c_void_p(flags.ctypes.data)))
+    else:
+        ctx._check(lib().rt_winding_numbers_fast(ctx._h, scene._h, _fp(p)[1], p.shape[0], int(object), float(beta), None, C.c_void_p(flags.ctypes.data)))
     return flags.astype(bool)
+
+
+def winding_numbers_fast(ctx, scene, points, object=WINDING_SOLIDS, beta=WINDING_BETA_DEFAULT, inside=False):
+    """winding_numbers through the meshes' dipole cluster trees (rt_winding_numbers_fast): far clusters of triangles answer with their
+    dipole, so the cost per point grows with the logarithm of a mesh's size and not with the size.  beta > 0 (inf allowed): the larger,
+    the closer to the exact answer and the slower; the result is a defined function of the scene and beta.  Objects that are no meshes
+    answer exactly.  Worth it on meshes of thousands of triangles; on a few hundred the exact query can be as quick."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    w = np.zeros(n, np.float32)
+    flags = np.zeros(n, np.uint8) if inside else None
+    ctx._check(lib().rt_winding_numbers_fast(ctx._h, scene._h, _fp(p)[1], n, int(object), float(beta), _fp(w)[1], C.c_void_p(flags.ctypes.data) if inside else None))
+    return (w, flags) if inside else w
 
 
 def winding_numbers_device(ctx, scene, points, object=WINDING_SOLIDS, winding=None, inside=None, n=None, stream=None):
@@ -302,10 +319,25 @@ def winding_numbers_device(ctx, scene, points, object=WINDING_SOLIDS, winding=No
     context's launch order.  `points` is a float32 torch tensor of 3 n elements on the scene's GPU, `winding` None or a float32 tensor of
     n, `inside` None or a uint8 tensor of n: returns (winding, inside), with a new winding tensor where neither was passed.  Or all three
     are device pointers as ints (one of the outputs may be None) together with n."""
+    return _winding_device(ctx, scene, points, object, None, winding, inside, n, stream)
+
+
+def winding_numbers_fast_device(ctx, scene, points, object=WINDING_SOLIDS, beta=WINDING_BETA_DEFAULT, winding=None, inside=None, n=None, stream=None):
+    """Device-buffer form of winding_numbers_fast (rt_winding_numbers_fast_device): the arguments of winding_numbers_device and beta.  The
+    trees' moments are refitted on `stream` ahead of the query when the scene was updated since the last fast query."""
+    return _winding_device(ctx, scene, points, object, float(beta), winding, inside, n, stream)
+
+
+def _winding_device(ctx, scene, points, object, beta, winding, inside, n, stream):
+    def call(p, count, w, f):
+        if beta is None:
+            ctx._check(lib().rt_winding_numbers_device(ctx._h, scene._h, _dptr(p), count, int(object), _dptr(w), _dptr(f), _dptr(stream)))
+        else:
+            ctx._check(lib().rt_winding_numbers_fast_device(ctx._h, scene._h, _dptr(p), count, int(object), beta, _dptr(w), _dptr(f), _dptr(stream)))
     if isinstance(points, int):
         if n is None:
             raise ValueError("device pointers need n, the number of points")
-        ctx._check(lib().rt_winding_numbers_device(ctx._h, scene._h, _dptr(points), int(n), int(object), _dptr(winding), _dptr(inside), _dptr(stream)))
+        call(points, int(n), winding, inside)
         return winding, inside
     import torch
     ptr, count = _device_floats(points, 3, "points")
@@ -317,8 +349,7 @@ def winding_numbers_device(ctx, scene, points, object=WINDING_SOLIDS, winding=No
         raise ValueError("winding must be a contiguous float32 tensor on the GPU, one per point")
     if inside is not None and (str(inside.dtype) != "torch.uint8" or not inside.is_contiguous() or not inside.is_cuda or inside.numel() != count):
         raise ValueError("inside must be a contiguous uint8 tensor on the GPU, one per point")
-    ctx._check(lib().rt_winding_numbers_device(ctx._h, scene._h, _dptr(ptr), count, int(object), _dptr(winding.data_ptr() if winding is not None else None),
-                                               _dptr(inside.data_ptr() if inside is not None else None), _dptr(stream)))
+    call(ptr, count, winding.data_ptr() if winding is not None else None, inside.data_ptr() if inside is not None else None)
     return winding, inside
 
 
@@ -335,14 +366,41 @@ def signed_distance(ctx, scene, points, max_dist=None):
     return sdf, rec
 
 
+def signed_distance_fast(ctx, scene, points, max_dist=None, beta=WINDING_BETA_DEFAULT):
+    """signed_distance with the sign from the fast winding numbers (rt_signed_distance_fast): the records are the same, the sign is
+    winding_numbers_fast's."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = p.shape[0]
+    lim = _limits(max_dist, n)
+    rec = np.zeros(n, NEAREST_DTYPE)
+    sdf = np.zeros(n, np.float32)
+    ctx._check(lib().rt_signed_distance_fast(ctx._h, scene._h, _fp(p)[1], _fp(lim)[1] if lim is not None else None, n, float(beta), C.c_void_p(rec.ctypes.data),
+                                             _fp(sdf)[1]))
+    return sdf, rec
+
+
+def signed_distance_fast_device(ctx, scene, points, max_dist=None, beta=WINDING_BETA_DEFAULT, sdf=None, records=None, n=None, stream=None):
+    """Device-buffer form of signed_distance_fast (rt_signed_distance_fast_device): the arguments of signed_distance_device and beta."""
+    return _signed_distance_device(ctx, scene, points, max_dist, float(beta), sdf, records, n, stream)
+
+
 def signed_distance_device(ctx, scene, points, max_dist=None, sdf=None, records=None, n=None, stream=None):
     """Device-buffer form (rt_signed_distance_device), asynchronous on `stream` and in the context's launch order.  `points` is a float32 torch
     tensor of 3 n elements on the scene's GPU, `max_dist` None or one of n, `sdf` None or a float32 tensor of n, `records` None (the
     context keeps them) or a uint8 tensor of 32 n bytes: returns (sdf, records).  Or all are device pointers as ints together with n."""
+    return _signed_distance_device(ctx, scene, points, max_dist, None, sdf, records, n, stream)
+
+
+def _signed_distance_device(ctx, scene, points, max_dist, beta, sdf, records, n, stream):
+    def call(p, lim, count, rec, out):
+        if beta is None:
+            ctx._check(lib().rt_signed_distance_device(ctx._h, scene._h, _dptr(p), _dptr(lim), count, _dptr(rec), _dptr(out), _dptr(stream)))
+        else:
+            ctx._check(lib().rt_signed_distance_fast_device(ctx._h, scene._h, _dptr(p), _dptr(lim), count, beta, _dptr(rec), _dptr(out), _dptr(stream)))
     if isinstance(points, int):
         if n is None or sdf is None:
             raise ValueError("device pointers need n, the number of points, and sdf")
-        ctx._check(lib().rt_signed_distance_device(ctx._h, scene._h, _dptr(points), _dptr(max_dist), int(n), _dptr(records), _dptr(sdf), _dptr(stream)))
+        call(points, max_dist, int(n), records, sdf)
         return sdf, records
     import torch
     ptr, count = _device_floats(points, 3, "points")
@@ -359,14 +417,14 @@ def signed_distance_device(ctx, scene, points, max_dist=None, sdf=None, records=
         raise ValueError("sdf must be a contiguous float32 tensor on the GPU, one per point")
     if records is not None and (str(records.dtype) != "torch.uint8" or not records.is_contiguous() or not records.is_cuda or records.numel() != count * NEAREST_DTYPE.itemsize):
         raise ValueError("records must be a contiguous uint8 tensor on the GPU of 32 bytes per point")
-    ctx._check(lib().rt_signed_distance_device(ctx._h, scene._h, _dptr(ptr), _dptr(lim_ptr), count, _dptr(records.data_ptr() if records is not None else None),
-                                               _dptr(sdf.data_ptr()), _dptr(stream)))
+    call(ptr, lim_ptr, count, records.data_ptr() if records is not None else None, sdf.data_ptr())
     return sdf, records
 
 
-def signed_distance_grid(scene, lo, hi, shape, max_dist=None, stream=None):
+def signed_distance_grid(scene, lo, hi, shape, max_dist=None, stream=None, beta=None):
     """The scene's SIGNED distance field on distance_grid's lattice, answered by signed_distance_device without a host round trip.  Returns
-    (sdf, records): a float32 tensor [nx, ny, nz], negative inside, and the uint8 records [nx * ny * nz, 32], x slowest."""
+    (sdf, records): a float32 tensor [nx, ny, nz], negative inside, and the uint8 records [nx * ny * nz, 32], x slowest.  beta None: the
+    exact sign; a number: signed_distance_fast_device's with that beta."""
     import torch
     ctx = scene.ctx
     pts = _lattice(scene, lo, hi, shape)
@@ -374,5 +432,5 @@ def signed_distance_grid(scene, lo, hi, shape, max_dist=None, stream=None):
     if stream is None:
         stream = torch.cuda.current_stream(pts.device).cuda_stream      # the lattice was produced on it: the query is queued behind
     rec = torch.empty((pts.shape[0], NEAREST_DTYPE.itemsize), dtype=torch.uint8, device=pts.device)
-    sdf, _ = signed_distance_device(ctx, scene, pts, lim, records=rec, stream=stream)
+    sdf, _ = _signed_distance_device(ctx, scene, pts, lim, None if beta is None else float(beta), None, rec, None, stream)
     return sdf.reshape(int(shape[0]), int(shape[1]), int(shape[2])), rec

@@ -1,7 +1,7 @@
 """Time-varying geometry: a committed mesh rebuilt from new vertices on the device (rt_scene_update_mesh[_device], include/rt_amd.h).
 The methods are attached to :class:`Scene`: ``scene.update_mesh(i, triangles)``, ``scene.update_mesh_device(i, tensor)``."""
-from ._abi import REBUILD_LDS_TRIS, C, _dptr, fp, lib, np, rt_flat_view  # noqa: F401  (REBUILD_LDS_TRIS is re-exported)
-from .objects import Scene, _flat_view_arrays
+from ._abi import REBUILD_LDS_TRIS, C, _dptr, fp, lib, np, rt_flat_view, rt_winding_tree_view  # noqa: F401  (REBUILD_LDS_TRIS is re-exported)
+from .objects import Scene, _flat_view_arrays, _winding_tree_arrays
 
 
 def _triangle_rows(triangles):
@@ -42,6 +42,15 @@ def debug_read(self):
     return _flat_view_arrays(v)
 
 
+def debug_winding_tree(self):
+    """The fast winding numbers' cluster trees as the device holds them now, in the dict shape of SceneObjects.debug_winding_tree() (tests
+    only; builds and refits them if no fast query has, and waits for the device)."""
+    v = rt_winding_tree_view()
+    self.ctx._check(lib().rt_debug_scene_winding_tree(self.ctx._h, self._h, C.byref(v)))
+    return _winding_tree_arrays(v)
+
+
+Scene.debug_winding_tree = debug_winding_tree
 Scene.update_mesh = update_mesh
 Scene.update_mesh_device = update_mesh_device
 Scene.debug_read = debug_read
