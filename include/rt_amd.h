@@ -717,6 +717,86 @@ rt_status rt_trace_rays_multi_device(rt_ctx *ctx, const rt_scene *scene, const f
 rt_status rt_trace_rays_multi(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions, const float *tmax,
                               int64_t n, int32_t k, rt_hit *hits, int32_t *counts);
 
+/* ---- sphere-cast queries: where a moving ball first touches the scene ------------------------------
+ * "How far can a ball of radius r travel along d before it touches anything, and where does it touch?" - what a particle, a cloth
+ * vertex, a collision probe, a camera rig and a ball-nose tool path ask.  A ray has no thickness and slips between triangles a ball
+ * would hit; a chain of rt_nearest_points launches (step by distance - r, ask again) takes an unbounded number of launches and never
+ * ends on the surface.  Here: one call, n balls.
+ *
+ * The answer is DEFINED to the bit, like the nearest-surface and the multi-hit records: binary32 + - * / sqrt, comparisons and selects,
+ * every operation rounded once, nothing fused, in the order written here, so tests/sweep_ref.py (NumPy float32, every candidate of
+ * every query, no traversal) gives the same bytes.  dot and sq as above; cross(a, b) = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx).
+ * The ball (o, d, r) is taken as given, as a ray is for rt_trace_rays: d is not normalised, t is in units of its length.
+ *
+ * 1. Invalid input - a miss: a NaN or infinite component of o or d; dx == dy == dz == 0; r NaN, below zero or infinite; with a limit
+ *    array, tmax NaN or not above zero.  lim = min(tmax, RT_HIT_MISS_T), or RT_HIT_MISS_T without the array.
+ * 2. Start overlap - decided by the nearest-surface definition as it stands: if rt_nearest_points at o with the limit r is a hit, the
+ *    record is t = 0, centre = o, point / object / triangle those of that nearest record, feature = -1, overlap = 1.
+ * 3. Candidates otherwise, a time t each; dd = sq(d); `floor0(t)` is t <= 0 ? 0 : t (a NaN stays; a root that rounding put a hair
+ *    below zero is a contact at the start, not a tunnel: the tests are "approaching", never "t > epsilon").  The roots of the sphere and
+ *    the cylinder are NOT taken from the origin: the discriminant's rounding error grows with the square of the length of m, so m is
+ *    first moved to the path's point of closest approach, where it is about as long as the miss distance.
+ *    ball(m, rad) - the near root of |m + t d| = rad:  b = dot(m, d); t0 = -b / dd; n = d*t0 + m (per component one product, one sum);
+ *                    b2 = dot(n, d); c2 = sq(n) - rad*rad; disc = b2*b2 - dd*c2; offered when disc >= 0 and b < 0:
+ *                    t = floor0(t0 + (-b2 - sqrt(disc)) / dd).  The far root, farball(m, rad): the same with + sqrt(disc), offered when
+ *                    disc >= 0.
+ *    sphere (c, R):  m = o - c; outside when sq(m) > R*R: ball(m, R + r).  Inside: the FAR root on the inner surface (a sphere is a
+ *                    surface, as for rt_nearest_points), farball(m, R - r), only when R - r > 0.  feature = -1, triangle = -1;
+ *                    point = the nearest-surface definition's sphere point for p = centre.
+ *    triangle record (p0, s1, s2) - a loose triangle, both records of a quad (a one-way quad counts from both sides), a cuboid's
+ *    twelve, every mesh triangle: ap = o - p0; bp = ap - s1; cp = ap - s2; e3 = s2 - s1; rr = r*r.  Seven features in index order; the
+ *    candidate is the smallest t, on equal t the lower index (a NaN t is never smaller):
+ *      0 the face:   nrm = cross(s1, s2); nn = sq(nrm); len = sqrt(nn); h = dot(ap, nrm); dn = dot(d, nrm); neg = h < 0;
+ *                    hs = neg ? -h : h; ds = neg ? -dn : dn; rl = r * len.  Offered when nn > 0 and hs >= rl and ds < 0:
+ *                    t = floor0((rl - hs) / ds); centre = d*t + o; k = r / len; ks = neg ? -k : k; point = centre - nrm*ks;
+ *                    w = point - p0; d00 = sq(s1); d01 = dot(s1, s2); d11 = sq(s2); d20 = dot(w, s1); d21 = dot(w, s2);
+ *                    vn = d11*d20 - d01*d21; wn = d00*d21 - d01*d20; den = d00*d11 - d01*d01; accepted when vn >= 0 and wn >= 0
+ *                    and vn + wn <= den.
+ *      1..3 the edges (A, e, m) = (p0, s1, ap), (p0, s2, ap), (p0 + s1, e3, bp) - the infinite cylinder about the edge (Ericson,
+ *                    Real-Time Collision Detection 5.3.7), from the foot of the common perpendicular of the path and the edge's line:
+ *                    ee = sq(e); de = dot(d, e); me = dot(m, e); md = dot(m, d); a = ee*dd - de*de; b = ee*md - de*me; t0 = -b / a;
+ *                    n = d*t0 + m; s0 = dot(n, e) / ee; p = n - e*s0; me2 = dot(p, e); md2 = dot(p, d); mm2 = sq(p);
+ *                    b2 = ee*md2 - de*me2; c2 = ee*(mm2 - rr) - me2*me2; disc = b2*b2 - a*c2; t1 = (-b2 - sqrt(disc)) / a.  Offered
+ *                    when a > 0 and disc >= 0 and b < 0:  t = floor0(t0 + t1); s = s0 + (me2 + t1*de) / ee; accepted when
+ *                    0 <= s <= 1; point = A + e*s.
+ *      4..6 the vertices: ball(ap, r), ball(bp, r), ball(cp, r); point = p0, p0 + s1, p0 + s2.
+ *    The smallest accepted t is the first contact of a ball that does not overlap at the start: the volume the triangle sweeps out
+ *    against the ball's centre is the union of a prism, three capped cylinders and three spheres, and the prism's sides and the
+ *    cylinders' caps lie inside the other pieces.
+ *    a mesh's triangle, additionally: every box on its path - the mesh table's root box, then the child box stored in each node down to
+ *    the leaf - inflated by r (lo - r, hi + r, one rounding each) must pass the multi-hit section's slab test from tmin = 0, and the
+ *    key is K = max(t, B), B the largest entry distance over those inflated boxes (K = t outside a mesh).  K orders and limits, the
+ *    record reports the raw t.  The multi-hit section's argument holds word for word: every candidate below a box has a key no
+ *    smaller than that box's entry distance, so "skip a subtree whose inflated box fails the slab test or is entered beyond the best
+ *    key so far" is exact in any visiting order; a subtree entered AT the best key is still visited, because of the tie rule.
+ * 4. Winner: the smallest K; on equal K the lower object index, then the lower triangle index; a candidate counts when K <= lim; a
+ *    NaN never wins.  The record: t; centre = d*t + o (per component one product, one sum); point, formed again from the winner's
+ *    record; object; triangle (-1 on a sphere); feature; overlap = 0. */
+typedef struct __attribute__((aligned(16))) rt_sweep {
+    float t;               /* time of first contact, in units of |d|; RT_HIT_MISS_T for a miss */
+    float centre[3];       /* the ball's centre then: o + d * t */
+    float point[3];        /* the contact point on the surface */
+    int32_t object;        /* as rt_nearest.object; -1: a miss */
+    int32_t triangle;      /* as rt_nearest.triangle; -1 for a sphere or a miss */
+    int32_t feature;       /* -1 a scene sphere, a start overlap or a miss; 0 the face; 1..3 the edges (p0, s1), (p0, s2), (p0 + s1, s2 - s1);
+                              4..6 the vertices p0, p0 + s1, p0 + s2 */
+    int32_t overlap;       /* 1: the ball touches the scene already at t = 0 */
+    int32_t reserved;      /* 0 */
+} rt_sweep;                /* 48 bytes.  A miss is {RT_HIT_MISS_T, {0,0,0}, {0,0,0}, -1, -1, -1, 0, 0} bit for bit */
+
+/* Device-buffer form: d_origins, d_directions (n x 3 floats each), d_radius (n floats), d_tmax (n floats, or NULL) and d_out (n records,
+ * 16-byte aligned) are device memory of ctx's GPU.  Two launches inside one launch bracket: the nearest-surface kernel over d_origins
+ * with d_radius itself as its limits, into records the context keeps, then the sweep kernel, which reads them.  Asynchronous on
+ * hip_stream and ordered like rt_nearest_points_device.  n == 0 succeeds and touches nothing; n < 0, n > 2^30, a null pointer (other
+ * than d_tmax) with n > 0, a misaligned d_out and a scene committed on another context are RT_ERR_INVALID and leave the launch order
+ * as it was.  rt_last_kernel_ms then reports the sweep kernel (the second of the two).  A scene updated by
+ * rt_scene_update_mesh_device answers for its new geometry. */
+rt_status rt_sweep_spheres_device(rt_ctx *ctx, const rt_scene *scene, const float *d_origins, const float *d_directions,
+                                  const float *d_radius, const float *d_tmax, int64_t n, rt_sweep *d_out, void *hip_stream);
+/* Host-buffer form: uploads the balls (and limits), answers, downloads the records and returns when they are in `out`. */
+rt_status rt_sweep_spheres(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions, const float *radius,
+                           const float *tmax, int64_t n, rt_sweep *out);
+
 /* ---- occlusion (any-hit) ray queries and the light-visibility plane ------------------------------
  * "Is anything in the way?": line of sight, shadow masks, reachability probes.  For a ray (o, d) taken as given and a limit tmax,
  *     occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_trace_rays answers) finds a hit AND its t <= tmax.

@@ -94,6 +94,9 @@ HIT_MISS_T = np.float32(1073741824.0)      # RT_HIT_MISS_T
 # rt_nearest (include/rt_amd.h) as a NumPy record: what nearest_points returns.  A miss: distance and distance2 HIT_MISS_T, object -1
 NEAREST_DTYPE = np.dtype([("distance", np.float32), ("distance2", np.float32), ("point", np.float32, (3,)), ("object", np.int32),
                           ("triangle", np.int32), ("reserved", np.int32)])
+# rt_sweep (include/rt_amd.h) as a NumPy record: what sweep_spheres returns.  A miss: t HIT_MISS_T, object, triangle and feature -1
+SWEEP_DTYPE = np.dtype([("t", np.float32), ("centre", np.float32, (3,)), ("point", np.float32, (3,)), ("object", np.int32), ("triangle", np.int32),
+                        ("feature", np.int32), ("overlap", np.int32), ("reserved", np.int32)])
 WINDING_SOLIDS = -1                                 # RT_WINDING_SOLIDS: the `object` that asks for the sum over the spheres, cuboids and meshes
 WINDING_BETA_DEFAULT, WINDING_LEAF_TRIS = 2.0, 8   # RT_WINDING_BETA_DEFAULT, RT_WINDING_LEAF_TRIS: the fast winding numbers' accuracy parameter and leaf size
 MULTIHIT_MAX = 8                                  # RT_MULTIHIT_MAX: the most records per ray of trace_rays_multi
@@ -196,6 +199,8 @@ ABI = {
     "rt_signed_distance_fast": (st, [vp, vp, fp, fp, i64, f32, vp, fp]),
     "rt_trace_rays_multi_device": (st, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
     "rt_trace_rays_multi": (st, [vp, vp, fp, fp, fp, i64, i32, vp, i32p]),
+    "rt_sweep_spheres_device": (st, [vp, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "rt_sweep_spheres": (st, [vp, vp, fp, fp, fp, fp, i64, vp]),
     "rt_occluded_rays_device": (st, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "rt_occluded_rays": (st, [vp, vp, fp, fp, fp, i64, vp]),
     "rt_render_visibility_device": (st, [vp, vp, cam, fp, f32, vp, vp]),

@@ -78,7 +78,8 @@ hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t height, int32
                           int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream);
 
 /* ---- rt_nearest_kernel.h (in every build) ---- */
-/* the signature is the ray kernels'; `front` is not read: the kernel has the one front */
+/* the signature is the ray kernels'; front 0: the nearest-surface kernel, front 1: the sphere-cast kernel (rt_sweep_kernel.h), which reads the
+ * block's sw_ fields and the records a nearest-surface launch left in sw_nearest */
 hipError_t rt_launch_nearest(const rt_nearest_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
 
 /* ---- rt_winding_kernel.h (in every build) ---- */

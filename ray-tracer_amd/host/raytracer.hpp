@@ -508,6 +508,25 @@ public:
         check(rt_nearest_points(ctx_, scene_, point.data(), &max_dist, 1, &r));
         return r;
     }
+    /* Where a ball first touches the scene (rt_sweep_spheres): origins and directions hold n x 3 floats (a direction is taken as given: t is
+     * in units of its length), radius n floats, tmax n limits on t, or none.  A miss - nothing within the limit, or an input that is not
+     * valid - has object -1 and t RT_HIT_MISS_T; a ball that touches the scene at the start has overlap 1 and t 0. */
+    std::vector<rt_sweep> sweep_spheres(const std::vector<float> &origins, const std::vector<float> &directions, const std::vector<float> &radius,
+                                        const std::vector<float> &tmax = {})
+    {
+        if (origins.size() % 3 != 0 || directions.size() != origins.size()) throw std::invalid_argument("origins and directions must hold n x 3 floats each");
+        std::vector<rt_sweep> out(origins.size() / 3);
+        if (radius.size() != out.size()) throw std::invalid_argument("radius must hold n floats");
+        if (!tmax.empty() && tmax.size() != out.size()) throw std::invalid_argument("tmax must hold n floats, or none");
+        check(rt_sweep_spheres(ctx_, scene_, origins.data(), directions.data(), radius.data(), tmax.empty() ? nullptr : tmax.data(), (int64_t)out.size(), out.data()));
+        return out;
+    }
+    rt_sweep sweep_sphere(Vec3 origin, Vec3 direction, float radius, float tmax = INFINITY)
+    {
+        rt_sweep r;
+        check(rt_sweep_spheres(ctx_, scene_, origin.data(), direction.data(), &radius, &tmax, 1, &r));
+        return r;
+    }
     /* The generalized winding number of every point (rt_winding_numbers): points holds n x 3 floats; object an index of the scene's object
      * list, or RT_WINDING_SOLIDS for the sum over its spheres, cuboids and meshes.  1 (or -1) inside a closed surface, 0 outside. */
     std::vector<float> winding_numbers(const std::vector<float> &points, int32_t object = RT_WINDING_SOLIDS)

@@ -1,11 +1,11 @@
 """Queries: closest hits and first-hit planes, multi-hit queries (the first k hits of a ray, hit counts), occlusion (any-hit), the
 light-visibility plane, the ambient-occlusion plane, the nearest-surface queries (closest point and distance, which are no ray questions), and
-the winding-number queries (point containment, the signed distance)."""
+the winding-number queries (point containment, the signed distance), and the sphere-cast queries (where a moving ball first touches the scene)."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, SWEEP_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -434,3 +434,83 @@ def signed_distance_grid(scene, lo, hi, shape, max_dist=None, stream=None, beta=
     rec = torch.empty((pts.shape[0], NEAREST_DTYPE.itemsize), dtype=torch.uint8, device=pts.device)
     sdf, _ = _signed_distance_device(ctx, scene, pts, lim, None if beta is None else float(beta), None, rec, None, stream)
     return sdf.reshape(int(shape[0]), int(shape[1]), int(shape[2])), rec
+
+
+SweepRecord = SWEEP_DTYPE           # rt_sweep as a structured dtype: t, centre[3], point[3], object, triangle, feature, overlap, reserved
+
+
+def sweep_spheres(ctx, scene, origins, directions, radius, tmax=None):
+    """Where a ball of radius `radius` moving from origins[i] along directions[i] first touches the scene (rt_sweep_spheres): origins,
+    directions [n, 3] float32, the direction taken as it is (not normalised; t is in units of its length); radius a scalar or n float32;
+    tmax None, a scalar or n float32 limits on t.  Returns n records of SweepRecord: the time of first contact, the ball's centre then,
+    the contact point, the object, the flattened triangle index and which feature of the triangle was touched (0 the face, 1..3 an edge,
+    4..6 a vertex; -1 on a sphere); overlap 1 (with t 0) where the ball touches the scene already at the start.  A miss - nothing within
+    the limit, or an input that is not finite, a zero direction, a negative radius - has object -1 and t HIT_MISS_T."""
+    o, d = _ray_arrays(origins, directions)
+    n = o.shape[0]
+    r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (n,)))
+    lim = _ray_limits(tmax, n)
+    out = np.zeros(n, SWEEP_DTYPE)
+    ctx._check(lib().rt_sweep_spheres(ctx._h, scene._h, _fp(o)[1], _fp(d)[1], _fp(r)[1], _fp(lim)[1] if lim is not None else None, n, C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def sweep_spheres_device(ctx, scene, origins, directions, radius, tmax=None, out=None, n=None, stream=None):
+    """Device-buffer form (rt_sweep_spheres_device), asynchronous on `stream` (a hipStream_t as an int; None with tensors: torch's
+    current stream, which produced them; None with pointers: the default stream) and in the context's launch order.  origins, directions are float32 torch tensors of 3 n elements on the scene's GPU, radius a number or a
+    tensor of n, tmax None, a number or a tensor of n, out None or a uint8 tensor of 48 n bytes - or all are device pointers as ints
+    (tmax may be None) together with n.  With tensors the records come back as a uint8 tensor [n, 48] (the one passed as `out`, or a new
+    one): `.cpu().numpy().view(SweepRecord)` reads them."""
+    if isinstance(origins, int):
+        if n is None or out is None:
+            raise ValueError("device pointers need n, the number of balls, and out")
+        ctx._check(lib().rt_sweep_spheres_device(ctx._h, scene._h, _dptr(origins), _dptr(directions), _dptr(radius), _dptr(tmax), int(n), _dptr(out), _dptr(stream)))
+        return out
+    import torch
+    o_ptr, count = _device_floats(origins, 3, "origins")
+    d_ptr, n_d = _device_floats(directions, 3, "directions")
+    if n_d != count or (n is not None and int(n) != count):
+        raise ValueError("origins, directions and n differ")
+
+    # the stream the kernels are queued on: the one given, else torch's current stream (what produced the tensors), never the null stream
+    # behind torch's back - a number is broadcast on that stream, so that the fill is ordered ahead of the kernels
+    if stream is None:
+        stream = torch.cuda.current_stream(origins.device).cuda_stream
+    queue = torch.cuda.ExternalStream(int(stream), device=origins.device) if int(stream) else torch.cuda.default_stream(origins.device)
+
+    def per_ball(x, what):
+        if not torch.is_tensor(x):
+            with torch.cuda.stream(queue):
+                x = torch.full((count,), float(x), dtype=torch.float32, device=origins.device)
+            x.record_stream(queue)
+        ptr, m = _device_floats(x, 1, what)
+        if m != count:
+            raise ValueError("%s must hold one value per ball" % what)
+        return x, ptr
+    radius, r_ptr = per_ball(radius, "radius")
+    t_ptr = None
+    if tmax is not None:
+        tmax, t_ptr = per_ball(tmax, "tmax")
+    if out is None:
+        out = torch.empty((count, SWEEP_DTYPE.itemsize), dtype=torch.uint8, device=origins.device)
+    elif str(out.dtype) != "torch.uint8" or not out.is_contiguous() or not out.is_cuda or out.numel() != count * SWEEP_DTYPE.itemsize:
+        raise ValueError("out must be a contiguous uint8 tensor on the GPU of 48 bytes per ball")
+    ctx._check(lib().rt_sweep_spheres_device(ctx._h, scene._h, _dptr(o_ptr), _dptr(d_ptr), _dptr(r_ptr), _dptr(t_ptr), count, _dptr(out.data_ptr()), _dptr(stream)))
+    return out
+
+
+def sweep_grid(scene, lo, hi, shape, direction, radius, tmax=None, stream=None):
+    """A ball of `radius` sent along `direction` from every point of distance_grid's lattice (shape = (nx, ny, nz) points from corner lo
+    to corner hi inclusive), built with torch on the context's GPU and answered by sweep_spheres_device without a host round trip: with
+    a flat lattice above a part and the direction straight down, the rest heights of the ball - the dilated height field a ball-nose tool
+    path or a "place on surface" uses.  Returns (t, records): a float32 tensor [nx, ny, nz] (HIT_MISS_T where the ball meets nothing) and
+    the uint8 records [nx * ny * nz, 48], x slowest."""
+    import torch
+    ctx = scene.ctx
+    pts = _lattice(scene, lo, hi, shape)
+    dirs = torch.tensor([float(direction[0]), float(direction[1]), float(direction[2])], dtype=torch.float32, device=pts.device).repeat(pts.shape[0], 1).contiguous()
+    if stream is None:
+        stream = torch.cuda.current_stream(pts.device).cuda_stream      # the lattice was produced on it: the query is queued behind
+    rec = sweep_spheres_device(ctx, scene, pts, dirs, radius, tmax, stream=stream)
+    t = rec.view(torch.float32).reshape(-1, 12)[:, 0].reshape(int(shape[0]), int(shape[1]), int(shape[2]))
+    return t, rec
