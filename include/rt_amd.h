@@ -797,6 +797,66 @@ rt_status rt_sweep_spheres_device(rt_ctx *ctx, const rt_scene *scene, const floa
 rt_status rt_sweep_spheres(rt_ctx *ctx, const rt_scene *scene, const float *origins, const float *directions, const float *radius,
                            const float *tmax, int64_t n, rt_sweep *out);
 
+/* ---- box-overlap queries: which surfaces touch a box ----------------------------------------------
+ * The VOLUME question beside the ray and the point questions: "which surfaces lie in this region?" - what a voxeliser, the broad phase
+ * of a collision test, a "select everything in this box" tool and an octree or sparse-grid builder ask.  Thresholding a distance grid
+ * at a cell's half diagonal gives a superset and does not say which triangles; with rt_winding_numbers' containment for the interior,
+ * the surface test here completes a voxeliser.
+ *
+ * The answer is DEFINED to the bit, like its neighbours: binary32, every operation rounded once, nothing fused, in the order written
+ * here, so tests/overlap_ref.py (NumPy float32, every candidate of every box, no traversal) gives the same bytes.  dot, sq and cross as
+ * above.  A box (lo, hi) is axis-aligned and CLOSED: touching counts.
+ *
+ * Validity: all six floats finite and lo.a <= hi.a on every axis.  A box that is not valid overlaps nothing.
+ * Centre and half extents: c = lo*0.5f + hi*0.5f, h = hi*0.5f - lo*0.5f (two products, then one sum or difference, per component:
+ * no overflow for finite input).
+ * Candidates: the nearest-surface section's - every sphere, as a SURFACE, and every triangle record (p0, s1, s2): loose triangles, both
+ * records of a quad (a one-way quad counts from both sides), a cuboid's twelve, every mesh triangle.
+ *   sphere (cs, R): per axis e = max(max(lo - cs, cs - hi), 0) (the nearest section's box distance) and g = max(cs - lo, hi - cs);
+ *                   dmin2 = (sq(e.x) + sq(e.y)) + sq(e.z), dmax2 likewise from g, rr = R*R.  Overlaps when dmin2 <= rr and dmax2 >= rr:
+ *                   a box wholly inside the ball touches no surface.
+ *   triangle record: the separating-axis test of Akenine-Moller (2001) on the record as stored.  q0 = p0, q1 = p0 + s1, q2 = p0 + s2.
+ *                   Overlaps when none of thirteen axes separates:
+ *       the box's axes (3): axis a separates when all three q_i.a > hi.a or all three q_i.a < lo.a (compares on lo and hi themselves).
+ *       the plane (1):      v_i = q_i - c; nrm = cross(s1, s2); d = dot(nrm, v0); r = (h.x*|nrm.x| + h.y*|nrm.y|) + h.z*|nrm.z|;
+ *                           separates when d > r or d < -r.
+ *       the edges (9):      for f in f0 = s1, f1 = s2 - s1, f2 = -s2 the three axes
+ *                             px(v) = v.z*f.y - v.y*f.z, rad = h.y*|f.z| + h.z*|f.y|;
+ *                             py(v) = v.x*f.z - v.z*f.x, rad = h.x*|f.z| + h.z*|f.x|;
+ *                             pz(v) = v.y*f.x - v.x*f.y, rad = h.x*|f.y| + h.y*|f.x|;
+ *                           an axis separates when all three projections > rad or all three < -rad.
+ *     A compare with a NaN does not hold: an overflowed product leaves its axis unseparated, which is conservative.  A degenerate
+ *     record (s1 and s2 parallel, or zero) is tested as it stands and may be reported conservatively.  The thirteen verdicts have no
+ *     side effects: an implementation may take them in any order and leave at the first that separates.
+ *   a mesh's triangle, additionally: every box on its path - the mesh table's root box, then the child box stored in each node down to
+ *     the leaf - must overlap the query box by compares alone: nlo.a <= hi.a and lo.a <= nhi.a on all three axes.  This is the multi-hit
+ *     section's path rule without arithmetic: "skip a subtree whose box does not overlap" is exact in any visiting order, with no error
+ *     analysis.  The rule only bites where p0 + s1 rounds a hair outside a box built from the vertex itself;
+ *     tests/golden/overlap_meta.json has the measured share of such pairs.
+ * What the test is not: exact near touching.  Within a band of a few ulps of the scene's scale around "just touching" the thirteen
+ * rounded verdicts may fall either way (tests/golden/overlap_meta.json has the measured band).
+ * Output, for box i (each pointer optional, at least one given): d_counts[i] = the number of ALL candidates that overlap; d_any[i] =
+ * count > 0; for k > 0, d_ids[i*k + rank] = the k overlapping candidates lowest in (object, then triangle) order, ascending; slots past
+ * the count are {-1, -1}.  ANY-ONLY mode - only d_any asked for (k == 0, d_counts NULL): a box may stop at its first overlapping
+ * candidate; the byte is the same by definition. */
+#define RT_OVERLAP_MAX 8                /* ids per box, at most */
+typedef struct rt_overlap_id {
+    int32_t object;        /* index in the scene's object list; -1: no candidate at this rank */
+    int32_t triangle;      /* index of the triangle record in the flattened scene; -1 for a sphere or an empty slot */
+} rt_overlap_id;           /* 8 bytes */
+/* Device-buffer form: d_lo, d_hi (n x 3 floats each), d_ids (n * k records, [box][rank], 8-byte aligned), d_counts (n int32) and d_any
+ * (n bytes) are device memory of ctx's GPU; asynchronous on hip_stream and ordered like rt_trace_rays_device.  n == 0 succeeds and
+ * touches nothing.  RT_ERR_INVALID, leaving the launch order as it was: n < 0 or n > 2^30; k < 0 or k > RT_OVERLAP_MAX; a null box
+ * pointer with n > 0; d_ids null or misaligned while k > 0; d_ids, d_counts and d_any all null; a scene of another context; a scene of
+ * more than 4,096 objects (an id is one 32-bit word, object << 20 | triangle, a sphere's triangle field all ones).
+ * rt_last_kernel_ms then reports the overlap kernel.  A scene updated by rt_scene_update_mesh[_device] answers for its new geometry. */
+rt_status rt_overlap_boxes_device(rt_ctx *ctx, const rt_scene *scene, const float *d_lo, const float *d_hi, int64_t n, int32_t k,
+                                  rt_overlap_id *d_ids, int32_t *d_counts, uint8_t *d_any, void *hip_stream);
+/* Host-buffer form: uploads the boxes, answers, downloads each output whose pointer is not NULL and returns when they are in host
+ * memory (the context keeps the device buffers). */
+rt_status rt_overlap_boxes(rt_ctx *ctx, const rt_scene *scene, const float *lo, const float *hi, int64_t n, int32_t k, rt_overlap_id *ids,
+                           int32_t *counts, uint8_t *any);
+
 /* ---- occlusion (any-hit) ray queries and the light-visibility plane ------------------------------
  * "Is anything in the way?": line of sight, shadow masks, reachability probes.  For a ray (o, d) taken as given and a limit tmax,
  *     occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_trace_rays answers) finds a hit AND its t <= tmax.

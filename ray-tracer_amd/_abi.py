@@ -99,6 +99,9 @@ SWEEP_DTYPE = np.dtype([("t", np.float32), ("centre", np.float32, (3,)), ("point
                         ("feature", np.int32), ("overlap", np.int32), ("reserved", np.int32)])
 WINDING_SOLIDS = -1                                 # RT_WINDING_SOLIDS: the `object` that asks for the sum over the spheres, cuboids and meshes
 WINDING_BETA_DEFAULT, WINDING_LEAF_TRIS = 2.0, 8   # RT_WINDING_BETA_DEFAULT, RT_WINDING_LEAF_TRIS: the fast winding numbers' accuracy parameter and leaf size
+# rt_overlap_id (include/rt_amd.h) as a NumPy record: what overlap_boxes returns per rank.  An empty slot: {-1, -1}
+OVERLAP_ID_DTYPE = np.dtype([("object", np.int32), ("triangle", np.int32)])
+OVERLAP_MAX = 8                                   # RT_OVERLAP_MAX: the most ids per box of overlap_boxes
 MULTIHIT_MAX = 8                                  # RT_MULTIHIT_MAX: the most records per ray of trace_rays_multi
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
 VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
@@ -201,6 +204,8 @@ ABI = {
     "rt_trace_rays_multi": (st, [vp, vp, fp, fp, fp, i64, i32, vp, i32p]),
     "rt_sweep_spheres_device": (st, [vp, vp, vp, vp, vp, vp, i64, vp, vp]),
     "rt_sweep_spheres": (st, [vp, vp, fp, fp, fp, fp, i64, vp]),
+    "rt_overlap_boxes_device": (st, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "rt_overlap_boxes": (st, [vp, vp, fp, fp, i64, i32, vp, i32p, vp]),
     "rt_occluded_rays_device": (st, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "rt_occluded_rays": (st, [vp, vp, fp, fp, fp, i64, vp]),
     "rt_render_visibility_device": (st, [vp, vp, cam, fp, f32, vp, vp]),

@@ -36,6 +36,7 @@
 #include "rt_intersect.h"
 #include "rt_launch.h"
 #include "rt_math.h"
+#include "rt_overlap_kernel.h"
 #include "rt_ray_kernel.h"
 #include "rt_surface.h"
 #include "rt_traverse.h"
@@ -227,15 +228,15 @@ extern "C" hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *args, int
 }
 
 /* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
-/* rt_ray_kernel.h's table has two fronts per shape; this kernel has one, entered under both */
+/* rt_ray_kernel.h's table has two fronts per shape: 0 this kernel, 1 the box-overlap kernel (rt_overlap_kernel.h) on the same argument block */
 struct rt_multihit_kernels {
     typedef rt_multihit_args args;
-    template <int NT, bool HAS_MESH, int MODE, bool FRONT> static constexpr auto kernel = &rt_multihit_kernel<NT, HAS_MESH, MODE>;
+    template <int NT, bool HAS_MESH, int MODE, bool FRONT> static constexpr auto kernel = FRONT ? &rt_overlap_kernel<NT, HAS_MESH, MODE> : &rt_multihit_kernel<NT, HAS_MESH, MODE>;
 };
 
-extern "C" hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int, int num_cus, size_t lds_bytes, hipStream_t stream)
+extern "C" hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)
 {
-    return rt_ray_launch<rt_multihit_kernels>(args, shape, 0, num_cus, lds_bytes, stream);
+    return rt_ray_launch<rt_multihit_kernels>(args, shape, front, num_cus, lds_bytes, stream);
 }
 #endif
 

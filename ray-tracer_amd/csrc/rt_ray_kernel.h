@@ -1,6 +1,7 @@
 /*
  * rt_ray_kernel.h — the launch path the ray kernels (rt_query_kernel.h: closest hit; rt_occlusion_kernel.h: any hit; rt_ao_kernel.h: the
- * ambient-occlusion plane, one front under both values of `front`) share: one launcher
+ * ambient-occlusion plane, one front under both values of `front`; and, with a kernel of another kind as the second front, rt_nearest_kernel.h
+ * with the sphere-cast kernel and rt_multihit_kernel.h with the box-overlap kernel) share: one launcher
  * over the kernel (the LDS opt-in, the occupancy cache, the grid sized from the ray count) and one table of its instantiations over
  * RT_SHAPES.  The grid: one wave per 64 rays up to the persistent grid (every
  * CU filled), so a handful of rays stages the scene once, not once per CU.

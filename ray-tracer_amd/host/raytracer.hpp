@@ -605,6 +605,33 @@ public:
         check(rt_trace_rays_multi(ctx_, scene_, origins.data(), directions.data(), tmax.empty() ? nullptr : tmax.data(), (int64_t)counts.size(), 0, nullptr, counts.data()));
         return counts;
     }
+    /* Which surfaces touch every axis-aligned, closed box (rt_overlap_boxes): lo, hi hold n x 3 floats; k from 0 to RT_OVERLAP_MAX.  counts
+     * holds, per box, the number of ALL surfaces - spheres and triangle records - that overlap it; ids n * k records, [box][rank], the k of
+     * them lowest in (object, triangle) order, {-1, -1} behind a box's last.  A box that is not finite or has lo > hi overlaps nothing;
+     * a sphere is a surface: a box wholly inside it does not touch it. */
+    struct Overlaps {
+        std::vector<int32_t> counts;
+        std::vector<rt_overlap_id> ids;
+    };
+    Overlaps overlap_boxes(const std::vector<float> &lo, const std::vector<float> &hi, int k = 0)
+    {
+        if (lo.size() != hi.size() || lo.size() % 3 != 0) throw std::invalid_argument("lo and hi must hold n x 3 floats each");
+        if (k < 0 || k > RT_OVERLAP_MAX) throw std::invalid_argument("k must be 0 .. RT_OVERLAP_MAX");
+        const size_t n = lo.size() / 3;
+        Overlaps out;
+        out.counts.resize(n);
+        out.ids.resize(n * (size_t)k);
+        check(rt_overlap_boxes(ctx_, scene_, lo.data(), hi.data(), (int64_t)n, k, k > 0 ? out.ids.data() : nullptr, out.counts.data(), nullptr));
+        return out;
+    }
+    /* Whether any surface touches every box (rt_overlap_boxes in any-only mode: a box stops at its first overlapping surface): 1 or 0 */
+    std::vector<uint8_t> touches(const std::vector<float> &lo, const std::vector<float> &hi)
+    {
+        if (lo.size() != hi.size() || lo.size() % 3 != 0) throw std::invalid_argument("lo and hi must hold n x 3 floats each");
+        std::vector<uint8_t> any(lo.size() / 3);
+        check(rt_overlap_boxes(ctx_, scene_, lo.data(), hi.data(), (int64_t)any.size(), 0, nullptr, nullptr, any.data()));
+        return any;
+    }
     /* The first-hit planes of a view (rt_render_aov), all five of them: depth W*H, normal / albedo / ray W*H*3, object W*H */
     struct Aov {
         std::vector<float> depth, normal, albedo, ray;

@@ -1,11 +1,12 @@
 """Queries: closest hits and first-hit planes, multi-hit queries (the first k hits of a ray, hit counts), occlusion (any-hit), the
 light-visibility plane, the ambient-occlusion plane, the nearest-surface queries (closest point and distance, which are no ray questions), and
-the winding-number queries (point containment, the signed distance), and the sphere-cast queries (where a moving ball first touches the scene)."""
+the winding-number queries (point containment, the signed distance), the sphere-cast queries (where a moving ball first touches the scene), and
+the box-overlap queries (which surfaces touch a box; a voxeliser)."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, SWEEP_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, OVERLAP_ID_DTYPE, OVERLAP_MAX, SWEEP_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -514,3 +515,122 @@ def sweep_grid(scene, lo, hi, shape, direction, radius, tmax=None, stream=None):
     rec = sweep_spheres_device(ctx, scene, pts, dirs, radius, tmax, stream=stream)
     t = rec.view(torch.float32).reshape(-1, 12)[:, 0].reshape(int(shape[0]), int(shape[1]), int(shape[2]))
     return t, rec
+
+
+OverlapId = OVERLAP_ID_DTYPE        # rt_overlap_id as a structured dtype: object, triangle ({-1, -1}: no candidate at this rank)
+
+
+def _box_arrays(lo, hi):
+    lo = np.ascontiguousarray(lo, dtype=np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, dtype=np.float32).reshape(-1, 3)
+    if lo.shape != hi.shape:
+        raise ValueError("lo and hi must hold n x 3 floats each")
+    return lo, hi
+
+
+def overlap_boxes(scene, lo, hi, k=0):
+    """Which surfaces touch every axis-aligned, closed box (rt_overlap_boxes): lo, hi [n, 3] float32; k from 0 to OVERLAP_MAX.  Returns
+    (counts, ids): counts [n] int32, the number of ALL surfaces - spheres and triangle records - that overlap the box, and ids [n, k]
+    records of OverlapId, the k of them lowest in (object, triangle) order, {-1, -1} behind a box's last.  A box with a component that is
+    not finite or with lo > hi on an axis overlaps nothing.  A sphere is a surface: a box wholly inside it does not touch it."""
+    ctx = scene.ctx
+    lo, hi = _box_arrays(lo, hi)
+    n, k = lo.shape[0], int(k)
+    if not 0 <= k <= OVERLAP_MAX:
+        raise ValueError("k must be 0 .. %d" % OVERLAP_MAX)
+    ids = np.zeros((n, k), OVERLAP_ID_DTYPE)
+    counts = np.zeros(n, np.int32)
+    ctx._check(lib().rt_overlap_boxes(ctx._h, scene._h, _fp(lo)[1], _fp(hi)[1], n, k, C.c_void_p(ids.ctypes.data) if ids.size else None,
+                                      counts.ctypes.data_as(C.POINTER(C.c_int32)), None))
+    return counts, ids
+
+
+def boxes_touch(scene, lo, hi):
+    """Whether any surface touches every box (rt_overlap_boxes in any-only mode: a box stops at its first overlapping surface): n bool."""
+    ctx = scene.ctx
+    lo, hi = _box_arrays(lo, hi)
+    flags = np.zeros(lo.shape[0], np.uint8)
+    ctx._check(lib().rt_overlap_boxes(ctx._h, scene._h, _fp(lo)[1], _fp(hi)[1], lo.shape[0], 0, None, None, C.c_void_p(flags.ctypes.data)))
+    return flags.astype(bool)
+
+
+def overlap_boxes_device(scene, lo, hi, k=0, ids=None, counts=None, any=None, n=None, stream=None):
+    """Device-buffer form (rt_overlap_boxes_device), asynchronous on `stream` (a hipStream_t as an int; None: the default stream) and in
+    the context's launch order.  lo, hi are float32 torch tensors of 3 n elements on the scene's GPU; ids None or a uint8 tensor of
+    n * k * 8 bytes, counts None or an int32 tensor of n, any None or a uint8 tensor of n - or all are device pointers as ints (outputs
+    may be None where the entry point allows it) together with n.  With tensors returns (counts, ids, any): new counts where none of the
+    three was passed, and new ids [n, k, 8] for k > 0 where none were (`.cpu().numpy().view(OverlapId)[..., 0]` reads them); with k == 0, no counts and
+    `any` given the query runs in any-only mode."""
+    ctx = scene.ctx
+    k = int(k)
+    if isinstance(lo, int):
+        if n is None:
+            raise ValueError("device pointers need n, the number of boxes")
+        ctx._check(lib().rt_overlap_boxes_device(ctx._h, scene._h, _dptr(lo), _dptr(hi), int(n), k, _dptr(ids), _dptr(counts), _dptr(any), _dptr(stream)))
+        return counts, ids, any
+    import torch
+    lo_ptr, count = _device_floats(lo, 3, "lo")
+    hi_ptr, n_hi = _device_floats(hi, 3, "hi")
+    if n_hi != count or (n is not None and int(n) != count):
+        raise ValueError("lo, hi and n differ")
+    if not 0 <= k <= OVERLAP_MAX:
+        raise ValueError("k must be 0 .. %d" % OVERLAP_MAX)
+    none_given = ids is None and counts is None and any is None
+    if k == 0:
+        ids = None
+    elif ids is None:
+        ids = torch.empty((count, k, OVERLAP_ID_DTYPE.itemsize), dtype=torch.uint8, device=lo.device)
+    elif str(ids.dtype) != "torch.uint8" or not ids.is_contiguous() or not ids.is_cuda or ids.numel() != count * k * OVERLAP_ID_DTYPE.itemsize:
+        raise ValueError("ids must be a contiguous uint8 tensor on the GPU of 8 bytes per id")
+    if none_given or (counts is None and any is None and k == 0):
+        counts = torch.empty((count,), dtype=torch.int32, device=lo.device)
+    if counts is not None and (str(counts.dtype) != "torch.int32" or not counts.is_contiguous() or not counts.is_cuda or counts.numel() != count):
+        raise ValueError("counts must be a contiguous int32 tensor on the GPU, one per box")
+    if any is not None and (str(any.dtype) != "torch.uint8" or not any.is_contiguous() or not any.is_cuda or any.numel() != count):
+        raise ValueError("any must be a contiguous uint8 tensor on the GPU, one per box")
+    ctx._check(lib().rt_overlap_boxes_device(ctx._h, scene._h, _dptr(lo_ptr), _dptr(hi_ptr), count, k, _dptr(ids.data_ptr() if ids is not None else None),
+                                             _dptr(counts.data_ptr() if counts is not None else None), _dptr(any.data_ptr() if any is not None else None), _dptr(stream)))
+    return counts, ids, any
+
+
+def voxel_boxes(lo, hi, shape):
+    """The cells of voxelize as boxes: shape = (nx, ny, nz) cells between corner lo and corner hi, cell i of an axis from edge i to edge
+    i + 1 of its nx + 1 edges (lo + (hi - lo) * i / nx in binary64, rounded to float32 once; the last edge is hi), so that neighbours
+    share a face exactly.  Returns (cell_lo, cell_hi, centre): float32 arrays [nx * ny * nz, 3], x slowest as in distance_grid; a centre
+    is (lo + hi) * 0.5 per component."""
+    edges = []
+    for a in range(3):
+        m = int(shape[a])
+        if m < 1:
+            raise ValueError("shape must be at least 1 along every axis")
+        e = (float(lo[a]) + (float(hi[a]) - float(lo[a])) * np.arange(m + 1, dtype=np.float64) / m).astype(np.float32)
+        e[m] = np.float32(hi[a])
+        edges.append(e)
+    cell_lo = np.stack(np.meshgrid(*[e[:-1] for e in edges], indexing="ij"), axis=-1).reshape(-1, 3)
+    cell_hi = np.stack(np.meshgrid(*[e[1:] for e in edges], indexing="ij"), axis=-1).reshape(-1, 3)
+    centre = (cell_lo + cell_hi) * np.float32(0.5)
+    return np.ascontiguousarray(cell_lo), np.ascontiguousarray(cell_hi), np.ascontiguousarray(centre)
+
+
+def voxelize(scene, lo, hi, shape, solid=False, beta=None):
+    """The scene as voxels: shape = (nx, ny, nz) cells between corner lo and corner hi (voxel_boxes; distance_grid's axis order, x
+    slowest).  A cell is set where a surface touches its closed box (overlap_boxes_device in any-only mode) and, with solid=True, also
+    where its centre lies inside (contains_points' rule, |w| >= 0.5 over the spheres, cuboids and meshes; beta None: the exact winding
+    numbers, a number: the fast ones with that beta).  The cell boxes are built with NumPy on the host (voxel_boxes) and uploaded, which
+    is most of the call's time on a large grid; the queries run on the context's GPU, queued behind the upload on torch's current stream.
+    The cells are CELLS between nx + 1 edges per axis, not distance_grid's lattice of points that includes both corners: only the axis
+    order is shared.  Returns a bool tensor [nx, ny, nz]."""
+    import torch
+    ctx = scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    cell_lo, cell_hi, centre = voxel_boxes(lo, hi, shape)
+    stream = torch.cuda.current_stream(dev).cuda_stream      # the boxes are produced on it: the queries are queued behind
+    d_lo, d_hi = torch.from_numpy(cell_lo).to(dev), torch.from_numpy(cell_hi).to(dev)
+    flags = torch.empty((cell_lo.shape[0],), dtype=torch.uint8, device=dev)
+    overlap_boxes_device(scene, d_lo, d_hi, 0, any=flags, stream=stream)
+    cells = flags != 0
+    if solid:
+        inside = torch.empty_like(flags)
+        _winding_device(ctx, scene, torch.from_numpy(centre).to(dev), WINDING_SOLIDS, None if beta is None else float(beta), None, inside, None, stream)
+        cells = cells | (inside != 0)
+    return cells.reshape(int(shape[0]), int(shape[1]), int(shape[2]))
