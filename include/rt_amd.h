@@ -857,6 +857,70 @@ rt_status rt_overlap_boxes_device(rt_ctx *ctx, const rt_scene *scene, const floa
 rt_status rt_overlap_boxes(rt_ctx *ctx, const rt_scene *scene, const float *lo, const float *hi, int64_t n, int32_t k, rt_overlap_id *ids,
                            int32_t *counts, uint8_t *any);
 
+/* ---- triangle-overlap queries: which surfaces a triangle cuts, and where ---------------------------
+ * The NARROW phase behind the box query's broad phase: "does this part cut the scene, which triangles, and along which curve?" - a
+ * mesh-scene collision test, the intersection curve of two surfaces (the CSG preview of the winding section), a cross-section (tile the
+ * cutting plane into triangles).  The query is a triangle (a0, a1, a2), n x 9 floats as given.
+ *
+ * The answer is DEFINED to the bit, like its neighbours: binary32, every operation rounded once, nothing fused, in the order written
+ * here, so tests/tritri_ref.py (NumPy float32, every candidate of every query, no traversal) gives the same bytes.  dot(a, b) =
+ * (a.x*b.x + a.y*b.y) + a.z*b.z; cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).
+ *
+ * Validity: all nine floats finite.  A query that is not valid overlaps nothing.  A zero-area query is tested as it stands.
+ * Of the query: lo.a = min(min(a0.a, a1.a), a2.a), hi.a likewise with max; z = a0 - a0 (the zero vector), e1 = a1 - a0, e2 = a2 - a0,
+ * na = cross(e1, e2).
+ * Candidates: the box section's - every sphere, as a SURFACE, and every triangle record (p0, s1, s2): q0 = p0, q1 = p0 + s1, q2 = p0 + s2.
+ *   triangle record, in this order (nb = cross(s1, s2); d_j = q_j - a0):
+ *     1. the query's bounding box: no overlap when on some axis all three q_j.a > hi.a or all three q_j.a < lo.a (compares alone).
+ *     2. hA_i = dot(nb, a_i - q0): no overlap when all three are > 0 or all three are < 0.  Zero counts as touching.
+ *     3. hB_j = dot(na, d_j): likewise.
+ *     4. if hA_0 == hA_1 == hA_2 == 0 or hB_0 == hB_1 == hB_2 == 0 the pair is COPLANAR (or a normal vanished) and is decided by six
+ *        in-plane axes: X = cross(na, f) for f in e1, a2 - a1, a0 - a2, then X = cross(nb, g) for g in s1, s2 - s1, -s2.  On an axis
+ *        the query projects to u = dot(X, z), dot(X, e1), dot(X, e2) and the record to w_j = dot(X, d_j); the axis separates when all nine
+ *        u_i < w_j hold or all nine u_i > w_j hold.  The pair overlaps when no axis separates: a vanished normal gives axes that
+ *        separate nothing and is reported conservatively.  Such a pair has no segment (kind 2).
+ *     5. otherwise Moeller's interval test (1997) on D = cross(na, nb): pA = dot(D, z), dot(D, e1), dot(D, e2); pB_j = dot(D, d_j).
+ *        A triangle's LONE vertex l from its heights (h0, h1, h2), Moeller's sign rule: h0*h1 > 0: l = 2; else h0*h2 > 0: l = 1; else
+ *        h1*h2 > 0 or h0 != 0: l = 0; else h1 != 0: l = 1; else l = 2.  The other two, o and o', in index order.  Its interval's two ends,
+ *        end 1 towards o and end 2 towards o': x = p_l + (p_o - p_l) * (h_l / (h_l - h_o)) - one IEEE division, then the product, then
+ *        the sum; x = p_l when h_l - h_o == 0.  No overlap when all four xA < xB hold (xA_1 < xB_1, xA_1 < xB_2, xA_2 < xB_1,
+ *        xA_2 < xB_2: the query's maximum below the record's minimum), or all four xB < xA.  A compare with a NaN does not hold: an
+ *        overflowed product leaves the pair reported, which is conservative.
+ *   The verdicts of steps 1 to 3 have no side effects: an implementation may leave at the first that separates.
+ *   a mesh's triangle, additionally: the box section's path rule, with (lo, hi) the query's bounding box.
+ *   sphere (c, R): near2 = the nearest section's point-triangle dist2 of the point c and the record (a0, e1, e2); far2 =
+ *     max(max(dot(v0, v0), dot(v1, v1)), dot(v2, v2)) with v_i = a_i - c; rr = R*R.  Overlaps when near2 <= rr and far2 >= rr: a triangle
+ *     wholly inside the ball touches no surface.
+ * The SEGMENT of an overlapping pair of step 5 (kind 1) is the overlap of its two intervals.  An interval's minimum is its end 1 where
+ * x_1 <= x_2, else its end 2; the maximum is the other.  p belongs to the record where minB > minA, else to the query (a tie goes to the
+ * query); q to the record where maxB < maxA, else to the query.  The point of an end is its edge crossing: per component
+ * v_l + (v_o - v_l) * (h_l / (h_l - h_o)), the same quotient as the end's, v_l where the denominator is zero; v are a0..a2 of the
+ * query, q0..q2 of the record.  A point contact has p == q.
+ * What the test is not: exact near touching, or for nearly coplanar pairs - the rounded heights and interval ends may fall either way
+ * within a band of the scene's scale (tests/golden/tritri_meta.json has the measured share against exact rational arithmetic) - and not
+ * a self-intersection test: asked with a mesh's own triangles, every neighbour that shares a vertex touches by definition and crowds out
+ * the eight ids.
+ * Output, for query i: d_counts, d_any and d_ids exactly as in the box section, ANY-ONLY mode included.  d_segments[i*k + rank]
+ * (needs k > 0 and d_ids) is the segment of the pair in d_ids[i*k + rank]. */
+typedef struct rt_tri_segment {
+    float p[3];            /* the segment's ends (kind 1); zeros in an empty slot; NaNs (0x7fc00000) for kind 2 */
+    float q[3];
+    int32_t kind;          /* 0: an empty slot; 1: a segment from p to q; 2: a pair that has no segment - a sphere, or a coplanar pair */
+    int32_t reserved;      /* 0 */
+} rt_tri_segment;          /* 32 bytes */
+/* Device-buffer form: d_tris (n x 9 floats), d_ids (n * k records, [query][rank], 8-byte aligned), d_counts (n int32), d_any (n bytes)
+ * and d_segments (n * k records, 16-byte aligned) are device memory of ctx's GPU; asynchronous on hip_stream and ordered like
+ * rt_trace_rays_device.  n == 0 succeeds and touches nothing.  RT_ERR_INVALID, leaving the launch order as it was: n < 0 or n > 2^30;
+ * k < 0 or k > RT_OVERLAP_MAX; a null d_tris with n > 0; d_ids null or misaligned while k > 0; d_ids, d_counts and d_any all null;
+ * d_segments given with k == 0, or misaligned; a scene of another context; a scene of more than 4,096 objects.  rt_last_kernel_ms then
+ * reports the triangle-overlap kernel.  A scene updated by rt_scene_update_mesh[_device] answers for its new geometry. */
+rt_status rt_overlap_triangles_device(rt_ctx *ctx, const rt_scene *scene, const float *d_tris, int64_t n, int32_t k, rt_overlap_id *d_ids,
+                                      int32_t *d_counts, uint8_t *d_any, rt_tri_segment *d_segments, void *hip_stream);
+/* Host-buffer form: uploads the triangles, answers, downloads each output whose pointer is not NULL and returns when they are in host
+ * memory (the context keeps the device buffers). */
+rt_status rt_overlap_triangles(rt_ctx *ctx, const rt_scene *scene, const float *tris, int64_t n, int32_t k, rt_overlap_id *ids,
+                               int32_t *counts, uint8_t *any, rt_tri_segment *segments);
+
 /* ---- occlusion (any-hit) ray queries and the light-visibility plane ------------------------------
  * "Is anything in the way?": line of sight, shadow masks, reachability probes.  For a ray (o, d) taken as given and a limit tmax,
  *     occluded(o, d, tmax) := get_ray_collision (src/raytracer.cu:24-46; what rt_trace_rays answers) finds a hit AND its t <= tmax.

@@ -102,6 +102,9 @@ WINDING_BETA_DEFAULT, WINDING_LEAF_TRIS = 2.0, 8   # RT_WINDING_BETA_DEFAULT, RT
 # rt_overlap_id (include/rt_amd.h) as a NumPy record: what overlap_boxes returns per rank.  An empty slot: {-1, -1}
 OVERLAP_ID_DTYPE = np.dtype([("object", np.int32), ("triangle", np.int32)])
 OVERLAP_MAX = 8                                   # RT_OVERLAP_MAX: the most ids per box of overlap_boxes
+# rt_tri_segment (include/rt_amd.h) as a NumPy record: what overlap_triangles returns per rank with segments=True.  kind 0: an empty slot;
+# 1: a segment from p to q; 2: a pair that has no segment (a sphere, a coplanar pair), its floats NaN
+TRI_SEGMENT_DTYPE = np.dtype([("p", np.float32, (3,)), ("q", np.float32, (3,)), ("kind", np.int32), ("reserved", np.int32)])
 MULTIHIT_MAX = 8                                  # RT_MULTIHIT_MAX: the most records per ray of trace_rays_multi
 AOV_PLANES = ("depth", "normal", "albedo", "object", "ray")
 VIS_BLOCKED, VIS_LIT, VIS_NO_SURFACE = 0, 1, 2      # RT_VIS_*: the bytes of render_visibility's plane
@@ -206,6 +209,8 @@ ABI = {
     "rt_sweep_spheres": (st, [vp, vp, fp, fp, fp, fp, i64, vp]),
     "rt_overlap_boxes_device": (st, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
     "rt_overlap_boxes": (st, [vp, vp, fp, fp, i64, i32, vp, i32p, vp]),
+    "rt_overlap_triangles_device": (st, [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "rt_overlap_triangles": (st, [vp, vp, fp, i64, i32, vp, i32p, vp, vp]),
     "rt_occluded_rays_device": (st, [vp, vp, vp, vp, vp, i64, vp, vp]),
     "rt_occluded_rays": (st, [vp, vp, fp, fp, fp, i64, vp]),
     "rt_render_visibility_device": (st, [vp, vp, cam, fp, f32, vp, vp]),

@@ -12,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libraytracer_amd.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_nearest_capi.cpp", "rt_sweep_capi.cpp", "rt_multihit_capi.cpp", "rt_overlap_capi.cpp", "rt_winding_capi.cpp", "rt_denoise_capi.cpp", "rt_adaptive_capi.cpp", "rt_views_capi.cpp", "rt_sky_capi.cpp", "rt_update_capi.cpp", "rt_host.cpp")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("rt_kernel.hip", "rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_multi_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_nearest_capi.cpp", "rt_sweep_capi.cpp", "rt_multihit_capi.cpp", "rt_overlap_capi.cpp", "rt_tritri_capi.cpp", "rt_winding_capi.cpp", "rt_denoise_capi.cpp", "rt_adaptive_capi.cpp", "rt_views_capi.cpp", "rt_sky_capi.cpp", "rt_update_capi.cpp", "rt_host.cpp")]
 # every header there is: a new one cannot be forgotten, and needs_build() then serves no stale library after an edit
 HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "rt_amd.h")]
 # text a header includes more than once (the wave loop both render kernels run): watched like the headers
@@ -66,6 +66,7 @@ XRAY_EXAMPLE = os.path.join(HERE, "host", "example_xray")
 SDF_EXAMPLE = os.path.join(HERE, "host", "example_sdf")
 SWEEP_EXAMPLE = os.path.join(HERE, "host", "example_sweep")
 VOXELIZE_EXAMPLE = os.path.join(HERE, "host", "example_voxelize")
+SLICE_EXAMPLE = os.path.join(HERE, "host", "example_slice")
 
 
 def _build_host_program(source, exe):
@@ -134,6 +135,11 @@ def build_sweep_example():
 def build_voxelize_example():
     """The mirror's box-overlap queries (host/example_voxelize.cpp): the monkey voxelised, one slice as a PGM, the surface and solid cells counted."""
     return _build_host_program("example_voxelize.cpp", VOXELIZE_EXAMPLE)
+
+
+def build_slice_example():
+    """The mirror's triangle-overlap queries (host/example_slice.cpp): a cross-section of the monkey, its outline rasterised from the segments into a PGM."""
+    return _build_host_program("example_slice.cpp", SLICE_EXAMPLE)
 
 
 if __name__ == "__main__":

@@ -495,19 +495,19 @@ Args ray_args_view(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *ca
 }
 
 /* A ray kernel of the scene's shape queued on `stream` behind the clearing of its ticket counter (`launcher`: rt_launch_query, rt_launch_occlusion,
- * rt_launch_ao, rt_launch_nearest or rt_launch_multihit, with its `front`).  Without the bracket: for the work of a caller that is inside one. */
+ * rt_launch_ao, rt_launch_nearest or rt_launch_multihit, with its `front`: 0, 1 or, where the family has a third, 2).  Without the bracket: for the work of a caller that is inside one. */
 template <class Args>
-rt_status enqueue_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), bool front,
+rt_status enqueue_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), int front,
                        const char *what_clear, const char *what, hipStream_t stream)
 {
     RT_HIP(ctx, hipMemsetAsync(a.counter, 0, 512, stream), what_clear);
-    RT_HIP(ctx, launcher(&a, scene->kernel.shape, front ? 1 : 0, ctx->num_cus, scene->kernel.lds_bytes, stream), what);
+    RT_HIP(ctx, launcher(&a, scene->kernel.shape, front, ctx->num_cus, scene->kernel.lds_bytes, stream), what);
     return RT_OK;
 }
 
 /* One launch of a ray kernel in the launch bracket: the ticket counter is shared with the render launches. */
 template <class Args>
-rt_status launch_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), bool front,
+rt_status launch_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), int front,
                       const char *what, hipStream_t stream)
 {
     return launch_bracket(ctx, stream, [&]() -> rt_status { return enqueue_rays(ctx, scene, a, launcher, front, "clearing the ray counter", what, stream); });

@@ -54,7 +54,8 @@ hipError_t rt_launch_query(const rt_query_args *args, rt_shape shape, int aov, i
 hipError_t rt_launch_occlusion(const rt_occlusion_args *args, rt_shape shape, int vis, int num_cus, size_t lds_bytes, hipStream_t stream);
 hipError_t rt_launch_ao(const rt_ao_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
 /* rt_multihit_kernel.h, with them: the signature is the ray kernels' (rt_internal.h's enqueue_rays calls it); front 0: the multi-hit kernel,
- * front 1: the box-overlap kernel (rt_overlap_kernel.h), which reads the block's ov_ fields */
+ * front 1: the box-overlap kernel (rt_overlap_kernel.h), which reads the block's ov_ fields, front 2: the triangle-overlap kernel
+ * (rt_tritri_kernel.h), which reads its ot_ fields */
 hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
 /* ... and its second pass over the records: the texture coordinates of those on a sphere whose material needs them */
 hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *args, int num_cus, hipStream_t stream);

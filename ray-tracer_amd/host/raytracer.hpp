@@ -632,6 +632,37 @@ public:
         check(rt_overlap_boxes(ctx_, scene_, lo.data(), hi.data(), (int64_t)any.size(), 0, nullptr, nullptr, any.data()));
         return any;
     }
+    /* Which surfaces every query triangle cuts (rt_overlap_triangles): triangles holds n x 9 floats, the vertices a0, a1, a2; k from 0 to
+     * RT_OVERLAP_MAX.  counts and ids as in overlap_boxes; with `segments` (needs k > 0) segments holds n * k records beside the ids: kind 1
+     * a segment from p to q that the pair shares, kind 2 a sphere or a coplanar pair (no segment), kind 0 an empty slot.  A triangle that
+     * is not finite overlaps nothing. */
+    struct TriangleOverlaps {
+        std::vector<int32_t> counts;
+        std::vector<rt_overlap_id> ids;
+        std::vector<rt_tri_segment> segments;
+    };
+    TriangleOverlaps overlap_triangles(const std::vector<float> &triangles, int k = 0, bool segments = false)
+    {
+        if (triangles.size() % 9 != 0) throw std::invalid_argument("triangles must hold n x 9 floats");
+        if (k < 0 || k > RT_OVERLAP_MAX) throw std::invalid_argument("k must be 0 .. RT_OVERLAP_MAX");
+        if (segments && k == 0) throw std::invalid_argument("segments need k > 0");
+        const size_t n = triangles.size() / 9;
+        TriangleOverlaps out;
+        out.counts.resize(n);
+        out.ids.resize(n * (size_t)k);
+        if (segments) out.segments.resize(n * (size_t)k);
+        check(rt_overlap_triangles(ctx_, scene_, triangles.data(), (int64_t)n, k, k > 0 ? out.ids.data() : nullptr, out.counts.data(), nullptr,
+                                   segments ? out.segments.data() : nullptr));
+        return out;
+    }
+    /* Whether the triangle (a0, a1, a2) cuts any surface (rt_overlap_triangles in any-only mode) */
+    bool touches(Vec3 a0, Vec3 a1, Vec3 a2)
+    {
+        const float t[9] = {a0.x, a0.y, a0.z, a1.x, a1.y, a1.z, a2.x, a2.y, a2.z};
+        uint8_t any = 0;
+        check(rt_overlap_triangles(ctx_, scene_, t, 1, 0, nullptr, nullptr, &any, nullptr));
+        return any != 0;
+    }
     /* The first-hit planes of a view (rt_render_aov), all five of them: depth W*H, normal / albedo / ray W*H*3, object W*H */
     struct Aov {
         std::vector<float> depth, normal, albedo, ray;

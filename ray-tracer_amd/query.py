@@ -1,12 +1,13 @@
 """Queries: closest hits and first-hit planes, multi-hit queries (the first k hits of a ray, hit counts), occlusion (any-hit), the
 light-visibility plane, the ambient-occlusion plane, the nearest-surface queries (closest point and distance, which are no ray questions), and
 the winding-number queries (point containment, the signed distance), the sphere-cast queries (where a moving ball first touches the scene), and
-the box-overlap queries (which surfaces touch a box; a voxeliser)."""
+the box-overlap queries (which surfaces touch a box; a voxeliser), and the triangle-overlap queries (which surfaces a triangle cuts, and
+along which segment; a mesh-scene collision test)."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, OVERLAP_ID_DTYPE, OVERLAP_MAX, SWEEP_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
+from ._abi import AO_PLANES, AOV_PLANES, HIT_DTYPE, MULTIHIT_MAX, NEAREST_DTYPE, OVERLAP_ID_DTYPE, OVERLAP_MAX, SWEEP_DTYPE, TRI_SEGMENT_DTYPE, WINDING_BETA_DEFAULT, WINDING_SOLIDS, _dptr, _fp, _ray_arrays, lib
 
 
 def trace_rays(ctx, scene, origins, directions):
@@ -634,3 +635,108 @@ def voxelize(scene, lo, hi, shape, solid=False, beta=None):
         _winding_device(ctx, scene, torch.from_numpy(centre).to(dev), WINDING_SOLIDS, None if beta is None else float(beta), None, inside, None, stream)
         cells = cells | (inside != 0)
     return cells.reshape(int(shape[0]), int(shape[1]), int(shape[2]))
+
+
+TriSegment = TRI_SEGMENT_DTYPE      # rt_tri_segment as a structured dtype: p[3], q[3], kind (0 empty, 1 a segment, 2 a pair without one), reserved
+
+
+def _tri_array(triangles):
+    t = np.ascontiguousarray(triangles, dtype=np.float32)
+    if t.size % 9:
+        raise ValueError("triangles must hold n x 9 floats: a0, a1, a2")
+    return t.reshape(-1, 9)
+
+
+def overlap_triangles(scene, triangles, k=0, segments=False):
+    """Which surfaces every query triangle cuts (rt_overlap_triangles): triangles [n, 3, 3] or [n, 9] float32, the vertices a0, a1, a2;
+    k from 0 to OVERLAP_MAX.  Returns (counts, ids), and with segments=True (counts, ids, segs): counts [n] int32, the number of ALL
+    surfaces - spheres and triangle records - that overlap the triangle; ids [n, k] records of OverlapId, the k of them lowest in
+    (object, triangle) order, {-1, -1} behind a query's last; segs [n, k] records of TriSegment, the segment each pair of ids shares
+    (kind 1), kind 2 for a sphere or a coplanar pair, kind 0 in an empty slot.  A triangle with a component that is not finite overlaps
+    nothing.  segments=True needs k > 0."""
+    ctx = scene.ctx
+    t = _tri_array(triangles)
+    n, k = t.shape[0], int(k)
+    if not 0 <= k <= OVERLAP_MAX:
+        raise ValueError("k must be 0 .. %d" % OVERLAP_MAX)
+    if segments and k == 0:
+        raise ValueError("segments need k > 0")
+    ids = np.zeros((n, k), OVERLAP_ID_DTYPE)
+    counts = np.zeros(n, np.int32)
+    segs = np.zeros((n, k), TRI_SEGMENT_DTYPE) if segments else None
+    ctx._check(lib().rt_overlap_triangles(ctx._h, scene._h, _fp(t)[1], n, k, C.c_void_p(ids.ctypes.data) if ids.size else None,
+                                          counts.ctypes.data_as(C.POINTER(C.c_int32)), None,
+                                          C.c_void_p(segs.ctypes.data) if segments and segs.size else None))
+    return (counts, ids, segs) if segments else (counts, ids)
+
+
+def triangles_touch(scene, triangles):
+    """Whether every query triangle cuts any surface (rt_overlap_triangles in any-only mode: a query stops at its first): n bool."""
+    ctx = scene.ctx
+    t = _tri_array(triangles)
+    flags = np.zeros(t.shape[0], np.uint8)
+    ctx._check(lib().rt_overlap_triangles(ctx._h, scene._h, _fp(t)[1], t.shape[0], 0, None, None, C.c_void_p(flags.ctypes.data), None))
+    return flags.astype(bool)
+
+
+def overlap_triangles_device(scene, triangles, k=0, ids=None, counts=None, any=None, segments=None, n=None, stream=None):
+    """Device-buffer form (rt_overlap_triangles_device), asynchronous on `stream` (a hipStream_t as an int; None: the default stream) and
+    in the context's launch order.  triangles is a float32 torch tensor of 9 n elements on the scene's GPU; ids None or a uint8 tensor of
+    n * k * 8 bytes, counts None or an int32 tensor of n, any None or a uint8 tensor of n, segments None, True (a new tensor) or a uint8
+    tensor of n * k * 32 bytes - or all are device pointers as ints (outputs may be None where the entry point allows it) together with
+    n.  With tensors returns (counts, ids, any, segments): new counts where none of ids, counts and any was passed, new ids [n, k, 8] for
+    k > 0 where none were, new segments [n, k, 32] for segments=True (`.cpu().numpy().view(TriSegment)[..., 0]` reads them); with k == 0,
+    no counts and `any` given the query runs in any-only mode."""
+    ctx = scene.ctx
+    k = int(k)
+    if isinstance(triangles, int):
+        if n is None:
+            raise ValueError("device pointers need n, the number of triangles")
+        ctx._check(lib().rt_overlap_triangles_device(ctx._h, scene._h, _dptr(triangles), int(n), k, _dptr(ids), _dptr(counts), _dptr(any), _dptr(segments), _dptr(stream)))
+        return counts, ids, any, segments
+    import torch
+    t_ptr, count = _device_floats(triangles, 9, "triangles")
+    if n is not None and int(n) != count:
+        raise ValueError("triangles and n differ")
+    if not 0 <= k <= OVERLAP_MAX:
+        raise ValueError("k must be 0 .. %d" % OVERLAP_MAX)
+    none_given = ids is None and counts is None and any is None
+    if k == 0:
+        ids = None
+    elif ids is None:
+        ids = torch.empty((count, k, OVERLAP_ID_DTYPE.itemsize), dtype=torch.uint8, device=triangles.device)
+    elif str(ids.dtype) != "torch.uint8" or not ids.is_contiguous() or not ids.is_cuda or ids.numel() != count * k * OVERLAP_ID_DTYPE.itemsize:
+        raise ValueError("ids must be a contiguous uint8 tensor on the GPU of 8 bytes per id")
+    if segments is False:
+        segments = None
+    if segments is not None and k == 0:
+        raise ValueError("segments need k > 0")
+    if segments is True:
+        segments = torch.empty((count, k, TRI_SEGMENT_DTYPE.itemsize), dtype=torch.uint8, device=triangles.device)
+    elif segments is not None and (str(segments.dtype) != "torch.uint8" or not segments.is_contiguous() or not segments.is_cuda
+                                   or segments.numel() != count * k * TRI_SEGMENT_DTYPE.itemsize):
+        raise ValueError("segments must be a contiguous uint8 tensor on the GPU of 32 bytes per segment")
+    if none_given or (counts is None and any is None and k == 0):
+        counts = torch.empty((count,), dtype=torch.int32, device=triangles.device)
+    if counts is not None and (str(counts.dtype) != "torch.int32" or not counts.is_contiguous() or not counts.is_cuda or counts.numel() != count):
+        raise ValueError("counts must be a contiguous int32 tensor on the GPU, one per triangle")
+    if any is not None and (str(any.dtype) != "torch.uint8" or not any.is_contiguous() or not any.is_cuda or any.numel() != count):
+        raise ValueError("any must be a contiguous uint8 tensor on the GPU, one per triangle")
+    ptr = lambda x: _dptr(x.data_ptr() if x is not None else None)
+    ctx._check(lib().rt_overlap_triangles_device(ctx._h, scene._h, _dptr(t_ptr), count, k, ptr(ids), ptr(counts), ptr(any), ptr(segments), _dptr(stream)))
+    return counts, ids, any, segments
+
+
+def collide_mesh(scene, triangles, k=OVERLAP_MAX):
+    """A mesh against the scene: every triangle of `triangles` [n, 3, 3] asked with k ids and segments (overlap_triangles), the pairs
+    returned as flat arrays.  Returns a dict: query [m] (the index into `triangles`), object [m], triangle [m] (-1: a sphere), p [m, 3],
+    q [m, 3], kind [m] (1: a segment from p to q - together the intersection curve; 2: a sphere or a coplanar pair, p and q NaN), counts
+    [n] and truncated [n] bool, true where a triangle cuts more than k surfaces and the pairs hold only its k lowest."""
+    k = int(k)
+    if not 1 <= k <= OVERLAP_MAX:
+        raise ValueError("k must be 1 .. %d" % OVERLAP_MAX)
+    counts, ids, segs = overlap_triangles(scene, triangles, k, segments=True)
+    held = ids["object"] >= 0
+    query = np.broadcast_to(np.arange(ids.shape[0], dtype=np.int64)[:, None], ids.shape)[held]
+    return {"query": query, "object": ids["object"][held], "triangle": ids["triangle"][held], "p": segs["p"][held], "q": segs["q"][held],
+            "kind": segs["kind"][held], "counts": counts, "truncated": counts > k}
