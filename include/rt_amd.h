@@ -1223,6 +1223,16 @@ rt_status rt_debug_primary_cull(rt_ctx *ctx, uint32_t *words, int32_t capacity_w
  * root box, those of them that are flagged, nodes the centre direction visits in the flagged ones, ... in all root-entering pixels, flagged
  * pixels in all, words of the plane} */
 rt_status rt_debug_primary_cull_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats6);
+/* The subtree cull (rt_cull.h): behind its bit each pixel of the view has a 32-bit word, bit g set iff gate g of the scene's one mesh - the g-th
+ * non-root reference of its tree in breadth-first order, g = 1..31 - leads the pixel's primary rays to no leaf; the kernel above does not enter such a
+ * reference with a primary ray.  RT_AMD_SUBTREE_CULL=0 (read by rt_ctx_create) writes every word as 0.  Frames are bit-identical either way.
+ * rt_debug_subtree_cull: the words the context's last render launch was handed, read back (waits for the device).  info4 as above, its fourth
+ * entry the word count width * height: pixel py * width + px is word py * width + px. */
+rt_status rt_debug_subtree_cull(rt_ctx *ctx, uint32_t *words, int32_t capacity_words, int32_t *info4);
+/* the same words computed on the HOST (no device is touched) from a flattened scene.  words: width * height of them, or NULL.  stats4, or NULL, over
+ * the unflagged pixels whose jitter cone may enter the root box, their centre ray walked in the kernel's order: {those pixels, its node steps
+ * ungated, its node steps with the pixel's word, pixels whose word is not 0} */
+rt_status rt_debug_subtree_cull_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats4);
 /* evaluates one function of the shared math / RNG headers ON THE DEVICE, element-wise, on raw
  * 32-bit patterns (host pointers).  op: 0 rt_logf, 1 rt_cosf, 2 rt_sinf, 3 rt_asinf, 4 rt_acosf,
  * 5 rt_u01, 6 rt_jitter, 7 rt_theta (5-7 take the uint32 hash output), 8 sqrtf, 9 1.0f/x,

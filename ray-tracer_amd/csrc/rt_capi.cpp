@@ -167,6 +167,7 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     k.descend_keep_given = env_int("RT_AMD_DESCEND_KEEP", 0, 64, -1) >= 0;      /* (an explicit value replaces the per-shape default: rt_sched::render_descend_keep) */
     ctx->multi.careful = env_int("RT_AMD_MULTI_CAREFUL", INT_MIN, INT_MAX, 0) != 0;
     ctx->cull.enabled = env_int("RT_AMD_PRIMARY_CULL", 0, 1, 1) != 0;
+    ctx->cull.gates = env_int("RT_AMD_SUBTREE_CULL", 0, 1, 1) != 0;
     if (ctx->tile_counter.grow(256) != hipSuccess ||
         hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
         delete ctx;
@@ -685,7 +686,7 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
     k.width = cam->width; k.height = cam->height; k.antialias = rs->antialias ? 1 : 0;
     const rt_cull_host::Step step = cp.plan.next(k, enabled, [&](size_t words) {
         /* (the old plane is freed first, which waits for the launches that read it) */
-        const bool ok = cp.d.grow(words) == hipSuccess;
+        const bool ok = cp.d.grow(rt_cull_alloc_words(words)) == hipSuccess;     /* the bits and, behind them, the gate words */
         if (!ok) (void)hipGetLastError();
         return ok;
     });
@@ -698,7 +699,7 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
             for (FrameSlot &fs : ctx->pipe.slots)
                 if (fs.used && &fs != slot) ok = ok && hipEventSynchronize(fs.ev_done) == hipSuccess;
         if (ok && !cp.ev.e) ok = hipEventCreateWithFlags(&cp.ev.e, hipEventDisableTiming) == hipSuccess;
-        ok = ok && rt_launch_cull(k.cam, k.width, k.height, k.antialias, scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
+        ok = ok && rt_launch_cull(k.cam, k.width, k.height, (k.antialias ? RT_CULL_ANTIALIAS : 0) | (cp.gates ? RT_CULL_WITH_GATES : 0), scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
                                   scene->flat.num_meshes, cp.d.p, stream) == hipSuccess;
         ok = ok && hipEventRecord(cp.ev, stream) == hipSuccess;
         cp.stream = stream;
@@ -893,6 +894,58 @@ extern "C" rt_status rt_debug_primary_cull(rt_ctx *ctx, uint32_t *words, int32_t
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
     RT_HIP(ctx, hipMemcpy(words, cp.d.p, n * 4, hipMemcpyDeviceToHost), "reading the cull plane");
+    return RT_OK;
+}
+
+/* test hook: the subtree cull's gate words (rt_cull.h) the last render launch of the context was handed, one per pixel, read back (waits for
+ * the device).  info4 as rt_debug_primary_cull's, with the pixel count as the words */
+extern "C" rt_status rt_debug_subtree_cull(rt_ctx *ctx, uint32_t *words, int32_t capacity_words, int32_t *info4)
+{
+    if (!ctx || !info4 || capacity_words < 0) return set_err(ctx, RT_ERR_INVALID, "bad argument");
+    const CullPlane &cp = ctx->cull;
+    const bool have = cp.plan.valid && cp.plan.used_last && cp.d.p;
+    const size_t n = have ? (size_t)cp.plan.key.width * (size_t)cp.plan.key.height : 0;
+    info4[0] = have ? 1 : 0;
+    info4[1] = have ? cp.plan.key.width : 0;
+    info4[2] = have ? cp.plan.key.height : 0;
+    info4[3] = (int32_t)n;
+    if (!have || !words || (size_t)capacity_words < n) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
+    RT_HIP(ctx, hipMemcpy(words, cp.d.p + rt_cull_words(cp.plan.key.width, cp.plan.key.height), n * 4, hipMemcpyDeviceToHost), "reading the gate words");
+    return RT_OK;
+}
+
+/* test / development hook, host only (no device is touched): rt_cull_gate_word per pixel of `cam`'s image on a flattened scene, as the
+ * pre-pass writes it (0 everywhere unless the scene has exactly one mesh; a pixel the bit plane flags has every gate dead).  words: width * height, or NULL.
+ * stats4, or NULL: over the unflagged pixels whose cone may enter the root box, the centre ray's walk in the render kernel's order (far
+ * child first, the pop rule, the med3 or the min / max slab form as the kernel picks it; no triangle is tested, so `best` stays infinite
+ * and this counts at least the steps of the real traversal) - {those pixels, its node steps ungated, its node steps with the pixel's word,
+ * pixels whose word is not 0} - what tools/primary_cull_estimate.py prints. */
+extern "C" rt_status rt_debug_subtree_cull_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats4)
+{
+    if (!view || !cam || !view->blob || cam->width <= 0 || cam->height <= 0 || (int64_t)cam->width * cam->height > (1 << 28)) return RT_ERR_INVALID;
+    float c12[12];
+    camera_floats(*cam, c12);
+    int64_t st[4] = {0, 0, 0, 0};
+    for (int py = 0; py < cam->height; py++)
+        for (int px = 0; px < cam->width; px++) {
+            float P[3];
+            rt_cull_primary(c12, px, py, P);
+            const rt_cull_cone cone = rt_cull_cone_of(P, c12, antialias);
+            const bool flagged = rt_cull_no_leaf(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, view->num_meshes, rt_cull_local_stack());
+            const uint32_t word = view->num_meshes == 1 ? rt_cull_gate_word(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, rt_cull_local_stack()) : 0u;
+            if (words) words[(size_t)py * (size_t)cam->width + (size_t)px] = word;
+            if (flagged || view->num_meshes != 1) continue;
+            const float *m0 = view->blob + 4 * (size_t)view->off_meshes;
+            if (rt_cull_box_missed(cone, m0[0], m0[1], m0[2], m0[3], m0[4], m0[5])) continue;
+            const float inv[3] = {1.0f / P[0], 1.0f / P[1], 1.0f / P[2]};
+            st[0]++;
+            st[1] += rt_cull_walk_steps(view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, c12, P, inv, 0u);
+            st[2] += rt_cull_walk_steps(view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, c12, P, inv, word);
+            st[3] += word != 0u;
+        }
+    if (stats4) std::memcpy(stats4, st, sizeof st);
     return RT_OK;
 }
 

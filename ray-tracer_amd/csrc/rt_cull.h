@@ -56,7 +56,9 @@
 #define RT_CULL_JITTER 0.001f            /* rt_jitter's range (rt_rng.h) */
 #define RT_CULL_TINY 9.094947017729282e-13f      /* 2^-40: the least |v_k|, N and F the bound is used from */
 #define RT_CULL_HUGE 549755813888.0f             /* 2^39: the largest |b|, |o| */
+#ifndef RT_CULL_E                        /* (tests/sanitize/gate_soundness.cpp is also built with the margin taken away, to show that it finds the loss) */
 #define RT_CULL_E 2.384185791015625e-07          /* E = 2^-22 (binary64) */
+#endif
 #define RT_CULL_STACK 16                 /* pending siblings of the walk: at most one per level of a depth-RT_BVH_DEPTH tree */
 static_assert(RT_CULL_STACK > RT_STACK_ENTRIES, "the walk's stack holds a pending sibling per tree level");
 
@@ -187,6 +189,103 @@ RT_CULL_HD bool rt_cull_no_leaf(const rt_cull_cone &c, const float *blob, int32_
     return none;
 }
 
+/* ================= THE SUBTREE CULL: the same question one level down, per gate of the one mesh (rt_device_scene.h: rt_node, RT_GATE_COUNT) =====
+ * Beside its bit a pixel gets a word: bit g is set iff gate g is DEAD for the pixel's cone.  A reference is dead when its box is certainly
+ * missed (rt_cull_box_missed of the box its parent holds for it), or it is the empty leaf, or it is an internal node whose two references are
+ * both dead - so no cone-live path leads from it to a leaf with triangles - or the reference above it is dead (which only spares the walk:
+ * nothing below a dead reference is reached).  There is no new predicate and no new error bound.  The render kernel that reads the plane
+ * (rt_descend_pop<.., GATES>, rt_traverse.h) does not enter a dead gate with a PRIMARY ray of the pixel; bounce rays are never gated.
+ *
+ * WHY THE FRAMES STAY BIT-IDENTICAL.  Below a dead reference every root-to-leaf path has a box that no slab form accepts for any sample of
+ * the pixel and any `best` (the bound above, unchanged), or ends in the empty leaf.  So the ungated traversal of that subtree tests no
+ * triangle: w_best and w_prim do not move, and whatever it pushes it pops or refuses before it returns to the entry below.  Not entering
+ * the reference leaves the lane in the state the ungated traversal reaches after the subtree:
+ *   - had the dead child been visited first and its sibling deferred, the sibling was pushed with dist < best and best has not changed when
+ *     it is popped, so the pop is a take (dist < best takes through a chain edge too): going to the sibling directly is the same decision;
+ *   - had the dead child been the deferred one, its later pop, taken or refused, changes nothing;
+ *   - with both children dead the node is a dead end and pops, as the ungated traversal does after two fruitless subtrees.
+ * A traversal draws no random numbers.  Only the cost counters change, which feed the tile schedule and not the image.
+ * tests/sanitize/gate_soundness.cpp walks both traversals side by side and compares the triangles tested and the result.
+ *
+ * THE WORDS sit behind the bit plane in the same allocation: pixel i's word is word rt_cull_words(W, H) + i; the allocation is
+ * rt_cull_alloc_words(rt_cull_words(W, H)) words, a word for every thread of the pre-pass. */
+#define RT_CULL_ANTIALIAS 1              /* rt_launch_cull's view_flags: the view's rays are jittered ... */
+#define RT_CULL_WITH_GATES 2             /* ... and the gate words are to be computed (else every one is written as 0) */
+RT_CULL_HD size_t rt_cull_alloc_words(size_t plane_words) { return plane_words + plane_words * 32; }
+
+/* no cone-live path from `ref` (whose own box is not missed) to a leaf with triangles?  rt_cull_no_leaf's walk from a reference, on the stack's
+ * entries from `base` up; a reference outside the nodes or a full stack answers "a leaf may be reached" */
+template <class Stack>
+RT_CULL_HD bool rt_cull_ref_no_leaf(const rt_cull_cone &c, const float *blob, int32_t off_nodes, int32_t num_nodes, uint32_t ref, Stack &stack, int base)
+{
+    int sp = base;
+    uint32_t cur = ref;
+    for (;;) {
+        if (cur & RT_REF_LEAF) {
+            if (((cur >> RT_REF_COUNT_SHIFT) & RT_REF_COUNT_MAX) != 0u) return false;
+            if (sp == base) return true;
+            cur = stack[--sp];
+            continue;
+        }
+        const uint32_t idx = cur & RT_REF_NODE_MASK;
+        if (idx >= (uint32_t)num_nodes) return false;
+        const float *n = blob + 4 * ((size_t)off_nodes + 4 * (size_t)idx);
+        const bool l_missed = rt_cull_box_missed(c, n[0], n[1], n[2], n[3], n[4], n[5]);
+        const bool r_missed = rt_cull_box_missed(c, n[6], n[7], n[8], n[9], n[10], n[11]);
+        const uint32_t lref = rt_cull_bits(n[12]), rref = rt_cull_bits(n[13]);
+        if (!l_missed && !r_missed) {
+            if (sp >= RT_CULL_STACK) return false;
+            stack[sp++] = rref;
+            cur = lref;
+        } else if (!l_missed) {
+            cur = lref;
+        } else if (!r_missed) {
+            cur = rref;
+        } else {
+            if (sp == base) return true;
+            cur = stack[--sp];
+        }
+    }
+}
+
+/* The gate word of a cone for mesh `mesh` of a flattened scene: bit g set iff gate g is dead.  Walks the nodes that hold gates (a reference
+ * without a gate has none below it: the numbering is breadth-first) with the pending ones on the stack, a dead parent marked in the entry's
+ * chain bit, and asks rt_cull_ref_no_leaf about every gate that is neither below a dead one nor missed.  Anything unexpected (a cone that is
+ * not ok, a reference outside the nodes, a full stack) leaves bits clear: "not dead" is always safe. */
+#define RT_CULL_DEAD_ABOVE RT_REF_CHAIN
+template <class Stack>
+RT_CULL_HD uint32_t rt_cull_gate_word(const rt_cull_cone &c, const float *blob, int32_t off_nodes, int32_t num_nodes, int32_t off_meshes, int32_t mesh, Stack stack)
+{
+    if (!c.ok) return 0u;
+    const uint32_t root = rt_cull_bits(blob[4 * ((size_t)off_meshes + 2 * (size_t)mesh + 1) + 2]);
+    if (root & RT_REF_LEAF) return 0u;
+    uint32_t word = 0u;
+    int sp = 0;
+    uint32_t cur = root & RT_REF_NODE_MASK;
+    {
+        /* (a cone that misses the root box: every gate is below a dead reference) */
+        const float *m0 = blob + 4 * ((size_t)off_meshes + 2 * (size_t)mesh);
+        if (rt_cull_box_missed(c, m0[0], m0[1], m0[2], m0[3], m0[4], m0[5])) cur |= RT_CULL_DEAD_ABOVE;
+    }
+    for (;;) {
+        const uint32_t idx = cur & RT_REF_NODE_MASK;
+        if (idx >= (uint32_t)num_nodes) return word;
+        const float *n = blob + 4 * ((size_t)off_nodes + 4 * (size_t)idx);
+        for (int side = 0; side < 2; side++) {
+            const uint32_t gate = rt_cull_bits(n[14 + side]) & ~1u;
+            if (gate == 0u) continue;
+            const uint32_t ref = rt_cull_bits(n[12 + side]);
+            const float *b = n + 6 * side;
+            bool dead = (cur & RT_CULL_DEAD_ABOVE) != 0u || rt_cull_box_missed(c, b[0], b[1], b[2], b[3], b[4], b[5]);
+            if (!dead) dead = rt_cull_ref_no_leaf(c, blob, off_nodes, num_nodes, ref, stack, sp);
+            if (dead) word |= gate;
+            if (!(ref & RT_REF_LEAF) && sp < RT_CULL_STACK) stack[sp++] = (ref & RT_REF_NODE_MASK) | (dead ? RT_CULL_DEAD_ABOVE : 0u);
+        }
+        if (sp == 0) return word;
+        cur = stack[--sp];
+    }
+}
+
 /* ---- the slab test's three forms (rt_intersect.h: box_test, box_enter, box_enter_med3) restated for host code, operation for operation:
  * what tests/sanitize/cull_soundness.cpp holds the predicate against.  fminf / fmaxf drop a NaN operand like the device's. */
 RT_CULL_HD bool rt_cull_slab_test(const float b0[3], const float b1[3], const float o[3], const float inv[3])
@@ -217,6 +316,81 @@ RT_CULL_HD bool rt_cull_slab_enter_med3(const float b0[3], const float b1[3], co
         lo = rt_cull_med3(t1, t2, lo); hi = rt_cull_med3(t1, t2, hi);
     }
     return lo < hi;
+}
+
+/* ---- the render kernel's traversal of one mesh (rt_render_loop.inc: the ONE_MESH root test, rt_descend_pop's step, the leaf, rt_pop) restated
+ * for host code with the slab forms above: far child first, strict <, the pop rule, the med3 form unless a direction component is exactly
+ * zero.  `gates` is the lane's gate word (0: the ungated traversal).  leaf(ref, best, prim) tests a leaf's triangles and may lower best.
+ * Returns the node steps, -1 for a tree the flattener did not make.  What tests/sanitize/gate_soundness.cpp and the estimate tool walk. */
+RT_CULL_HD bool rt_cull_walk_enter(const float *b, const float o[3], const float inv[3], float best, bool med3, float &dist)
+{
+    const float b0[3] = {b[0], b[1], b[2]}, b1[3] = {b[3], b[4], b[5]};
+    if (med3) {
+        float lo = 0.0f;
+        for (int k = 0; k < 3; k++) lo = rt_cull_med3((b0[k] - o[k]) * inv[k], (b1[k] - o[k]) * inv[k], lo);
+        dist = lo;
+        return rt_cull_slab_enter_med3(b0, b1, o, inv, best);
+    }
+    float tmin = 0.0f;
+    for (int k = 0; k < 3; k++) tmin = fmaxf(tmin, fminf((b0[k] - o[k]) * inv[k], (b1[k] - o[k]) * inv[k]));
+    dist = tmin;
+    return rt_cull_slab_enter(b0, b1, o, inv, best);
+}
+template <class Leaf>
+RT_CULL_HD int64_t rt_cull_walk(const float *blob, int32_t off_nodes, int32_t num_nodes, int32_t off_meshes, int32_t mesh, const float o[3], const float d[3],
+                                const float inv[3], uint32_t gates, float &best, int32_t &prim, Leaf leaf)
+{
+    best = RT_INF_F; prim = -1;
+    if (d[0] != d[0] || d[1] != d[1] || d[2] != d[2]) return 0;
+    const float *m0 = blob + 4 * ((size_t)off_meshes + 2 * (size_t)mesh);
+    const uint32_t root = rt_cull_bits(m0[6]);
+    {
+        const float b0[3] = {m0[0], m0[1], m0[2]}, b1[3] = {m0[3], m0[4], m0[5]};
+        float rd = 0.0f;
+        for (int k = 0; k < 3; k++) rd = fmaxf(rd, fminf((b0[k] - o[k]) * inv[k], (b1[k] - o[k]) * inv[k]));
+        if (!rt_cull_slab_test(b0, b1, o, inv) || rd > RT_INF_F || ((root & RT_REF_CHAIN) && !(rd < RT_INF_F))) return 0;
+    }
+    const bool med3 = !(d[0] == 0.0f || d[1] == 0.0f || d[2] == 0.0f);
+    struct { float dist; uint32_t ref; } stack[RT_STACK_ENTRIES + 2];
+    int sp = 0;
+    int64_t steps = 0;
+    uint32_t cur = root;
+    for (;;) {
+        if (!(cur & RT_REF_LEAF)) {
+            const uint32_t idx = cur & RT_REF_NODE_MASK;
+            if (idx >= (uint32_t)num_nodes) return -1;
+            steps++;
+            const float *n = blob + 4 * ((size_t)off_nodes + 4 * (size_t)idx);
+            float ld, rdist;
+            bool l_push = rt_cull_walk_enter(n, o, inv, best, med3, ld), r_push = rt_cull_walk_enter(n + 6, o, inv, best, med3, rdist);
+            const uint32_t lref = rt_cull_bits(n[12]), rref = rt_cull_bits(n[13]);
+            l_push = l_push && (gates & rt_cull_bits(n[14])) == 0u;
+            r_push = r_push && (gates & rt_cull_bits(n[15])) == 0u;
+            const bool l_first = ld < rdist;
+            if (l_push && r_push) {
+                if (sp > RT_STACK_ENTRIES) return -1;
+                stack[sp].dist = l_first ? ld : rdist;
+                stack[sp].ref = l_first ? lref : rref;
+                sp++;
+                cur = l_first ? rref : lref;
+                continue;
+            }
+            if (l_push || r_push) { cur = l_push ? lref : rref; continue; }
+            cur = RT_REF_EMPTY_LEAF;
+        }
+        if (((cur >> RT_REF_COUNT_SHIFT) & RT_REF_COUNT_MAX) != 0u) leaf(cur, best, prim);
+        if (sp == 0) return steps;
+        sp--;
+        const bool take = stack[sp].dist < best || (stack[sp].dist == best && !(stack[sp].ref & RT_REF_CHAIN));
+        cur = take ? stack[sp].ref : RT_REF_EMPTY_LEAF;
+    }
+}
+struct rt_cull_no_triangles { RT_CULL_HD_MEMBER void operator()(uint32_t, float &, int32_t &) const {} };
+RT_CULL_HD int64_t rt_cull_walk_steps(const float *blob, int32_t off_nodes, int32_t num_nodes, int32_t off_meshes, int32_t mesh, const float o[3], const float d[3],
+                                      const float inv[3], uint32_t gates)
+{
+    float best; int32_t prim;
+    return rt_cull_walk(blob, off_nodes, num_nodes, off_meshes, mesh, o, d, inv, gates, best, prim, rt_cull_no_triangles());
 }
 
 #include <cstring>

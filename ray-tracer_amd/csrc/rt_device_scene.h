@@ -173,7 +173,11 @@ enum { RT_OBJ_SPHERE = 0, RT_OBJ_TRIANGLE = 1, RT_OBJ_QUAD = 2, RT_OBJ_ONE_WAY_Q
 typedef struct __attribute__((aligned(16))) { float x, y, z, w; } rt_f4;
 
 /* q0 = (lmin.x lmin.y lmin.z lmax.x) q1 = (lmax.y lmax.z rmin.x rmin.y) q2 = (rmin.z rmax.x rmax.y rmax.z)
- * q3 = (lref, rref, 0, 0) as raw bits */
+ * q3 = (lref, rref, lgate, rgate) as raw bits.  A gate (rt_cull.h, the subtree cull) is one of a mesh's first RT_GATE_COUNT non-root references
+ * in breadth-first order, left before right: internal nodes, leaves and chain edges alike.  Gate g (1..RT_GATE_COUNT) is the one-hot word
+ * 1 << g in lgate / rgate of the node that holds the reference; every other reference has 0 there, and bit 0 is never a gate.  The words are
+ * topology like the references: a rebuild (rt_rebuild_kernel.h) keeps them. */
+#define RT_GATE_COUNT 31u
 typedef struct { rt_f4 q[4]; } rt_node;
 
 /* q0 = (p0.x p0.y p0.z s1.x) q1 = (s1.y s1.z s2.x s2.y) q2 = (s2.z n.x n.y n.z) */

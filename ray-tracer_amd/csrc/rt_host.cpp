@@ -761,10 +761,27 @@ std::string rt_flatten(const rt_scene_builder &b, FlatScene &out)
             mesh_i++;
             out.stack_entries = std::max(out.stack_entries, o.stack_need);
         }
+        /* the mesh's gates (rt_device_scene.h, rt_node): its first RT_GATE_COUNT non-root references in breadth-first order, left before right */
+        std::vector<uint32_t> lgate(o.nodes.size(), 0u), rgate(o.nodes.size(), 0u);
+        if (o.type == RT_OBJ_MESH && !(o.root_ref & RT_REF_LEAF)) {
+            std::vector<uint32_t> queue{o.root_ref & RT_REF_NODE_MASK};
+            uint32_t g = 0;
+            for (size_t at = 0; at < queue.size() && g < RT_GATE_COUNT; at++) {
+                const uint32_t k = queue[at];
+                if (k >= o.nodes.size()) break;
+                const uint32_t refs[2] = {rt_f2u(o.nodes[k].q[3].x), rt_f2u(o.nodes[k].q[3].y)};
+                for (int side = 0; side < 2 && g < RT_GATE_COUNT; side++) {
+                    (side ? rgate : lgate)[k] = 1u << ++g;
+                    if (!(refs[side] & RT_REF_LEAF)) queue.push_back(refs[side] & RT_REF_NODE_MASK);
+                }
+            }
+        }
         for (size_t k = 0; k < o.nodes.size(); k++) {
             rt_node n = o.nodes[k];
             n.q[3].x = rt_u2f(rebase(rt_f2u(n.q[3].x)));
             n.q[3].y = rt_u2f(rebase(rt_f2u(n.q[3].y)));
+            n.q[3].z = rt_u2f(lgate[k]);
+            n.q[3].w = rt_u2f(rgate[k]);
             std::memcpy(&out.blob[(size_t)out.off_nodes + (node_base + k) * 4], &n, sizeof n);
         }
         for (size_t k = 0; k < o.tris.size(); k++) {

@@ -176,6 +176,7 @@ struct CullPlane {
     Event ev;                            /* recorded behind the pre-pass */
     hipStream_t stream = nullptr;        /* ... on this stream (the caller's: not owned) */
     bool enabled = true;                 /* RT_AMD_PRIMARY_CULL=0: every launch renders without the plane */
+    bool gates = true;                   /* RT_AMD_SUBTREE_CULL=0: the pre-pass writes every gate word as 0 (the kernel then gates nothing) */
 };
 
 /* knobs (RT_AMD_*), none changes an image: rt_schedule.h has them, their accepted ranges and what the kernel is handed for them

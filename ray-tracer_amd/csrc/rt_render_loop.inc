@@ -51,7 +51,17 @@
     uint32_t cur = 0;
     int sp = 0, w_prim = -1;
     float w_best = RT_INF_F;
-    uint32_t w_zero_dir = 0u;    /* this traversal's ray has a direction component of exactly zero (box_enter_med3); an integer: its lane mask is then one compare */
+    /* this traversal's ray, one word: bit 0 - RT_RAY_ZERO_DIR - says that its direction has a component of exactly zero (box_enter rather than
+     * box_enter_med3); an integer, so that its lane mask is one compare.  CULL: bits 1..31 are the traversal's dead gates (the subtree cull,
+     * rt_cull.h) - the pixel's gate word for a primary ray, 0 for a bounce ray - so the flag is read through RT_ZERO_DIR_LANES() alone, which masks */
+    uint32_t w_ray_bits = 0u;
+    constexpr uint32_t RT_RAY_ZERO_DIR = 1u;
+    static_assert((RT_RAY_ZERO_DIR & ~1u) == 0u, "gate g is bit g, g >= 1 (rt_device_scene.h): bit 0 is the zero-direction flag's");
+    /* (a macro, not a lambda: through a lambda 35 kernels that are not compiled with CULL come out with other code) */
+#define RT_ZERO_DIR_LANES() __builtin_amdgcn_uicmp(CULL ? w_ray_bits & RT_RAY_ZERO_DIR : w_ray_bits, 0u, RT_ICMP_NE)
+    /* CULL: the pixel's gate word, loaded by px_fetch with the pixel's cull bit and held in this register between the pixel's samples (the
+     * alternatives and what was measured: DESIGN.md section 24, "The subtree cull") */
+    uint32_t px_gates = 0u;
     Chunk ch;
     ch.next = 0; ch.end = 0; ch.frame = 0; ch.exhausted = false;
 #ifdef RT_STATS
@@ -89,7 +99,8 @@
             }
         }
         RT_LAP(TM_SHADE);
-        px_fetch<BUDGET, VIEWS, CULL>(p, ch, a, f, lane);
+        if (CULL) px_fetch<BUDGET, VIEWS, CULL>(p, ch, a, f, lane, &px_gates);
+        else px_fetch<BUDGET, VIEWS, CULL>(p, ch, a, f, lane);
         if (BUDGET) {
             /* Where budgets are sparse most slots hand their lane nothing.  A lane left in M_FETCH asks again at once instead of idling through
              * a round of the others' work: until every lane has a pixel to trace or the tiles are out (then px_fetch ends the lanes left).
@@ -115,7 +126,8 @@
                     const bool rh = box_test(m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, p.o, p.inv, rd);
                     if (!(!rh || rd > RT_INF_F || ((root_ref & RT_REF_CHAIN) && !(rd < RT_INF_F)))) {
                         cur = root_ref; sp = 0; w_best = RT_INF_F; w_prim = -1;
-                        w_zero_dir = (p.d.x == 0.0f || p.d.y == 0.0f || p.d.z == 0.0f) ? 1u : 0u;
+                        w_ray_bits = (p.d.x == 0.0f || p.d.y == 0.0f || p.d.z == 0.0f) ? RT_RAY_ZERO_DIR : 0u;
+                        if (CULL) w_ray_bits |= p.bounce == 0 ? px_gates & ~RT_RAY_ZERO_DIR : 0u;
                         p.mode = M_WAIT;
                         p.frame_steps |= 0x80000000u;
                         RT_STAT(ST_MESH_START);
@@ -141,7 +153,7 @@
                 const bool rh = box_test(m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, p.o, p.inv, rd);
                 if (!rh || rd > RT_INF_F || ((root_ref & RT_REF_CHAIN) && !(rd < RT_INF_F))) continue;
                 cur = root_ref; sp = 0; w_best = RT_INF_F; w_prim = -1;
-                w_zero_dir = (p.d.x == 0.0f || p.d.y == 0.0f || p.d.z == 0.0f) ? 1u : 0u;
+                w_ray_bits = (p.d.x == 0.0f || p.d.y == 0.0f || p.d.z == 0.0f) ? RT_RAY_ZERO_DIR : 0u;
                 p.mode = M_WAIT;
                 p.frame_steps |= 0x80000000u;           /* (cost bookkeeping: this pixel traverses) */
                 RT_STAT(ST_MESH_START);
@@ -188,11 +200,11 @@
                         /* the loop pops behind a dead end and goes on (rt_descend_pop, rt_traverse.h): what it hands the leaf section
                          * is a leaf with triangles, a finished mesh, or what the descend_keep rule sent out early */
                         if (rt_descend_pop_enters(cur, sp)) {
-                            if (__builtin_amdgcn_uicmp(w_zero_dir, 0u, RT_ICMP_NE) == 0ull) rt_descend_pop<NT, true>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
-                            else rt_descend_pop<NT, false>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
+                            if (RT_ZERO_DIR_LANES() == 0ull) rt_descend_pop<NT, true, CULL>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep, w_ray_bits RT_STAT_ARGS);
+                            else rt_descend_pop<NT, false, CULL>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep, w_ray_bits RT_STAT_ARGS);
                         }
                     } else if (!(cur & RT_REF_LEAF)) {
-                        if (__builtin_amdgcn_uicmp(w_zero_dir, 0u, RT_ICMP_NE) == 0ull) rt_descend<NT, true>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
+                        if (RT_ZERO_DIR_LANES() == 0ull) rt_descend<NT, true>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
                         else rt_descend<NT, false>(cur, sp, my_stack, L, o, inv, w_best, a.descend_keep RT_STAT_ARGS);
                     }
                     RT_LAP_SPLIT(TM_DESCEND)
@@ -234,5 +246,6 @@
 
         if (__ballot(p.mode != M_DONE) == 0ull) break;
     }
+#undef RT_ZERO_DIR_LANES
     RT_STATS_FLUSH();
 }

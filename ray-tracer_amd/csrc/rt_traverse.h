@@ -108,8 +108,12 @@ __device__ __forceinline__ bool rt_descend_pop_enters(uint32_t cur, int sp)
  * The body stays branch-free: the top of the stack is read with the node, every iteration, and the pop is selects on it.
  * Nothing a frame is made of changes: w_best does not change in here and no triangle is tested, so every take / refuse decision, every
  * box test, the push order and the visit order of a lane are those of rt_descend + rt_pop one macro step at a time - the frames are bit-identical. */
-template <int NT, bool MED3>
-__device__ __forceinline__ void rt_descend_pop(uint32_t &cur, int &sp, uint2 *my_stack, const Lds &L, V3 o, V3 inv, float w_best, int descend_keep RT_STAT_PARAMS)
+/* GATES (the subtree cull, rt_cull.h; only the kernel that reads the cull plane): `w_gates` is the lane's word of dead gates - its pixel's for a
+ * primary ray, 0 for a bounce ray; bit 0 is not a gate and is ignored here (the caller keeps the ray's zero-direction flag in it).  The node's
+ * last 16 bytes are then read whole, references and gate words, and a child whose gate is in the word is not entered, whatever its box says:
+ * rt_cull.h has the argument for why the frames stay bit-identical. */
+template <int NT, bool MED3, bool GATES = false>
+__device__ __forceinline__ void rt_descend_pop(uint32_t &cur, int &sp, uint2 *my_stack, const Lds &L, V3 o, V3 inv, float w_best, int descend_keep, uint32_t w_gates RT_STAT_PARAMS)
 {
     /* a lane that comes in on the empty leaf (the post-leaf pop refused its entry): pops until an entry is taken or the stack is empty (rare) */
     while (cur == RT_REF_EMPTY_LEAF && sp > 0) {
@@ -128,13 +132,23 @@ __device__ __forceinline__ void rt_descend_pop(uint32_t &cur, int &sp, uint2 *my
         const uint2 top = my_stack[top_slot * NT];
         const v4f *n = L.nodes + 4 * (int)(cur & RT_REF_NODE_MASK);
         const v4f q0 = n[0], q1 = n[1], q2 = n[2];
-        const uint2 refs = *(const uint2 *)(n + 3);          /* the two child references: 8 of the last 16 bytes */
+        uint32_t lref, rref, lgate = 0u, rgate = 0u;
+        if (GATES) {
+            const v4f q3 = n[3];                                 /* the references and their gate words: the last 16 bytes */
+            lref = __float_as_uint(q3.x); rref = __float_as_uint(q3.y); lgate = __float_as_uint(q3.z); rgate = __float_as_uint(q3.w);
+        } else {
+            const uint2 refs = *(const uint2 *)(n + 3);          /* the two child references: 8 of the last 16 bytes */
+            lref = refs.x; rref = refs.y;
+        }
+        /* (GATES: a dead child's box is tested against best = 0, which no box passes - both slab forms ask for an entry distance, never
+         * negative, below min(exit distance, best) - so the gate costs a select in front of the test and no lane mask of its own to combine
+         * behind it: with the masks combined the kernel spilled four more scalar registers and got a private segment) */
+        const float l_best = GATES && (w_gates & lgate) != 0u ? 0.0f : w_best, r_best = GATES && (w_gates & rgate) != 0u ? 0.0f : w_best;
         float ld, rdist;
-        const bool l_push = MED3 ? box_enter_med3(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, w_best, ld)
-                                 : box_enter(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, w_best, ld);
-        const bool r_push = MED3 ? box_enter_med3(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, w_best, rdist)
-                                 : box_enter(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, w_best, rdist);
-        const uint32_t lref = refs.x, rref = refs.y;
+        const bool l_push = MED3 ? box_enter_med3(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, l_best, ld)
+                                 : box_enter(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, l_best, ld);
+        const bool r_push = MED3 ? box_enter_med3(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, r_best, rdist)
+                                 : box_enter(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, r_best, rdist);
         const bool l_first = ld < rdist;
         /* (rt_descend's step: the deferred sibling always stored above the top, sp moves when both children are entered) */
         const bool both = l_push && r_push;

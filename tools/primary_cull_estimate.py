@@ -2,7 +2,9 @@
    python tools/primary_cull_estimate.py [--scene monkey] [--width 128] [--height 72] [--no-antialias]
 For a config scene (ray-tracer_amd/scenes.py) and an image size it evaluates the kernel's predicate per pixel through
 rt_debug_primary_cull_host and prints the flagged share of the pixels whose jitter cone may enter a mesh's root box, and the share of the
-centre-ray node steps of those pixels that the flagged ones carry - the traversal work the render kernel no longer does for primary rays."""
+centre-ray node steps of those pixels that the flagged ones carry - the traversal work the render kernel no longer does for primary rays.
+For the other root-entering pixels it prints, from rt_debug_subtree_cull_host, the share of the centre ray's node steps that lie below a dead
+gate (the subtree cull): the steps the kernel's walk takes without the pixel's gate word and no longer takes with it."""
 import argparse
 import importlib
 import json
@@ -20,6 +22,9 @@ def estimate(scene="monkey", width=128, height=72, antialias=True):
     st = dict(st, scene=scene, width=width, height=height, antialias=bool(antialias), pixels=width * height)
     st["flagged_share_of_root_entering"] = st["flagged_root_entering"] / st["root_entering"] if st["root_entering"] else 0.0
     st["step_share_of_flagged"] = st["centre_steps_flagged"] / st["centre_steps_root_entering"] if st["centre_steps_root_entering"] else 0.0
+    _gates, gt = rt.subtree_cull_host(rt.SceneObjects(objs), rt.Camera(width, height), antialias)
+    st.update({"gate_" + k: v for k, v in gt.items()})
+    st["dead_gate_step_share"] = 1.0 - gt["centre_steps_gated"] / gt["centre_steps"] if gt["centre_steps"] else 0.0
     return st
 
 
@@ -43,6 +48,10 @@ def main():
         st["centre_steps_flagged"] / max(st["flagged_root_entering"], 1),
         (st["centre_steps_root_entering"] - st["centre_steps_flagged"]) / max(st["root_entering"] - st["flagged_root_entering"], 1)))
     print("share of those steps carried by the flagged pixels: %.1f %%" % (100 * st["step_share_of_flagged"]))
+    print("unflagged root-entering pixels: %d, %d with a dead gate; kernel-order centre-ray node steps %.1f per pixel, %.1f with the gate word" % (
+        st["gate_pixels"], st["gate_pixels_with_dead_gates"], st["gate_centre_steps"] / max(st["gate_pixels"], 1),
+        st["gate_centre_steps_gated"] / max(st["gate_pixels"], 1)))
+    print("share of those steps below a dead gate:             %.1f %%" % (100 * st["dead_gate_step_share"]))
 
 
 if __name__ == "__main__":
