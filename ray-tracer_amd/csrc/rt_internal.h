@@ -496,7 +496,8 @@ Args ray_args_view(const rt_ctx *ctx, const rt_scene *scene, const rt_camera *ca
 }
 
 /* A ray kernel of the scene's shape queued on `stream` behind the clearing of its ticket counter (`launcher`: rt_launch_query, rt_launch_occlusion,
- * rt_launch_ao, rt_launch_nearest or rt_launch_multihit, with its `front`: 0, 1 or, where the family has a third, 2).  Without the bracket: for the work of a caller that is inside one. */
+ * rt_launch_ao, rt_launch_nearest, rt_launch_sweep, rt_launch_multihit, rt_launch_overlap or rt_launch_tritri, with its `front`: read by the
+ * first two only).  Without the bracket: for the work of a caller that is inside one. */
 template <class Args>
 rt_status enqueue_rays(rt_ctx *ctx, const rt_scene *scene, const Args &a, hipError_t (*launcher)(const Args *, rt_shape, int, int, size_t, hipStream_t), int front,
                        const char *what_clear, const char *what, hipStream_t stream)

@@ -53,9 +53,9 @@
 #include "rt_render_kernel.h"      /* the render kernel and its shape table */
 #include "rt_rebuild_kernel.h"     /* a committed mesh's BVH rebuilt from new vertices: nothing of the traversal either (last: the kernels before it are emitted as they were) */
 #include "rt_cull_kernel.h"        /* the primary-ray cull's pre-pass: one bit per pixel of a view (behind everything else, for the same reason) */
-#include "rt_sweep_kernel.h"      /* sphere-cast queries: where a moving ball first touches the scene (in every build; launched as the nearest kernel's second front) */
+#include "rt_sweep_kernel.h"      /* sphere-cast queries: where a moving ball first touches the scene (in every build; last, for the same reason) */
 #include "rt_nearest_kernel.h"     /* nearest-surface queries: closest point and distance (in every build; last, for the same reason) */
-#include "rt_overlap_kernel.h"     /* box-overlap queries: which surfaces touch a box (not in the development builds; launched as the multi-hit kernel's second front) */
-#include "rt_tritri_kernel.h"      /* triangle-overlap queries: which surfaces a triangle cuts, and where (not in the development builds; launched as the multi-hit kernel's third front) */
+#include "rt_overlap_kernel.h"     /* box-overlap queries: which surfaces touch a box (not in the development builds; last, for the same reason) */
+#include "rt_tritri_kernel.h"      /* triangle-overlap queries: which surfaces a triangle cuts, and where (not in the development builds; last, for the same reason) */
 #include "rt_multihit_kernel.h"    /* multi-hit ray queries: the first k hits of a ray, and hit counts (not in the development builds; last, for the same reason) */
 #include "rt_winding_kernel.h"     /* winding-number queries: containment and the sign of a distance; a dense reduction, no traversal (in every build; last, for the same reason) */

@@ -20,8 +20,11 @@
 #include "rt_multihit.h"
 #include "rt_nearest.h"
 #include "rt_occlusion.h"
+#include "rt_overlap.h"
 #include "rt_query.h"
 #include "rt_rebuild.h"
+#include "rt_sweep.h"
+#include "rt_tritri.h"
 #include "rt_winding.h"
 
 extern "C" {
@@ -49,16 +52,18 @@ hipError_t rt_launch_tiles_copy(float *compact, float *frame, const uint32_t *ti
 hipError_t rt_launch_rgba8(const float *rgb, int n_pixels, uint8_t *out, hipStream_t stream);
 
 /* ---- rt_ray_kernels.h: the ray kernels (hipErrorNotSupported in the development builds) ---- */
-/* aov, vis: 0 the caller's rays, 1 the pass over a view; the ambient-occlusion kernel has the one front, whatever `front` says */
+/* aov, vis: 0 the caller's rays, 1 the pass over a view; every other kernel here has the one front, whatever `front` says: the signature is
+ * kept so that rt_internal.h's enqueue_rays serves them all */
 hipError_t rt_launch_query(const rt_query_args *args, rt_shape shape, int aov, int num_cus, size_t lds_bytes, hipStream_t stream);
 hipError_t rt_launch_occlusion(const rt_occlusion_args *args, rt_shape shape, int vis, int num_cus, size_t lds_bytes, hipStream_t stream);
 hipError_t rt_launch_ao(const rt_ao_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
-/* rt_multihit_kernel.h, with them: the signature is the ray kernels' (rt_internal.h's enqueue_rays calls it); front 0: the multi-hit kernel,
- * front 1: the box-overlap kernel (rt_overlap_kernel.h), which reads the block's ov_ fields, front 2: the triangle-overlap kernel
- * (rt_tritri_kernel.h), which reads its ot_ fields */
+/* rt_multihit_kernel.h, with them */
 hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
 /* ... and its second pass over the records: the texture coordinates of those on a sphere whose material needs them */
 hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *args, int num_cus, hipStream_t stream);
+/* rt_overlap_kernel.h and rt_tritri_kernel.h, with them */
+hipError_t rt_launch_overlap(const rt_overlap_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
+hipError_t rt_launch_tritri(const rt_tritri_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
 
 /* ---- rt_denoise_kernel.h ---- */
 hipError_t rt_launch_denoise_pack(const rt_denoise_args *args, hipStream_t stream);
@@ -82,10 +87,11 @@ hipError_t rt_launch_rebuild(const rt_rebuild_args *args, hipStream_t stream);
 hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t height, int32_t view_flags, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
                           int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream);
 
-/* ---- rt_nearest_kernel.h (in every build) ---- */
-/* the signature is the ray kernels'; front 0: the nearest-surface kernel, front 1: the sphere-cast kernel (rt_sweep_kernel.h), which reads the
- * block's sw_ fields and the records a nearest-surface launch left in sw_nearest */
+/* ---- rt_nearest_kernel.h, rt_sweep_kernel.h (in every build) ---- */
+/* the signature is the ray kernels', `front` is not read */
 hipError_t rt_launch_nearest(const rt_nearest_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
+/* the sphere-cast kernel reads the records a nearest-surface launch over the origins, with the radii as limits, left in args->nearest */
+hipError_t rt_launch_sweep(const rt_sweep_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream);
 
 /* ---- rt_winding_kernel.h (in every build) ---- */
 /* the kernel stages nothing in LDS and is the same for every scene placement: no shape */

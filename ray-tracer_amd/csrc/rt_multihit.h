@@ -317,23 +317,6 @@ typedef struct {
     int32_t k;                         /* records per ray, 0 .. RT_MULTIHIT_MAX; 0: count only */
     rt_hit *hits;                      /* n * k records, [ray][rank], 16-byte aligned (not read with k == 0) */
     int32_t *counts;                   /* n, or NULL */
-    /* the second front, the box-overlap kernel (rt_overlap_kernel.h): n boxes; origins .. counts above are not read.  The multi-hit
-     * kernel reads none of these; ray_args_scene leaves them zero */
-    const float *ov_lo, *ov_hi;        /* n x 3 floats each */
-    rt_overlap_id *ov_ids;             /* n * ov_k records, [box][rank], 8-byte aligned (not read with ov_k == 0) */
-    int32_t *ov_counts;                /* n, or NULL */
-    uint8_t *ov_any;                   /* n, or NULL */
-    int32_t ov_k;                      /* ids per box, 0 .. RT_OVERLAP_MAX */
-    int32_t ov_any_only;               /* 1: only ov_any is asked for - a box stops at its first overlapping candidate */
-    /* the third front, the triangle-overlap kernel (rt_tritri_kernel.h): n query triangles; origins .. ov_any_only above are not read.
-     * The other two kernels read none of these; ray_args_scene leaves them zero */
-    const float *ot_tris;              /* n x 9 floats: a0, a1, a2 */
-    rt_overlap_id *ot_ids;             /* n * ot_k records, [query][rank], 8-byte aligned (not read with ot_k == 0) */
-    int32_t *ot_counts;                /* n, or NULL */
-    uint8_t *ot_any;                   /* n, or NULL */
-    rt_tri_segment *ot_segments;       /* n * ot_k records, 16-byte aligned, or NULL */
-    int32_t ot_k;                      /* ids per query, 0 .. RT_OVERLAP_MAX */
-    int32_t ot_any_only;               /* 1: only ot_any is asked for - a query stops at its first overlapping candidate */
 } rt_multihit_args;
 
 /* the second pass (rt_multihit_uv_kernel): the texture coordinates of the records that lie on a sphere whose material needs them */

@@ -36,11 +36,9 @@
 #include "rt_intersect.h"
 #include "rt_launch.h"
 #include "rt_math.h"
-#include "rt_overlap_kernel.h"
 #include "rt_ray_kernel.h"
 #include "rt_surface.h"
 #include "rt_traverse.h"
-#include "rt_tritri_kernel.h"
 #include "rt_vec.h"
 
 #define RT_MULTIHIT_REFILL 16   /* lanes of a wave holding a finished ray before the walk yields to store and refill them (the query kernel's value; not tuned) */
@@ -229,13 +227,10 @@ extern "C" hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *args, int
 }
 
 /* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
-/* rt_ray_kernel.h's table has three fronts per shape for this family: 0 this kernel, 1 the box-overlap kernel (rt_overlap_kernel.h) and
- * 2 the triangle-overlap kernel (rt_tritri_kernel.h), all on the same argument block */
+/* one front: both of rt_ray_launch's tables name the same thirteen kernels */
 struct rt_multihit_kernels {
     typedef rt_multihit_args args;
-    template <int NT, bool HAS_MESH, int MODE, bool FRONT> static constexpr auto kernel = FRONT ? &rt_overlap_kernel<NT, HAS_MESH, MODE> : &rt_multihit_kernel<NT, HAS_MESH, MODE>;
-    typedef void third_front;
-    template <int NT, bool HAS_MESH, int MODE> static constexpr auto third = &rt_tritri_kernel<NT, HAS_MESH, MODE>;
+    template <int NT, bool HAS_MESH, int MODE, bool> static constexpr auto kernel = &rt_multihit_kernel<NT, HAS_MESH, MODE>;
 };
 
 extern "C" hipError_t rt_launch_multihit(const rt_multihit_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)

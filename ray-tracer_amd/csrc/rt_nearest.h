@@ -241,13 +241,6 @@ typedef struct {
     const float *points;               /* n x 3 floats */
     const float *max_dist;             /* n floats, or NULL: unbounded */
     rt_nearest *out;                   /* n records, 16-byte aligned */
-    /* the second front, the sphere-cast kernel (rt_sweep_kernel.h): `points` are the origins, max_dist and out are not read.  The nearest
-     * kernel reads none of these; ray_args_scene leaves them zero */
-    const float *sw_directions;        /* n x 3 floats */
-    const float *sw_radius;            /* n floats */
-    const float *sw_tmax;              /* n floats, or NULL */
-    const rt_nearest *sw_nearest;      /* n records: the nearest-surface answers of the origins under the radii as limits */
-    rt_sweep *sw_out;                  /* n records, 16-byte aligned */
 } rt_nearest_args;
 
 #endif

@@ -25,7 +25,6 @@
 #include "rt_launch.h"
 #include "rt_nearest.h"
 #include "rt_ray_kernel.h"
-#include "rt_sweep_kernel.h"
 #include "rt_traverse.h"
 #include "rt_vec.h"
 
@@ -144,10 +143,10 @@ __global__ __launch_bounds__(NT, 4) void rt_nearest_kernel(const rt_nearest_args
 }
 
 /* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
-/* rt_ray_kernel.h's table has two fronts per shape: 0 this kernel, 1 the sphere-cast kernel (rt_sweep_kernel.h) on the same argument block */
+/* one front: both of rt_ray_launch's tables name the same thirteen kernels */
 struct rt_nearest_kernels {
     typedef rt_nearest_args args;
-    template <int NT, bool HAS_MESH, int MODE, bool FRONT> static constexpr auto kernel = FRONT ? &rt_sweep_kernel<NT, HAS_MESH, MODE> : &rt_nearest_kernel<NT, HAS_MESH, MODE>;
+    template <int NT, bool HAS_MESH, int MODE, bool> static constexpr auto kernel = &rt_nearest_kernel<NT, HAS_MESH, MODE>;
 };
 
 extern "C" hipError_t rt_launch_nearest(const rt_nearest_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)

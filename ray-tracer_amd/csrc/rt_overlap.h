@@ -10,7 +10,8 @@
  *    overlaps too, one node or ONE triangle per step.  The kernel runs one step per lane and round of its wave loop, the host test runs
  *    the same steps in a plain loop.
  *
- * The argument block is rt_multihit.h's rt_multihit_args (its ov_ fields): the kernel is the second front of rt_launch_multihit.
+ *  - the argument block (the launcher is rt_launch.h's rt_launch_overlap).
+ *
  * The definition - every formula in the order it is evaluated, and why compares alone make pruning exact - is include/rt_amd.h's.
  */
 #ifndef RT_OVERLAP_H
@@ -22,7 +23,7 @@
 
 #include "../../include/rt_amd.h"
 #include "rt_device_scene.h"
-#include "rt_multihit.h"        /* rt_multihit_args, RT_MH_MAX_OBJECTS, RT_MH_NO_TRI, RT_MH_UNIFORM */
+#include "rt_multihit.h"        /* RT_MH_MAX_OBJECTS, RT_MH_NO_TRI, RT_MH_UNIFORM */
 
 #if defined(__HIPCC__)
 #define RT_OV_HD __host__ __device__ inline __attribute__((always_inline))
@@ -249,5 +250,27 @@ RT_OV_HD rt_overlap_id rt_ov_id(uint32_t word, bool held)
     r.triangle = held ? rt_ov_word_triangle(word) : -1;
     return r;
 }
+
+/* ---- the argument block ------------------------------------------------------------------------------------------------------- */
+/* The scene and work fields carry the names rt_query_args gives them: rt_internal.h's ray_args_scene fills them, rt_stage_scene reads them. */
+typedef struct {
+    const rt_f4 *blob;
+    int32_t blob_f4;
+    int32_t off_nodes, off_tris, off_objlds, off_meshes, off_objtab;
+    int32_t num_objects, num_meshes;
+    int32_t descend_keep;              /* (not read: the walk has no descend loop of its own) */
+    /* the work: boxes [0, n) in chunks of 64, handed out from `counter` (zeroed before the launch) */
+    uint32_t n, num_chunks;
+    uint32_t *counter;
+    const float *lo, *hi;              /* n x 3 floats each */
+    rt_overlap_id *ids;                /* n * k records, [box][rank], 8-byte aligned (not read with k == 0) */
+    int32_t *counts;                   /* n, or NULL */
+    uint8_t *any;                      /* n, or NULL */
+    int32_t k;                         /* ids per box, 0 .. RT_OVERLAP_MAX */
+    int32_t any_only;                  /* 1: only `any` is asked for - a box stops at its first overlapping candidate */
+} rt_overlap_args;
+
+static_assert(sizeof(rt_overlap_id) == 8, "the kernels store an id as one 8-byte unit");
+static_assert(RT_OVERLAP_MAX == 8, "rt_ov_buf's slots and the kernels' stores are written for eight");
 
 #endif

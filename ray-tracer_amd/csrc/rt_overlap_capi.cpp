@@ -2,8 +2,6 @@
  * rt_overlap_capi.cpp — the box-overlap queries of the C ABI (include/rt_amd.h): argument checks, the launch, the host-buffer form.  The
  * kernel is rt_overlap_kernel.h, the tests, the id buffer and the walk rt_overlap.h; the context and the scene are rt_capi.cpp's, and the
  * checks, the argument block's shared part and the launch (in the context's launch order, between its timing events) are rt_internal.h's.
- *
- * The kernel is the second front of rt_launch_multihit, on rt_multihit_args' ov_ fields: no launcher of its own.
  */
 #include <cstdint>
 
@@ -11,9 +9,6 @@
 #include "rt_overlap.h"
 
 namespace {
-
-static_assert(sizeof(rt_overlap_id) == 8, "rt_overlap_id is one 8-byte unit");
-static_assert(RT_OVERLAP_MAX == 8, "rt_ov_buf's slots and the kernel's stores are written for eight");
 
 /* n boxes on a scene, k ids each and where the answers go (each output may be missing, not all of them) */
 rt_status check_overlap(rt_ctx *ctx, const rt_scene *scene, const void *lo, const void *hi, int64_t n, int32_t k, const void *ids, const void *counts, const void *any)
@@ -39,15 +34,15 @@ extern "C" rt_status rt_overlap_boxes_device(rt_ctx *ctx, const rt_scene *scene,
     if (st != RT_OK) return st;
     if (n == 0) return RT_OK;
     if (k > 0 && ((uintptr_t)d_ids & 7u)) return set_err(ctx, RT_ERR_INVALID, "d_ids must be 8-byte aligned");      /* (device memory: the kernel stores whole records) */
-    rt_multihit_args a = ray_args_scene<rt_multihit_args>(ctx, scene, (uint32_t)n);
-    a.ov_lo = d_lo;
-    a.ov_hi = d_hi;
-    a.ov_ids = k > 0 ? d_ids : nullptr;
-    a.ov_counts = d_counts;
-    a.ov_any = d_any;
-    a.ov_k = k;
-    a.ov_any_only = (k == 0 && !d_counts) ? 1 : 0;
-    return launch_rays(ctx, scene, a, rt_launch_multihit, true, "launching box-overlap kernel", (hipStream_t)hip_stream);
+    rt_overlap_args a = ray_args_scene<rt_overlap_args>(ctx, scene, (uint32_t)n);
+    a.lo = d_lo;
+    a.hi = d_hi;
+    a.ids = k > 0 ? d_ids : nullptr;
+    a.counts = d_counts;
+    a.any = d_any;
+    a.k = k;
+    a.any_only = (k == 0 && !d_counts) ? 1 : 0;
+    return launch_rays(ctx, scene, a, rt_launch_overlap, false, "launching box-overlap kernel", (hipStream_t)hip_stream);
 }
 
 extern "C" rt_status rt_overlap_boxes(rt_ctx *ctx, const rt_scene *scene, const float *lo, const float *hi, int64_t n, int32_t k, rt_overlap_id *ids,

@@ -1,8 +1,8 @@
 /*
  * rt_overlap_kernel.h — box-overlap queries: one box per lane against the scene the render kernel stages, the number of surfaces that
  * touch it, whether any does, and the k lowest of their ids written out.  The tests, the id buffer and the walk of a mesh are
- * rt_overlap.h's (one text for the device and the host tests); the scene staging is rt_traverse.h's; the launcher is
- * rt_multihit_kernel.h's: this kernel is the second front of rt_launch_multihit, on the same argument block (its ov_ fields).
+ * rt_overlap.h's (one text for the device and the host tests); the scene staging is rt_traverse.h's, the launcher at the end
+ * (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_launch.h.
  *
  * What is found is include/rt_amd.h's set: the objects that are not meshes in list order from their LDS records (rt_ov_simple), then
  * every mesh whose root box overlaps the box, walked by compares alone (rt_ov_step).  The order changes nothing of the result - a
@@ -29,6 +29,7 @@
 
 #if RT_RAY_KERNELS_BUILT
 #include "rt_device_scene.h"
+#include "rt_launch.h"
 #include "rt_ray_kernel.h"
 #include "rt_traverse.h"
 #include "rt_vec.h"
@@ -36,7 +37,7 @@
 #define RT_OVERLAP_REFILL 16    /* lanes of a wave holding a finished box before the walk yields to store and refill them (the query kernel's value; not tuned) */
 
 template <int NT, bool HAS_MESH, int MODE>
-__global__ __launch_bounds__(NT, 4) void rt_overlap_kernel(const rt_multihit_args a)
+__global__ __launch_bounds__(NT, 4) void rt_overlap_kernel(const rt_overlap_args a)
 {
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
@@ -49,8 +50,8 @@ __global__ __launch_bounds__(NT, 4) void rt_overlap_kernel(const rt_multihit_arg
     uint32_t *const my_stack = (uint32_t *)(stack + tid);
     rt_ov_scene<v4f> S;
     S.nodes = L.nodes; S.tris = L.tris; S.meshes = L.meshes; S.objtab = L.objtab;
-    const int32_t k = a.ov_k;
-    const bool any_only = a.ov_any_only != 0;
+    const int32_t k = a.k;
+    const bool any_only = a.any_only != 0;
 
     /* per-lane box, buffer and walk */
     int mode = M_FETCH;
@@ -70,12 +71,12 @@ __global__ __launch_bounds__(NT, 4) void rt_overlap_kernel(const rt_multihit_arg
         /* ================= SHADE: the box is finished; its count, its byte, its ids (whole 8-byte records) ============== */
         if (mode == M_SHADE) {
             const uint32_t total = buf.total;
-            int32_t *const counts = a.ov_counts;
+            int32_t *const counts = a.counts;
             if (counts) counts[id] = (int32_t)total;
-            uint8_t *const any = a.ov_any;
+            uint8_t *const any = a.any;
             if (any) any[id] = total > 0u ? (uint8_t)1 : (uint8_t)0;
             if (k > 0) {
-                int2 *const out = (int2 *)a.ov_ids + (size_t)id * (size_t)k;
+                int2 *const out = (int2 *)a.ids + (size_t)id * (size_t)k;
                 /* rank q is slot q: slot 0 is read and the slots move down by one, so that no slot is picked by an index.  One 8-byte
                  * store per id: the paired 16-byte stores an even k allows were tried, and their second loop cost the global-placement
                  * mesh shape two spilled scalar registers */
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(NT, 4) void rt_overlap_kernel(const rt_multihit_arg
                         mode = M_DONE;
                     } else {
                         id = (uint32_t)my_id;
-                        const float *ql = a.ov_lo + 3 * (size_t)id, *qh = a.ov_hi + 3 * (size_t)id;
+                        const float *ql = a.lo + 3 * (size_t)id, *qh = a.hi + 3 * (size_t)id;
                         box.lox = ql[0]; box.loy = ql[1]; box.loz = ql[2];
                         box.hix = qh[0]; box.hiy = qh[1]; box.hiz = qh[2];
                         rt_ov_clear(buf);
@@ -163,6 +164,18 @@ __global__ __launch_bounds__(NT, 4) void rt_overlap_kernel(const rt_multihit_arg
 
         if (__ballot(mode != M_DONE) == 0ull) break;
     }
+}
+
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
+/* one front: both of rt_ray_launch's tables name the same thirteen kernels */
+struct rt_overlap_kernels {
+    typedef rt_overlap_args args;
+    template <int NT, bool HAS_MESH, int MODE, bool> static constexpr auto kernel = &rt_overlap_kernel<NT, HAS_MESH, MODE>;
+};
+
+extern "C" hipError_t rt_launch_overlap(const rt_overlap_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)
+{
+    return rt_ray_launch<rt_overlap_kernels>(args, shape, front, num_cus, lds_bytes, stream);
 }
 #endif
 

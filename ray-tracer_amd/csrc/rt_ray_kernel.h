@@ -1,10 +1,9 @@
 /*
  * rt_ray_kernel.h — the launch path the ray kernels (rt_query_kernel.h: closest hit; rt_occlusion_kernel.h: any hit; rt_ao_kernel.h: the
- * ambient-occlusion plane, one front under both values of `front`; and, with a kernel of another kind as the second front, rt_nearest_kernel.h
- * with the sphere-cast kernel and rt_multihit_kernel.h with the box-overlap kernel and, as a third front, the triangle-overlap kernel) share: one launcher
- * over the kernel (the LDS opt-in, the occupancy cache, the grid sized from the ray count) and one table of its instantiations over
- * RT_SHAPES.  The grid: one wave per 64 rays up to the persistent grid (every
- * CU filled), so a handful of rays stages the scene once, not once per CU.
+ * ambient-occlusion plane; rt_nearest_kernel.h, rt_sweep_kernel.h, rt_multihit_kernel.h, rt_overlap_kernel.h and rt_tritri_kernel.h: the
+ * queries on points, balls, rays, boxes and triangles - like the ambient-occlusion kernel, one front under both values of `front`) share: one launcher over the
+ * kernel (the LDS opt-in, the occupancy cache, the grid sized from the ray count) and one table of its instantiations over RT_SHAPES.  The
+ * grid: one wave per 64 rays up to the persistent grid (every CU filled), so a handful of rays stages the scene once, not once per CU.
  *
  * The kernels' device code (the hand-out of ray ids, the tile slots and primary rays of a view, the MESH and WORK sections) is still stated in
  * each kernel: moved into functions here, or with the two argument blocks on a common base, the register allocation of the mesh shapes changes
@@ -18,7 +17,6 @@
 
 #include <array>
 #include <iterator>
-#include <type_traits>
 #include <utility>
 
 #include "rt_device_scene.h"
@@ -60,17 +58,6 @@ static constexpr std::array<hipError_t (*)(const typename K::args *, int, size_t
     return {{rt_ray_launch_one<K::template kernel<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode, FRONT>, RT_SHAPES[I].threads, typename K::args>...}};
 }
 
-/* A family may declare a third front - a member type third_front and K::third<threads, has_mesh, mode> - and then has a third row; a
- * front that a family lacks is hipErrorInvalidValue.  The tables of a family without one are what they were. */
-template <class K, class = void> struct rt_ray_has_third : std::false_type {};
-template <class K> struct rt_ray_has_third<K, std::void_t<typename K::third_front>> : std::true_type {};
-
-template <class K, size_t... I>
-static constexpr std::array<hipError_t (*)(const typename K::args *, int, size_t, hipStream_t), sizeof...(I)> rt_ray_third_fns_of(std::index_sequence<I...>)
-{
-    return {{rt_ray_launch_one<K::template third<RT_SHAPES[I].threads, RT_SHAPES[I].has_mesh != 0, RT_SHAPES[I].mode>, RT_SHAPES[I].threads, typename K::args>...}};
-}
-
 template <class K>
 static hipError_t rt_ray_launch(const typename K::args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)
 {
@@ -78,13 +65,6 @@ static hipError_t rt_ray_launch(const typename K::args *args, rt_shape shape, in
     static constexpr auto fronted = rt_ray_fns_of<K, true>(std::make_index_sequence<std::size(RT_SHAPES)>());
     const int i = rt_shape_index(shape);
     if (i < 0) return hipErrorInvalidValue;
-    if (front >= 2) {
-        if constexpr (rt_ray_has_third<K>::value) {
-            static constexpr auto third = rt_ray_third_fns_of<K>(std::make_index_sequence<std::size(RT_SHAPES)>());
-            if (front == 2) return third[i](args, num_cus, lds_bytes, stream);
-        }
-        return hipErrorInvalidValue;
-    }
     return (front ? fronted[i] : plain[i])(args, num_cus, lds_bytes, stream);
 }
 

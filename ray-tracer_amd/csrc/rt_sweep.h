@@ -10,7 +10,8 @@
  *    steps in a plain loop;
  *  - nothing is restated: the closest point on a sphere and the candidate comparison are rt_nearest.h's, the slab test rt_multihit.h's.
  *
- * The argument block is rt_nearest_args (rt_nearest.h): the sweep kernel is the second front of rt_launch_nearest.
+ *  - the argument block (the launcher is rt_launch.h's rt_launch_sweep).
+ *
  * The definition - every formula in the order it is evaluated, and why the key makes pruning exact - is include/rt_amd.h's.
  */
 #ifndef RT_SWEEP_H
@@ -308,5 +309,25 @@ RT_SW_HD void rt_sw_record(const rt_nr_scene<F4> &S, const rt_mh_ray &q, float d
     out.triangle = best.k.triangle;
     out.feature = best.feature;
 }
+
+/* ---- the argument block ------------------------------------------------------------------------------------------------------- */
+/* The scene and work fields carry the names rt_query_args gives them: rt_internal.h's ray_args_scene fills them, rt_stage_scene reads them. */
+typedef struct {
+    const rt_f4 *blob;
+    int32_t blob_f4;
+    int32_t off_nodes, off_tris, off_objlds, off_meshes, off_objtab;
+    int32_t num_objects, num_meshes;
+    int32_t descend_keep;              /* (not read: the walk has no descend loop of its own) */
+    /* the work: balls [0, n) in chunks of 64, handed out from `counter` (zeroed before the launch) */
+    uint32_t n, num_chunks;
+    uint32_t *counter;
+    const float *origins, *directions; /* n x 3 floats each */
+    const float *radius;               /* n floats */
+    const float *tmax;                 /* n floats, or NULL */
+    const rt_nearest *nearest;         /* n records: the nearest-surface answers of the origins under the radii as limits */
+    rt_sweep *out;                     /* n records, 16-byte aligned */
+} rt_sweep_args;
+
+static_assert(sizeof(rt_sweep) == 3 * sizeof(rt_f4) && sizeof(rt_nearest) == 2 * sizeof(rt_f4), "the kernel reads and stores the records in 16-byte units");
 
 #endif

@@ -4,7 +4,7 @@
  * shared part and the launch (in the context's launch order, between its timing events) are rt_internal.h's.
  *
  * A call is the nearest-surface launch over the origins with the radii as its limits - which decides, by that query's own definition, which
- * balls touch the scene at the start - and then the sweep kernel, the second front of rt_launch_nearest, which reads those records; both
+ * balls touch the scene at the start - and then the sweep kernel (rt_launch_sweep), which reads those records; both
  * inside one launch bracket, as rt_signed_distance_device chains its two.
  */
 #include <cstdint>
@@ -16,7 +16,6 @@
 namespace {
 
 static_assert(RT_SWEEP_MAX_QUERIES == RT_NEAREST_MAX_POINTS, "check_points serves the sweep too");
-static_assert(sizeof(rt_sweep) == 3 * sizeof(rt_f4) && sizeof(rt_nearest) == 2 * sizeof(rt_f4), "the records in 16-byte units");
 
 /* n balls on a scene and where the answers go (the limits may be missing) */
 rt_status check_sweep(rt_ctx *ctx, const rt_scene *scene, const void *origins, const void *directions, const void *radius, int64_t n, const void *out)
@@ -44,19 +43,18 @@ rt_status sweep_device(rt_ctx *ctx, const rt_scene *scene, const float *d_origin
     na.points = d_origins;
     na.max_dist = d_radius;
     na.out = d_near;
-    rt_nearest_args sa = na;
-    sa.max_dist = nullptr;
-    sa.out = nullptr;
-    sa.sw_directions = d_directions;
-    sa.sw_radius = d_radius;
-    sa.sw_tmax = d_tmax;
-    sa.sw_nearest = d_near;
-    sa.sw_out = d_out;
+    rt_sweep_args sa = ray_args_scene<rt_sweep_args>(ctx, scene, (uint32_t)n);
+    sa.origins = d_origins;
+    sa.directions = d_directions;
+    sa.radius = d_radius;
+    sa.tmax = d_tmax;
+    sa.nearest = d_near;
+    sa.out = d_out;
     return launch_bracket(ctx, stream, [&]() -> rt_status {
         const rt_status queued = enqueue_rays(ctx, scene, na, rt_launch_nearest, false, "clearing the point counter", "launching nearest-surface kernel", stream);
         if (queued != RT_OK) return queued;
         RT_HIP(ctx, hipEventRecord(ctx->ev_start, stream), "recording start event");        /* (again: rt_last_kernel_ms starts at the sweep kernel) */
-        return enqueue_rays(ctx, scene, sa, rt_launch_nearest, true, "clearing the ball counter", "launching sphere-cast kernel", stream);
+        return enqueue_rays(ctx, scene, sa, rt_launch_sweep, false, "clearing the ball counter", "launching sphere-cast kernel", stream);
     });
 }
 

@@ -1,8 +1,8 @@
 /*
  * rt_sweep_kernel.h — sphere-cast queries: one moving ball per lane through the scene the render kernel stages, the time and place of its
  * first contact written out.  The arithmetic and the walk of a mesh are rt_sweep.h's (one text for the device and the host tests); the
- * scene staging is rt_traverse.h's.  The kernel has no launcher of its own: it is the second front of rt_launch_nearest
- * (rt_nearest_kernel.h), on rt_nearest_args, and runs behind the nearest-surface launch whose records it reads.
+ * scene staging is rt_traverse.h's, the launcher at the end (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_launch.h.  The kernel
+ * runs behind the nearest-surface launch whose records it reads (rt_sweep_capi.cpp queues the two).
  *
  * What is found is the minimum of include/rt_amd.h's definition over every candidate of the scene: the objects that are not meshes in
  * list order from their LDS records (rt_sw_simple), then every mesh whose inflated root box the ball's path enters no later than the best
@@ -25,6 +25,8 @@
 
 #include "rt_device_scene.h"
 #include "rt_intersect.h"
+#include "rt_launch.h"
+#include "rt_ray_kernel.h"
 #include "rt_sweep.h"
 #include "rt_traverse.h"
 #include "rt_vec.h"
@@ -32,7 +34,7 @@
 #define RT_SWEEP_REFILL 16      /* lanes of a wave holding a finished ball before the walk yields to store and refill them (the query kernel's value; not tuned) */
 
 template <int NT, bool HAS_MESH, int MODE>
-__global__ __launch_bounds__(NT, 4) void rt_sweep_kernel(const rt_nearest_args a)
+__global__ __launch_bounds__(NT, 4) void rt_sweep_kernel(const rt_sweep_args a)
 {
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
@@ -65,8 +67,8 @@ __global__ __launch_bounds__(NT, 4) void rt_sweep_kernel(const rt_nearest_args a
         /* ================= SHADE: the winner is known; form the record and store it (48 bytes, three 16-byte stores) === */
         if (mode == M_SHADE) {
             rt_sweep rec;
-            rt_sw_record(S, q, dd, r, best, a.sw_nearest + id, rec);
-            v4f *o = (v4f *)a.sw_out + 3 * (size_t)id;
+            rt_sw_record(S, q, dd, r, best, a.nearest + id, rec);
+            v4f *o = (v4f *)a.out + 3 * (size_t)id;
             v4f r0, r1, r2;
             r0.x = rec.t; r0.y = rec.centre[0]; r0.z = rec.centre[1]; r0.w = rec.centre[2];
             r1.x = rec.point[0]; r1.y = rec.point[1]; r1.z = rec.point[2]; r1.w = __int_as_float(rec.object);
@@ -103,15 +105,15 @@ __global__ __launch_bounds__(NT, 4) void rt_sweep_kernel(const rt_nearest_args a
                         mode = M_DONE;
                     } else {
                         id = (uint32_t)my_id;
-                        const float *po = a.points + 3 * (size_t)id, *pd = a.sw_directions + 3 * (size_t)id;
+                        const float *po = a.origins + 3 * (size_t)id, *pd = a.directions + 3 * (size_t)id;
                         q.ox = po[0]; q.oy = po[1]; q.oz = po[2];
                         q.dx = pd[0]; q.dy = pd[1]; q.dz = pd[2];
-                        r = a.sw_radius[id];
-                        const bool has_limit = a.sw_tmax != nullptr;
-                        const float tmax = has_limit ? a.sw_tmax[id] : 0.f;
+                        r = a.radius[id];
+                        const bool has_limit = a.tmax != nullptr;
+                        const float tmax = has_limit ? a.tmax[id] : 0.f;
                         mode = M_SHADE;
                         if (rt_sw_begin(q, r, has_limit, tmax, dd, best)) {
-                            if (a.sw_nearest[id].object >= 0) {
+                            if (a.nearest[id].object >= 0) {
                                 best.k.object = RT_SW_OVERLAP;          /* touching at the start: the record is the nearest one's, nothing is walked */
                             } else {
                                 rt_sw_simple(S, a.num_objects, q, dd, r, best);
@@ -150,6 +152,18 @@ __global__ __launch_bounds__(NT, 4) void rt_sweep_kernel(const rt_nearest_args a
 
         if (__ballot(mode != M_DONE) == 0ull) break;
     }
+}
+
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
+/* one front: both of rt_ray_launch's tables name the same thirteen kernels */
+struct rt_sweep_kernels {
+    typedef rt_sweep_args args;
+    template <int NT, bool HAS_MESH, int MODE, bool> static constexpr auto kernel = &rt_sweep_kernel<NT, HAS_MESH, MODE>;
+};
+
+extern "C" hipError_t rt_launch_sweep(const rt_sweep_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)
+{
+    return rt_ray_launch<rt_sweep_kernels>(args, shape, front, num_cus, lds_bytes, stream);
 }
 
 #endif

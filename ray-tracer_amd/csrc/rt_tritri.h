@@ -9,7 +9,8 @@
  *  - the traversal of one mesh as steps over rt_overlap.h's state (rt_ov_walk): rt_ov_step with another leaf test.  The path rule is
  *    rt_ov_boxes as it stands, on the query's bounding box; the ids are kept by rt_ov_insert in an rt_ov_buf.
  *
- * The argument block is rt_multihit.h's rt_multihit_args (its ot_ fields): the kernel is the third front of rt_launch_multihit.
+ *  - the argument block (the launcher is rt_launch.h's rt_launch_tritri).
+ *
  * The definition - every formula in the order it is evaluated - is include/rt_amd.h's.
  */
 #ifndef RT_TRITRI_H
@@ -21,7 +22,7 @@
 
 #include "../../include/rt_amd.h"
 #include "rt_device_scene.h"
-#include "rt_multihit.h"        /* rt_multihit_args, RT_MH_MAX_OBJECTS, RT_MH_NO_TRI, RT_MH_UNIFORM */
+#include "rt_multihit.h"        /* RT_MH_MAX_OBJECTS, RT_MH_NO_TRI, RT_MH_UNIFORM */
 #include "rt_nearest.h"         /* rt_nr_tri: the point-triangle distance of the sphere test */
 #include "rt_overlap.h"         /* rt_ov_box, rt_ov_boxes, rt_ov_buf, rt_ov_offer, rt_ov_walk */
 
@@ -302,5 +303,27 @@ RT_OV_HD rt_tri_segment rt_tt_segment(const rt_ov_scene<F4> &S, uint32_t word, b
     }
     return seg;
 }
+
+/* ---- the argument block ------------------------------------------------------------------------------------------------------- */
+/* The scene and work fields carry the names rt_query_args gives them: rt_internal.h's ray_args_scene fills them, rt_stage_scene reads them. */
+typedef struct {
+    const rt_f4 *blob;
+    int32_t blob_f4;
+    int32_t off_nodes, off_tris, off_objlds, off_meshes, off_objtab;
+    int32_t num_objects, num_meshes;
+    int32_t descend_keep;              /* (not read: the walk has no descend loop of its own) */
+    /* the work: query triangles [0, n) in chunks of 64, handed out from `counter` (zeroed before the launch) */
+    uint32_t n, num_chunks;
+    uint32_t *counter;
+    const float *tris;                 /* n x 9 floats: a0, a1, a2 */
+    rt_overlap_id *ids;                /* n * k records, [query][rank], 8-byte aligned (not read with k == 0) */
+    int32_t *counts;                   /* n, or NULL */
+    uint8_t *any;                      /* n, or NULL */
+    rt_tri_segment *segments;          /* n * k records, 16-byte aligned, or NULL */
+    int32_t k;                         /* ids per query, 0 .. RT_OVERLAP_MAX */
+    int32_t any_only;                  /* 1: only `any` is asked for - a query stops at its first overlapping candidate */
+} rt_tritri_args;
+
+static_assert(sizeof(rt_tri_segment) == 32, "the kernel stores a segment as two 16-byte units");
 
 #endif

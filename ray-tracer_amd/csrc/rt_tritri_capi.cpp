@@ -3,8 +3,6 @@
  * The kernel is rt_tritri_kernel.h, the tests and the walk rt_tritri.h, the id buffer rt_overlap.h; the context and the scene are
  * rt_capi.cpp's, and the checks, the argument block's shared part and the launch (in the context's launch order, between its timing
  * events) are rt_internal.h's.
- *
- * The kernel is the third front of rt_launch_multihit, on rt_multihit_args' ot_ fields: no launcher of its own.
  */
 #include <cstdint>
 
@@ -12,9 +10,6 @@
 #include "rt_tritri.h"
 
 namespace {
-
-static_assert(sizeof(rt_tri_segment) == 32, "rt_tri_segment is two 16-byte units");
-static_assert(RT_OVERLAP_MAX == 8, "rt_ov_buf's slots and the kernel's stores are written for eight");
 
 /* n query triangles on a scene, k ids each and where the answers go (each output may be missing, not all of them) */
 rt_status check_tritri(rt_ctx *ctx, const rt_scene *scene, const void *tris, int64_t n, int32_t k, const void *ids, const void *counts, const void *any, const void *segments)
@@ -42,15 +37,15 @@ extern "C" rt_status rt_overlap_triangles_device(rt_ctx *ctx, const rt_scene *sc
     if (n == 0) return RT_OK;
     if (k > 0 && ((uintptr_t)d_ids & 7u)) return set_err(ctx, RT_ERR_INVALID, "d_ids must be 8-byte aligned");      /* (device memory: the kernel stores whole records) */
     if ((uintptr_t)d_segments & 15u) return set_err(ctx, RT_ERR_INVALID, "d_segments must be 16-byte aligned");
-    rt_multihit_args a = ray_args_scene<rt_multihit_args>(ctx, scene, (uint32_t)n);
-    a.ot_tris = d_tris;
-    a.ot_ids = k > 0 ? d_ids : nullptr;
-    a.ot_counts = d_counts;
-    a.ot_any = d_any;
-    a.ot_segments = d_segments;
-    a.ot_k = k;
-    a.ot_any_only = (k == 0 && !d_counts) ? 1 : 0;
-    return launch_rays(ctx, scene, a, rt_launch_multihit, 2, "launching triangle-overlap kernel", (hipStream_t)hip_stream);
+    rt_tritri_args a = ray_args_scene<rt_tritri_args>(ctx, scene, (uint32_t)n);
+    a.tris = d_tris;
+    a.ids = k > 0 ? d_ids : nullptr;
+    a.counts = d_counts;
+    a.any = d_any;
+    a.segments = d_segments;
+    a.k = k;
+    a.any_only = (k == 0 && !d_counts) ? 1 : 0;
+    return launch_rays(ctx, scene, a, rt_launch_tritri, false, "launching triangle-overlap kernel", (hipStream_t)hip_stream);
 }
 
 extern "C" rt_status rt_overlap_triangles(rt_ctx *ctx, const rt_scene *scene, const float *tris, int64_t n, int32_t k, rt_overlap_id *ids, int32_t *counts,

@@ -2,8 +2,7 @@
  * rt_tritri_kernel.h — triangle-overlap queries: one query triangle per lane against the scene the render kernel stages, the number of
  * surfaces it cuts, whether it cuts any, the k lowest of their ids and, where asked, each pair's segment written out.  The tests and
  * the walk of a mesh are rt_tritri.h's, the id buffer rt_overlap.h's (one text for the device and the host tests); the scene staging is
- * rt_traverse.h's; the launcher is rt_multihit_kernel.h's: this kernel is the third front of rt_launch_multihit, on the same argument
- * block (its ot_ fields).
+ * rt_traverse.h's, the launcher at the end (rt_ray_kernel.h's table over RT_SHAPES) is declared in rt_launch.h.
  *
  * It is the box-overlap kernel's state machine (rt_overlap_kernel.h has the account: FETCH -> MESH -> WAIT -> SHADE, the chunked refill,
  * one node or ONE triangle per step) with another leaf test.  A lane keeps a0..a2, na, lo, hi, the count, eight ids and the walk.
@@ -23,6 +22,7 @@
 
 #if RT_RAY_KERNELS_BUILT
 #include "rt_device_scene.h"
+#include "rt_launch.h"
 #include "rt_ray_kernel.h"
 #include "rt_traverse.h"
 #include "rt_vec.h"
@@ -30,7 +30,7 @@
 #define RT_TRITRI_REFILL 16     /* lanes of a wave holding a finished query before the walk yields to store and refill them (the query kernel's value; not tuned) */
 
 template <int NT, bool HAS_MESH, int MODE>
-__global__ __launch_bounds__(NT, 4) void rt_tritri_kernel(const rt_multihit_args a)
+__global__ __launch_bounds__(NT, 4) void rt_tritri_kernel(const rt_tritri_args a)
 {
     extern __shared__ v4f lds_raw[];
     const int tid = threadIdx.x;
@@ -43,8 +43,8 @@ __global__ __launch_bounds__(NT, 4) void rt_tritri_kernel(const rt_multihit_args
     uint32_t *const my_stack = (uint32_t *)(stack + tid);
     rt_ov_scene<v4f> S;
     S.nodes = L.nodes; S.tris = L.tris; S.meshes = L.meshes; S.objtab = L.objtab;
-    const int32_t k = a.ot_k;
-    const bool any_only = a.ot_any_only != 0;
+    const int32_t k = a.k;
+    const bool any_only = a.any_only != 0;
 
     /* per-lane query, buffer and walk */
     int mode = M_FETCH;
@@ -65,13 +65,13 @@ __global__ __launch_bounds__(NT, 4) void rt_tritri_kernel(const rt_multihit_args
         /* ================= SHADE: the query is finished; its count, its byte, its ids (8-byte records), its segments (two 16-byte stores) ==== */
         if (mode == M_SHADE) {
             const uint32_t total = buf.total;
-            int32_t *const counts = a.ot_counts;
+            int32_t *const counts = a.counts;
             if (counts) counts[id] = (int32_t)total;
-            uint8_t *const any = a.ot_any;
+            uint8_t *const any = a.any;
             if (any) any[id] = total > 0u ? (uint8_t)1 : (uint8_t)0;
             if (k > 0) {
-                int2 *const out = (int2 *)a.ot_ids + (size_t)id * (size_t)k;
-                v4f *const segs = a.ot_segments ? (v4f *)a.ot_segments + 2 * ((size_t)id * (size_t)k) : nullptr;
+                int2 *const out = (int2 *)a.ids + (size_t)id * (size_t)k;
+                v4f *const segs = a.segments ? (v4f *)a.segments + 2 * ((size_t)id * (size_t)k) : nullptr;
                 /* rank q is slot q: slot 0 is read and the slots move down by one, so that no slot is picked by an index */
 #pragma unroll 1
                 for (int32_t q = 0; q < k; q++) {
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(NT, 4) void rt_tritri_kernel(const rt_multihit_args
                         mode = M_DONE;
                     } else {
                         id = (uint32_t)my_id;
-                        const float *qt = a.ot_tris + 9 * (size_t)id;
+                        const float *qt = a.tris + 9 * (size_t)id;
                         t.a0x = qt[0]; t.a0y = qt[1]; t.a0z = qt[2];
                         t.a1x = qt[3]; t.a1y = qt[4]; t.a1z = qt[5];
                         t.a2x = qt[6]; t.a2y = qt[7]; t.a2z = qt[8];
@@ -167,6 +167,18 @@ __global__ __launch_bounds__(NT, 4) void rt_tritri_kernel(const rt_multihit_args
 
         if (__ballot(mode != M_DONE) == 0ull) break;
     }
+}
+
+/* ---- launcher (rt_launch.h) ----------------------------------------------------------------- */
+/* one front: both of rt_ray_launch's tables name the same thirteen kernels */
+struct rt_tritri_kernels {
+    typedef rt_tritri_args args;
+    template <int NT, bool HAS_MESH, int MODE, bool> static constexpr auto kernel = &rt_tritri_kernel<NT, HAS_MESH, MODE>;
+};
+
+extern "C" hipError_t rt_launch_tritri(const rt_tritri_args *args, rt_shape shape, int front, int num_cus, size_t lds_bytes, hipStream_t stream)
+{
+    return rt_ray_launch<rt_tritri_kernels>(args, shape, front, num_cus, lds_bytes, stream);
 }
 #endif
 

@@ -4,7 +4,7 @@
 // a link error and one whose signature differs from rt_launch.h does not compile, as with the stubs; tests/test_launch_order.py checks
 // that this file defines every launcher once.  The sizes restate what the kernels index (rt_render_kernel.h, rt_frame_kernels.h,
 // rt_query_kernel.h, rt_occlusion_kernel.h, rt_ao_kernel.h, rt_multihit_kernel.h, rt_denoise_kernel.h, rt_adaptive_kernel.h,
-// rt_rebuild_kernel.h, rt_cull_kernel.h, rt_nearest_kernel.h, rt_winding_kernel.h); the checker also refuses a range that leaves its
+// rt_rebuild_kernel.h, rt_cull_kernel.h, rt_nearest_kernel.h, rt_sweep_kernel.h, rt_overlap_kernel.h, rt_tritri_kernel.h, rt_winding_kernel.h); the checker also refuses a range that leaves its
 // allocation.  Included by one translation unit.
 #pragma once
 
@@ -153,6 +153,24 @@ hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *a, int, hipStream_t 
     // (a record names its object: the shading records are read up to the scene's last, which is as far as the blob goes for this block)
     return rec::launch("multi-hit uv", stream, {{a->objlds, rec::extent(a->objlds), R, "scene blob"}, {a->hits, (size_t)a->records * sizeof(rt_hit), W, "multi-hit records"}});
 }
+hipError_t rt_launch_overlap(const rt_overlap_args *a, rt_shape, int, int, size_t, hipStream_t stream)
+{
+    using namespace rec_detail;
+    const size_t n = a->n, k = (size_t)a->k;
+    return rec::launch("box overlap", stream, {{a->counter, COUNTER_BYTES, W, "ticket counter"}, {a->blob, (size_t)a->blob_f4 * 16, R, "scene blob"},
+                                               {a->lo, n * 12, R, "lower corners"}, {a->hi, n * 12, R, "upper corners"},
+                                               {k > 0 ? a->ids : nullptr, n * k * sizeof(rt_overlap_id), W, "overlap ids"}, {a->counts, n * 4, W, "overlap counts"},
+                                               {a->any, n, W, "overlap bytes"}});
+}
+hipError_t rt_launch_tritri(const rt_tritri_args *a, rt_shape, int, int, size_t, hipStream_t stream)
+{
+    using namespace rec_detail;
+    const size_t n = a->n, k = (size_t)a->k;
+    return rec::launch("triangle overlap", stream, {{a->counter, COUNTER_BYTES, W, "ticket counter"}, {a->blob, (size_t)a->blob_f4 * 16, R, "scene blob"},
+                                                    {a->tris, n * 36, R, "query triangles"}, {k > 0 ? a->ids : nullptr, n * k * sizeof(rt_overlap_id), W, "overlap ids"},
+                                                    {a->counts, n * 4, W, "overlap counts"}, {a->any, n, W, "overlap bytes"},
+                                                    {k > 0 ? a->segments : nullptr, n * k * sizeof(rt_tri_segment), W, "overlap segments"}});
+}
 hipError_t rt_launch_denoise_pack(const rt_denoise_args *a, hipStream_t stream)
 {
     using namespace rec_detail;
@@ -218,6 +236,14 @@ hipError_t rt_launch_nearest(const rt_nearest_args *a, rt_shape, int, int, size_
     const size_t n = a->n;
     return rec::launch("nearest", stream, {{a->counter, COUNTER_BYTES, W, "ticket counter"}, {a->blob, (size_t)a->blob_f4 * 16, R, "scene blob"}, {a->points, n * 12, R, "points"},
                                            {a->max_dist, n * 4, R, "limits"}, {a->out, n * sizeof(rt_nearest), W, "nearest records"}});
+}
+hipError_t rt_launch_sweep(const rt_sweep_args *a, rt_shape, int, int, size_t, hipStream_t stream)
+{
+    using namespace rec_detail;
+    const size_t n = a->n;
+    return rec::launch("sphere cast", stream, {{a->counter, COUNTER_BYTES, W, "ticket counter"}, {a->blob, (size_t)a->blob_f4 * 16, R, "scene blob"}, {a->origins, n * 12, R, "origins"},
+                                               {a->directions, n * 12, R, "directions"}, {a->radius, n * 4, R, "radii"}, {a->tmax, n * 4, R, "limits"},
+                                               {a->nearest, n * sizeof(rt_nearest), R, "sweep start records"}, {a->out, n * sizeof(rt_sweep), W, "sweep records"}});
 }
 hipError_t rt_launch_winding(const rt_winding_args *a, int, hipStream_t stream)
 {

@@ -24,6 +24,8 @@ hipError_t rt_launch_occlusion(const rt_occlusion_args *, rt_shape, int, int, si
 hipError_t rt_launch_ao(const rt_ao_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_multihit(const rt_multihit_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_multihit_uv(const rt_multihit_uv_args *, int, hipStream_t) { g_launches++; return hipErrorUnknown; }
+hipError_t rt_launch_overlap(const rt_overlap_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
+hipError_t rt_launch_tritri(const rt_tritri_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_denoise_pack(const rt_denoise_args *, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_denoise_level(const rt_denoise_args *, int, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_adaptive_plan(const rt_plan_args *, hipStream_t) { g_launches++; return hipErrorUnknown; }
@@ -31,6 +33,7 @@ hipError_t rt_launch_adaptive_combine(const float *, const float *, const uint32
 hipError_t rt_launch_rebuild(const rt_rebuild_args *, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_cull(const float *, int32_t, int32_t, int32_t, const rt_f4 *, int32_t, int32_t, int32_t, int32_t, uint32_t *, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_nearest(const rt_nearest_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
+hipError_t rt_launch_sweep(const rt_sweep_args *, rt_shape, int, int, size_t, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_winding(const rt_winding_args *, int, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_eval(int, const uint32_t *, uint32_t *, int, hipStream_t) { g_launches++; return hipErrorUnknown; }
 hipError_t rt_launch_exhaustive(unsigned long long *, hipStream_t) { g_launches++; return hipErrorUnknown; }

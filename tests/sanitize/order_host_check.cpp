@@ -423,10 +423,13 @@ template <class T> T *caller_alloc(size_t n)
 // the buffers of a caller who works on one stream: whatever touches them is ordered through that stream
 struct CallerBuffers {
     float *frame, *prev, *frames, *compact, *origins, *directions, *tmax, *depth, *normal, *albedo, *ray, *ao, *tile_error, *half_a, *half_b, *denoised;
-    float *triangles, *winding, *sdf;
+    float *triangles, *winding, *sdf, *radius, *query_tris;
     int32_t *object, *counts;
     rt_hit *hits, *multi_hits;
     rt_nearest *nearest;
+    rt_sweep *sweeps;
+    rt_overlap_id *ids;           // MAX_MULTI queries of an overlap call, RT_OVERLAP_MAX ids (and segments) each
+    rt_tri_segment *segments;
     unsigned char *spare;         // where the caller copies an answer to (as large as the largest: the multi-hit records)
     uint8_t *occluded, *visibility, *rgba, *inside;
     uint16_t *ao_count, *budget;
@@ -439,7 +442,10 @@ struct CallerBuffers {
         origins = f(3 * MAX_RAYS); directions = f(3 * MAX_RAYS); tmax = f(MAX_RAYS);
         depth = f(MAX_PX); normal = f(3 * MAX_PX); albedo = f(3 * MAX_PX); ray = f(3 * MAX_PX); ao = f(MAX_PX); tile_error = f(MAX_PX / 64 + 64);
         half_a = f(3 * MAX_PX); half_b = f(3 * MAX_PX); denoised = f(3 * MAX_PX);
-        triangles = f(9 * MESH_TRIS); winding = f(MAX_RAYS); sdf = f(MAX_RAYS);
+        triangles = f(9 * MESH_TRIS); winding = f(MAX_RAYS); sdf = f(MAX_RAYS); radius = f(MAX_RAYS); query_tris = f(9 * MAX_MULTI);
+        sweeps = caller_alloc<rt_sweep>(MAX_RAYS); ids = caller_alloc<rt_overlap_id>((size_t)MAX_MULTI * RT_OVERLAP_MAX);
+        segments = caller_alloc<rt_tri_segment>((size_t)MAX_MULTI * RT_OVERLAP_MAX);
+        for (void *p : {(void *)sweeps, (void *)ids, (void *)segments}) all.push_back(p);
         counts = caller_alloc<int32_t>(MAX_RAYS); multi_hits = caller_alloc<rt_hit>((size_t)MAX_MULTI * RT_MULTIHIT_MAX); nearest = caller_alloc<rt_nearest>(MAX_RAYS);
         spare = caller_alloc<unsigned char>((size_t)MAX_MULTI * RT_MULTIHIT_MAX * sizeof(rt_hit)); inside = caller_alloc<uint8_t>(MAX_RAYS);
         for (void *p : {(void *)counts, (void *)multi_hits, (void *)nearest, (void *)spare, (void *)inside}) all.push_back(p);
@@ -714,6 +720,42 @@ struct World {
         caller_reads(c, b.sdf, (size_t)n * 4);
         if (own_records) caller_reads(c, b.nearest, (size_t)n * sizeof(rt_nearest));
     }
+    // the nearest-surface records between the two launches are the context's, as in signed_distance without own_records
+    void sweep_spheres(const Shape &c, int n, bool limits)
+    {
+        g_call = "rt_sweep_spheres_device";
+        CallerBuffers &b = bufs[c.s];
+        caller_writes(c, b.origins, (size_t)n * 12);
+        caller_writes(c, b.radius, (size_t)n * 4);
+        expect_ok(rt_sweep_spheres_device(ctx[c.k], scene_of(c), b.origins, b.directions, b.radius, limits ? b.tmax : nullptr, n, b.sweeps, streams[c.s]), c);
+        caller_reads(c, b.sweeps, (size_t)n * sizeof(rt_sweep));
+    }
+    // outputs: 1 the counts, 2 the bytes; k == 0 with the bytes alone is the kernels' any-only mode
+    void overlap_boxes(const Shape &c, int n, int k, int outputs)
+    {
+        g_call = "rt_overlap_boxes_device";
+        CallerBuffers &b = bufs[c.s];
+        caller_writes(c, b.origins, (size_t)n * 12);
+        caller_writes(c, b.directions, (size_t)n * 12);
+        expect_ok(rt_overlap_boxes_device(ctx[c.k], scene_of(c), b.origins, b.directions, n, k, k > 0 ? b.ids : nullptr, outputs & 1 ? b.counts : nullptr,
+                                          outputs & 2 ? b.inside : nullptr, streams[c.s]), c);
+        if (k > 0) caller_reads(c, b.ids, (size_t)n * (size_t)k * sizeof(rt_overlap_id));
+        if (outputs & 1) caller_reads(c, b.counts, (size_t)n * 4);
+        if (outputs & 2) caller_reads(c, b.inside, (size_t)n);
+    }
+    void overlap_triangles(const Shape &c, int n, int k, int outputs, bool with_segments)
+    {
+        g_call = "rt_overlap_triangles_device";
+        CallerBuffers &b = bufs[c.s];
+        const bool segs = with_segments && k > 0;
+        caller_writes(c, b.query_tris, (size_t)n * 36);
+        expect_ok(rt_overlap_triangles_device(ctx[c.k], scene_of(c), b.query_tris, n, k, k > 0 ? b.ids : nullptr, outputs & 1 ? b.counts : nullptr,
+                                              outputs & 2 ? b.inside : nullptr, segs ? b.segments : nullptr, streams[c.s]), c);
+        if (k > 0) caller_reads(c, b.ids, (size_t)n * (size_t)k * sizeof(rt_overlap_id));
+        if (segs) caller_reads(c, b.segments, (size_t)n * (size_t)k * sizeof(rt_tri_segment));
+        if (outputs & 1) caller_reads(c, b.counts, (size_t)n * 4);
+        if (outputs & 2) caller_reads(c, b.inside, (size_t)n);
+    }
     void render_aov(const Shape &c)
     {
         g_call = "rt_render_aov_device";
@@ -859,7 +901,7 @@ struct World {
         const int32_t t1[1] = {1};
         rt_status st = RT_OK;
         g_call = "a refused call";
-        switch (pick(0, 17)) {
+        switch (pick(0, 20)) {
             case 0: st = rt_render_device(x, scene_of(c), &bad, &rs, 1, 0, nullptr, nullptr, b.frame, streams[c.s]); break;
             case 1: st = rt_render_device(x, other, &cam, &rs, 1, 0, nullptr, nullptr, b.frame, streams[c.s]); break;
             case 2: st = rt_render_device_batch(x, scene_of(c), &cam, &rs, t1, 33, 0, nullptr, b.frame, streams[c.s]); break;
@@ -877,6 +919,9 @@ struct World {
             case 14: st = rt_trace_rays_multi_device(x, scene_of(c), b.origins, b.directions, nullptr, 5, RT_MULTIHIT_MAX + 1, b.multi_hits, b.counts, streams[c.s]); break;
             case 15: st = rt_winding_numbers_device(x, scene_of(c), b.origins, 5, 99, b.winding, nullptr, streams[c.s]); break;
             case 16: st = rt_signed_distance_device(x, scene_of(c), b.origins, nullptr, 5, (rt_nearest *)((char *)b.nearest + 8), b.sdf, streams[c.s]); break;
+            case 17: st = rt_sweep_spheres_device(x, scene_of(c), b.origins, b.directions, nullptr, nullptr, 5, b.sweeps, streams[c.s]); break;
+            case 18: st = rt_overlap_boxes_device(x, scene_of(c), b.origins, b.directions, 5, 0, nullptr, nullptr, nullptr, streams[c.s]); break;
+            case 19: st = rt_overlap_triangles_device(x, scene_of(c), b.query_tris, 5, 0, nullptr, b.counts, nullptr, b.segments, streams[c.s]); break;
             default: st = rt_tiles_copy_device(x, b.compact, b.frame, c.w, c.h, nullptr, 3, 1, streams[c.s]); break;
         }
         refused++;
@@ -906,6 +951,12 @@ struct World {
             adaptive_plan(a); render_budget(b, -1, false);
             nearest_points(a, 900, true); trace_multi(b, m, 500, 3, true);                           // the ticket counter again, through the later families
             trace_multi(a, 2, MAX_MULTI, RT_MULTIHIT_MAX, false); trace_multi(b, 2, 200, 0, true); winding_numbers(a, 700, true, 3);
+            // a sweep behind and ahead of a nearest-surface call on its stream, and of a signed-distance call on the other one: the sweep's two
+            // launches and the signed distance's two hand their records on through the context's one buffer, which the growing counts regrow
+            nearest_points(a, 300, true); sweep_spheres(a, 300, true); nearest_points(a, 350, false);
+            signed_distance(b, 400, false, true); sweep_spheres(a, 500, false); signed_distance(b, 450, false, false);
+            overlap_boxes(b, 300, 0, 2); overlap_boxes(a, MAX_MULTI, RT_OVERLAP_MAX, 3);             // (k == 0 and the bytes alone: any-only)
+            overlap_triangles(b, 200, 4, 1, true); overlap_triangles(a, 100, 0, 2, false); sweep_spheres(b, 64, true);
             signed_distance(b, 600, false, true); signed_distance(a, MAX_RAYS, false, false);        // the context's records, regrown under the pending pair
             signed_distance(b, 100, true, true); winding_numbers(b, 50, false, 2);
             render_sky(a, 3, true, 0.0f); render_sky(b, 2, false, 0.5f); render_views(a, 2, false, 0.0f);
@@ -924,6 +975,7 @@ struct World {
             const Shape third = shape(0, 3, mm);
             trace_rays(third, 500); denoise(third, false); render_budget(third, 0, true); render_views(third, 2, true, 0.0f); render_ao(third);
             update_mesh(third); signed_distance(third, 2000, false, false); trace_multi(third, 2, 64, 2, true); render_sky(third, 2, true, 0.0f);
+            sweep_spheres(third, 700, true); overlap_boxes(third, 65, 2, 0); overlap_triangles(third, 129, RT_OVERLAP_MAX, 3, true);
             REQUIRE(frame_collect(0, 1, false) && frame_collect(0, 1, false));
             REQUIRE(frame_submit(a, 4));
             render_device(shape(0, 2, mm, 40, 24), 0, 40);                                           // another view while a frame is in flight
@@ -945,7 +997,7 @@ struct World {
             const int z = pick(0, 4);
             const Shape c = shape(pick(0, n_ctx - 1), pick(0, n_streams - 1), pick(0, 1) != 0, sizes[z][0], sizes[z][1]);
             const int spp = pick(0, 9) == 0 ? 40 : pick(1, 4);
-            switch (pick(0, 29)) {
+            switch (pick(0, 32)) {
                 case 0: case 1: render_device(c, pick(0, 6), spp); break;
                 case 2: render_batch(c, pick(0, 1) ? 0 : pick(2, 6), spp); break;
                 case 3: case 4: frame_submit(shape(c.k, c.s, c.mesh), spp); break;      // (one image size: the view stays, so frames overlap)
@@ -969,7 +1021,10 @@ struct World {
                 case 25: trace_multi(c, pick(0, 2), pick(1, MAX_MULTI), pick(0, 2) == 0 ? 0 : pick(1, RT_MULTIHIT_MAX), pick(0, 1) != 0); break;
                 case 26: winding_numbers(c, pick(1, MAX_RAYS), pick(0, 1) != 0, pick(1, 3)); break;
                 case 27: signed_distance(c, pick(1, MAX_RAYS), pick(0, 1) != 0, pick(0, 1) != 0); break;
-                case 28:
+                case 28: sweep_spheres(c, pick(1, MAX_RAYS), pick(0, 1) != 0); break;
+                case 29: { const int k = pick(0, 2) == 0 ? 0 : pick(1, RT_OVERLAP_MAX); overlap_boxes(c, pick(1, MAX_MULTI), k, k > 0 ? pick(0, 3) : pick(1, 3)); break; }
+                case 30: { const int k = pick(0, 2) == 0 ? 0 : pick(1, RT_OVERLAP_MAX); overlap_triangles(c, pick(1, MAX_MULTI), k, k > 0 ? pick(0, 3) : pick(1, 3), pick(0, 1) != 0); break; }
+                case 31:
                     g_call = "(the caller waits for its stream)";
                     REQUIRE(hipStreamSynchronize(streams[c.s]) == hipSuccess);
                     break;

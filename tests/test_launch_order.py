@@ -14,7 +14,7 @@ from test_launch_seam import DECLARED, DEFINITION, _names
 
 SOURCES = ["rt_capi.cpp", "rt_pipeline_capi.cpp", "rt_query_capi.cpp", "rt_occlusion_capi.cpp", "rt_ao_capi.cpp", "rt_denoise_capi.cpp",
            "rt_adaptive_capi.cpp", "rt_views_capi.cpp", "rt_host.cpp", "rt_multi_capi.cpp", "rt_sky_capi.cpp", "rt_update_capi.cpp", "rt_nearest_capi.cpp",
-           "rt_multihit_capi.cpp", "rt_winding_capi.cpp"]
+           "rt_multihit_capi.cpp", "rt_winding_capi.cpp", "rt_sweep_capi.cpp", "rt_overlap_capi.cpp", "rt_tritri_capi.cpp"]
 SEEDS = (1, 2, 3)
 ITERATIONS = 4000
 
@@ -51,5 +51,6 @@ def test_the_checker_finds_missing_waits(objects, tmp_path):
     assert "ticket counter" in r.stderr and "is not ordered behind" in r.stderr, r.stderr[-3000:]
     # ... and what the later families share: the view's cull plane, a scene's blob under an update, the context's query records (the program
     # prints the first violation of every buffer, so these are not lost behind the first twelve)
-    for kernel, buffer in (("cull pre-pass", "cull plane"), ("rebuild", "scene blob"), ("nearest", "nearest records")):
+    for kernel, buffer in (("cull pre-pass", "cull plane"), ("rebuild", "scene blob"), ("nearest", "nearest records"),
+                           ("sphere cast", "sweep start records")):
         assert re.search(r"order violation: \w+ of %s \[\d+, \d+\) by %s in " % (buffer, kernel), r.stderr), (buffer, r.stderr[-3000:])

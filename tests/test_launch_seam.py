@@ -56,7 +56,8 @@ def test_every_launcher_is_defined_once_in_the_kernel_headers():
     # the development builds' fallbacks: ray-kernel launchers that the header declares, and behind its include
     ray = _text(os.path.join(CSRC, "rt_ray_kernels.h"))
     fallbacks = [m.group(1) for m in DEFINITION.finditer(ray)]
-    assert sorted(fallbacks) == ["rt_launch_ao", "rt_launch_multihit", "rt_launch_multihit_uv", "rt_launch_occlusion", "rt_launch_query"], fallbacks
+    assert sorted(fallbacks) == ["rt_launch_ao", "rt_launch_multihit", "rt_launch_multihit_uv", "rt_launch_occlusion", "rt_launch_overlap", "rt_launch_query",
+                                 "rt_launch_tritri"], fallbacks
     assert ray.index('#include "rt_launch.h"') < DEFINITION.search(ray).start()
 
 
