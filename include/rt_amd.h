@@ -1233,6 +1233,16 @@ rt_status rt_debug_subtree_cull(rt_ctx *ctx, uint32_t *words, int32_t capacity_w
  * the unflagged pixels whose jitter cone may enter the root box, their centre ray walked in the kernel's order: {those pixels, its node steps
  * ungated, its node steps with the pixel's word, pixels whose word is not 0} */
 rt_status rt_debug_subtree_cull_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats4);
+/* The primary entry word (rt_entry.h): behind the gate words each pixel of the view has a third word that says where its primary rays end in the
+ * scene's one mesh - T << 1 | 1: every one of them ends on triangle T, and the kernel above starts it there; 2: none hits a triangle, and the pixel is
+ * treated as a flagged one; 0: not known.  RT_AMD_PRIMARY_ENTRY=0 (read by rt_ctx_create) writes every word as 0.  Frames are bit-identical either way.
+ * rt_debug_primary_entry: the words the context's last render launch was handed, read back (waits for the device); info4 and the layout as
+ * rt_debug_subtree_cull's. */
+rt_status rt_debug_primary_entry(rt_ctx *ctx, uint32_t *words, int32_t capacity_words, int32_t *info4);
+/* the same words computed on the HOST (no device is touched) from a flattened scene.  words: width * height of them, or NULL.  stats12, or NULL, over
+ * the unflagged pixels whose jitter cone may enter the root box, by class of their word - `triangle`, `nothing`, 0: {pixels x 3, the centre ray's node
+ * steps x 3, its triangle tests x 3}, walked in the kernel's order with the pixel's gate word, then {triangles the predicate looked at, 0, 0} */
+rt_status rt_debug_primary_entry_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats12);
 /* evaluates one function of the shared math / RNG headers ON THE DEVICE, element-wise, on raw
  * 32-bit patterns (host pointers).  op: 0 rt_logf, 1 rt_cosf, 2 rt_sinf, 3 rt_asinf, 4 rt_acosf,
  * 5 rt_u01, 6 rt_jitter, 7 rt_theta (5-7 take the uint32 hash output), 8 sqrtf, 9 1.0f/x,

@@ -168,6 +168,7 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     ctx->multi.careful = env_int("RT_AMD_MULTI_CAREFUL", INT_MIN, INT_MAX, 0) != 0;
     ctx->cull.enabled = env_int("RT_AMD_PRIMARY_CULL", 0, 1, 1) != 0;
     ctx->cull.gates = env_int("RT_AMD_SUBTREE_CULL", 0, 1, 1) != 0;
+    ctx->cull.entry = env_int("RT_AMD_PRIMARY_ENTRY", 0, 1, 1) != 0;
     if (ctx->tile_counter.grow(256) != hipSuccess ||
         hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
         delete ctx;
@@ -686,7 +687,7 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
     k.width = cam->width; k.height = cam->height; k.antialias = rs->antialias ? 1 : 0;
     const rt_cull_host::Step step = cp.plan.next(k, enabled, [&](size_t words) {
         /* (the old plane is freed first, which waits for the launches that read it) */
-        const bool ok = cp.d.grow(rt_cull_alloc_words(words)) == hipSuccess;     /* the bits and, behind them, the gate words */
+        const bool ok = cp.d.grow(rt_cull_alloc_words_entry(words)) == hipSuccess;     /* the bits and, behind them, the gate words and the entry words */
         if (!ok) (void)hipGetLastError();
         return ok;
     });
@@ -699,7 +700,10 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
             for (FrameSlot &fs : ctx->pipe.slots)
                 if (fs.used && &fs != slot) ok = ok && hipEventSynchronize(fs.ev_done) == hipSuccess;
         if (ok && !cp.ev.e) ok = hipEventCreateWithFlags(&cp.ev.e, hipEventDisableTiming) == hipSuccess;
-        ok = ok && rt_launch_cull(k.cam, k.width, k.height, (k.antialias ? RT_CULL_ANTIALIAS : 0) | (cp.gates ? RT_CULL_WITH_GATES : 0), scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
+        /* (the entry words need the triangles: where they start rides in the flags' upper bits, rt_entry.h) */
+        const bool entry = cp.entry && scene->flat.num_meshes == 1 && scene->flat.off_tris >= 0 && scene->flat.off_tris < (1 << (31 - RT_CULL_TRIS_SHIFT));
+        const int32_t view_flags = (k.antialias ? RT_CULL_ANTIALIAS : 0) | (cp.gates ? RT_CULL_WITH_GATES : 0) | (entry ? RT_CULL_WITH_ENTRY | (scene->flat.off_tris << RT_CULL_TRIS_SHIFT) : 0);
+        ok = ok && rt_launch_cull(k.cam, k.width, k.height, view_flags, scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
                                   scene->flat.num_meshes, cp.d.p, stream) == hipSuccess;
         ok = ok && hipEventRecord(cp.ev, stream) == hipSuccess;
         cp.stream = stream;
@@ -913,6 +917,64 @@ extern "C" rt_status rt_debug_subtree_cull(rt_ctx *ctx, uint32_t *words, int32_t
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
     RT_HIP(ctx, hipMemcpy(words, cp.d.p + rt_cull_words(cp.plan.key.width, cp.plan.key.height), n * 4, hipMemcpyDeviceToHost), "reading the gate words");
+    return RT_OK;
+}
+
+/* test hook: the primary entry words (rt_entry.h) the last render launch of the context was handed, one per pixel, read back (waits for the
+ * device).  info4 as rt_debug_subtree_cull's */
+extern "C" rt_status rt_debug_primary_entry(rt_ctx *ctx, uint32_t *words, int32_t capacity_words, int32_t *info4)
+{
+    if (!ctx || !info4 || capacity_words < 0) return set_err(ctx, RT_ERR_INVALID, "bad argument");
+    const CullPlane &cp = ctx->cull;
+    const bool have = cp.plan.valid && cp.plan.used_last && cp.d.p;
+    const size_t n = have ? (size_t)cp.plan.key.width * (size_t)cp.plan.key.height : 0;
+    info4[0] = have ? 1 : 0;
+    info4[1] = have ? cp.plan.key.width : 0;
+    info4[2] = have ? cp.plan.key.height : 0;
+    info4[3] = (int32_t)n;
+    if (!have || !words || (size_t)capacity_words < n) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
+    RT_HIP(ctx, hipMemcpy(words, cp.d.p + rt_cull_entry_base(rt_cull_words(cp.plan.key.width, cp.plan.key.height)), n * 4, hipMemcpyDeviceToHost), "reading the entry words");
+    return RT_OK;
+}
+
+/* test / development hook, host only (no device is touched): rt_entry_word per pixel of `cam`'s image on a flattened scene, as the pre-pass
+ * writes it (0 everywhere unless the scene has exactly one mesh).  words: width * height, or NULL.  stats12, or NULL: over the unflagged
+ * pixels whose cone may enter the root box, by class of the word - `triangle`, `nothing`, 0 - {pixels x 3, the centre ray's node steps x 3,
+ * its triangle tests x 3} walked in the render kernel's order with the pixel's gate word and the kernel's float tests, then {triangles
+ * the predicate classified, 0, 0} - what tools/primary_cull_estimate.py prints. */
+extern "C" rt_status rt_debug_primary_entry_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats12)
+{
+    if (!view || !cam || !view->blob || cam->width <= 0 || cam->height <= 0 || (int64_t)cam->width * cam->height > (1 << 28)) return RT_ERR_INVALID;
+    float c12[12];
+    camera_floats(*cam, c12);
+    int64_t st[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool one = view->num_meshes == 1;
+    for (int py = 0; py < cam->height; py++)
+        for (int px = 0; px < cam->width; px++) {
+            float P[3];
+            rt_cull_primary(c12, px, py, P);
+            const rt_cull_cone cone = rt_cull_cone_of(P, c12, antialias);
+            const uint32_t word = one ? rt_entry_word(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, view->off_tris, view->num_triangles,
+                                                      rt_cull_local_stack(), rt_cull_local_stack(), &st[9]) : 0u;
+            if (words) words[(size_t)py * (size_t)cam->width + (size_t)px] = word;
+            if (!one) continue;
+            const float *m0 = view->blob + 4 * (size_t)view->off_meshes;
+            if (rt_cull_box_missed(cone, m0[0], m0[1], m0[2], m0[3], m0[4], m0[5])) continue;
+            if (rt_cull_no_leaf(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 1, rt_cull_local_stack())) continue;
+            const uint32_t gates = rt_cull_gate_word(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, rt_cull_local_stack());
+            const float inv[3] = {1.0f / P[0], 1.0f / P[1], 1.0f / P[2]};
+            const int cls = (word & RT_ENTRY_TAG) ? 0 : (word == RT_ENTRY_NOTHING ? 1 : 2);
+            float best; int32_t prim;
+            int64_t tests = 0;
+            const int64_t steps = rt_cull_walk(view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, c12, P, inv, gates, best, prim,
+                                               rt_entry_leaf_tests{view->blob + 4 * (size_t)view->off_tris, c12, P, &tests});
+            st[cls]++;
+            st[3 + cls] += steps > 0 ? steps : 0;
+            st[6 + cls] += tests;
+        }
+    if (stats12) std::memcpy(stats12, st, sizeof st);
     return RT_OK;
 }
 

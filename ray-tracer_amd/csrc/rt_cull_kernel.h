@@ -11,6 +11,7 @@
 
 #include "rt_cull.h"
 #include "rt_device_scene.h"
+#include "rt_entry.h"
 #include "rt_launch.h"
 
 #define RT_CULL_THREADS 256
@@ -19,9 +20,11 @@ struct rt_cull_args {
     float cam[12];
     int32_t width, height, antialias;
     int32_t gates;               /* 0: every gate word is written as 0 (RT_AMD_SUBTREE_CULL=0, or a scene of several meshes: the words are one mesh's) */
+    int32_t entry;               /* 0: every entry word is written as 0 (RT_AMD_PRIMARY_ENTRY=0, or a scene of several meshes) */
+    int32_t off_tris, num_tris;  /* the triangles the entry words are about: where they start in the blob, and how many the nodes' leaves may name */
     const float *blob;
     int32_t off_nodes, num_nodes, off_meshes, num_meshes;
-    uint32_t *plane;             /* rt_cull_alloc_words(rt_cull_words(width, height)) words: the bits, then a gate word per thread of the grid */
+    uint32_t *plane;             /* rt_cull_alloc_words_entry(rt_cull_words(width, height)) words: the bits, then a gate word and then an entry word per thread of the grid */
 };
 
 /* a thread's column of the walk's stack in LDS, [entry][thread] */
@@ -32,14 +35,16 @@ struct rt_cull_lds_stack {
 
 /* Thread i has pixel i (py * width + px); a wave's 64 answers are one ballot, whose halves lanes 0 and 32 store: whole words, no atomics.
  * The grid covers rt_cull_words * 32 pixels, so every word of the plane is written; a thread past the image answers 0.  Every thread then
- * writes its gate word (0 past the image and without `gates`; a flagged pixel has every gate dead). */
+ * writes its gate word (0 past the image and without `gates`; a flagged pixel has every gate dead) and its entry word (rt_entry.h; 0 past
+ * the image, without `entry` and for a flagged pixel). */
 __global__ __launch_bounds__(RT_CULL_THREADS) void rt_cull_kernel(const rt_cull_args a)
 {
     __shared__ uint32_t stacks[RT_CULL_STACK * RT_CULL_THREADS];
+    __shared__ uint32_t bounds[RT_CULL_STACK * RT_CULL_THREADS];       /* the entry walk's path bounds, beside its pending references */
     const size_t i = (size_t)blockIdx.x * RT_CULL_THREADS + threadIdx.x;
     const size_t pixels = (size_t)a.width * (size_t)a.height;
     bool flagged = false;
-    uint32_t gate_word = 0u;
+    uint32_t gate_word = 0u, entry_word = 0u;
     if (i < pixels) {
         const int py = (int)(i / (size_t)a.width), px = (int)(i - (size_t)py * (size_t)a.width);
         float P[3];
@@ -47,6 +52,8 @@ __global__ __launch_bounds__(RT_CULL_THREADS) void rt_cull_kernel(const rt_cull_
         const rt_cull_cone c = rt_cull_cone_of(P, a.cam, a.antialias);
         flagged = rt_cull_no_leaf(c, a.blob, a.off_nodes, a.num_nodes, a.off_meshes, a.num_meshes, rt_cull_lds_stack{stacks + threadIdx.x});
         if (a.gates) gate_word = rt_cull_gate_word(c, a.blob, a.off_nodes, a.num_nodes, a.off_meshes, 0, rt_cull_lds_stack{stacks + threadIdx.x});
+        if (a.entry && !flagged)
+            entry_word = rt_entry_word(c, a.blob, a.off_nodes, a.num_nodes, a.off_meshes, 0, a.off_tris, a.num_tris, rt_cull_lds_stack{stacks + threadIdx.x}, rt_cull_lds_stack{bounds + threadIdx.x});
     }
     const unsigned long long bits = __ballot(flagged);
     const int lane = threadIdx.x & 63;
@@ -55,6 +62,7 @@ __global__ __launch_bounds__(RT_CULL_THREADS) void rt_cull_kernel(const rt_cull_
         if (lane == 0) a.plane[word] = (uint32_t)bits;
         if (lane == 32) a.plane[word] = (uint32_t)(bits >> 32);
         a.plane[rt_cull_words(a.width, a.height) + i] = gate_word;
+        a.plane[rt_cull_entry_base(rt_cull_words(a.width, a.height)) + i] = entry_word;
     }
 }
 
@@ -66,6 +74,9 @@ extern "C" hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t he
     for (int k = 0; k < 12; k++) a.cam[k] = cam[k];
     a.width = width; a.height = height; a.antialias = (view_flags & RT_CULL_ANTIALIAS) ? 1 : 0;
     a.gates = (view_flags & RT_CULL_WITH_GATES) && num_meshes == 1 ? 1 : 0;
+    a.entry = (view_flags & RT_CULL_WITH_ENTRY) && num_meshes == 1 ? 1 : 0;
+    a.off_tris = (int32_t)((uint32_t)view_flags >> RT_CULL_TRIS_SHIFT);
+    a.num_tris = (int32_t)(RT_REF_START_MASK + 1u);      /* (a leaf names at most that many; the blob ends with the triangles its leaves name) */
     a.blob = (const float *)blob;
     a.off_nodes = off_nodes; a.num_nodes = num_nodes; a.off_meshes = off_meshes; a.num_meshes = num_meshes;
     a.plane = plane;

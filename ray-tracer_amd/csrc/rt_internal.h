@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rt_cull.h"           /* the primary-ray cull: its plane's bookkeeping */
+#include "rt_entry.h"          /* ... and the entry words behind the plane */
 #include "rt_host.h"
 #include "rt_launch.h"         /* the kernel launchers: the seam to rt_kernel.hip */
 #include "rt_query.h"          /* RT_QUERY_MAX_RAYS */
@@ -177,6 +178,7 @@ struct CullPlane {
     hipStream_t stream = nullptr;        /* ... on this stream (the caller's: not owned) */
     bool enabled = true;                 /* RT_AMD_PRIMARY_CULL=0: every launch renders without the plane */
     bool gates = true;                   /* RT_AMD_SUBTREE_CULL=0: the pre-pass writes every gate word as 0 (the kernel then gates nothing) */
+    bool entry = true;                   /* RT_AMD_PRIMARY_ENTRY=0: the pre-pass writes every entry word as 0 (rt_entry.h: every primary ray starts at the root) */
 };
 
 /* knobs (RT_AMD_*), none changes an image: rt_schedule.h has them, their accepted ranges and what the kernel is handed for them

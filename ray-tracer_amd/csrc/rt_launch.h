@@ -83,7 +83,9 @@ hipError_t rt_launch_rebuild(const rt_rebuild_args *args, hipStream_t stream);
  * writes rt_cull_words(width, height) words of `plane`, a set bit: the pixel's primary rays reach no leaf of any mesh, and behind them a
  * word per pixel, the subtree cull's dead gates (rt_cull.h: `plane` has rt_cull_alloc_words of those words).  view_flags: RT_CULL_ANTIALIAS
  * (the view's rays are jittered) | RT_CULL_WITH_GATES (compute the gate words; without it, or with more than one mesh, every gate word is
- * written as 0); no other bit means anything */
+ * written as 0) | RT_CULL_WITH_ENTRY (rt_entry.h: compute the entry words behind the gate words - `plane` then has rt_cull_alloc_words_entry
+ * words -, of the triangles that start at 16-byte unit view_flags >> RT_CULL_TRIS_SHIFT of the blob; without it, or with more than one mesh,
+ * every entry word is written as 0) */
 hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t height, int32_t view_flags, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
                           int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream);
 

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "rt_cull.h"
+#include "rt_entry.h"
 #include "rt_device_scene.h"
 #include "rt_instrument.h"
 #include "rt_intersect.h"
@@ -568,6 +569,12 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
                 const unsigned pixel = (unsigned)(py * f.W + px);
                 nocull = (~(plane[pixel >> 5] >> (pixel & 31u))) << 31;
                 gates = plane[rt_cull_words(f.W, f.H) + pixel];
+                /* the pixel's entry word (rt_entry.h), behind the gate words: `nothing` makes the pixel a flagged one - its primary rays
+                 * test no triangle that they hit - and `triangle T`, tagged by bit 0, which no gate word has, takes the gate word's place:
+                 * the mesh start reads it there (rt_render_loop.inc) */
+                const uint32_t entry = plane[rt_cull_entry_base(rt_cull_words(f.W, f.H)) + pixel];
+                if (entry == RT_ENTRY_NOTHING) nocull = 0u;
+                if (entry & RT_ENTRY_TAG) gates = entry;
             }
             p.id |= nocull;
             *px_gates = gates;

@@ -127,7 +127,14 @@
                     if (!(!rh || rd > RT_INF_F || ((root_ref & RT_REF_CHAIN) && !(rd < RT_INF_F)))) {
                         cur = root_ref; sp = 0; w_best = RT_INF_F; w_prim = -1;
                         w_ray_bits = (p.d.x == 0.0f || p.d.y == 0.0f || p.d.z == 0.0f) ? RT_RAY_ZERO_DIR : 0u;
-                        if (CULL) w_ray_bits |= p.bounce == 0 ? px_gates & ~RT_RAY_ZERO_DIR : 0u;
+                        if (CULL) {
+                            /* a primary ray of a pixel whose word is tagged `triangle T` (rt_entry.h) starts on the one-triangle leaf (T)
+                             * with an empty stack and no gates: the leaf section tests T against best = RT_INF_F and merges.  Else the word
+                             * is the pixel's gate word */
+                            const bool tagged = p.bounce == 0 && (px_gates & RT_ENTRY_TAG) != 0u;
+                            if (tagged) cur = rt_entry_leaf(px_gates);
+                            w_ray_bits |= p.bounce == 0 && !tagged ? px_gates & ~RT_RAY_ZERO_DIR : 0u;
+                        }
                         p.mode = M_WAIT;
                         p.frame_steps |= 0x80000000u;
                         RT_STAT(ST_MESH_START);

@@ -1,5 +1,6 @@
 """The primary-ray cull's test and development hooks (csrc/rt_cull.h): the bit plane a context's last render launch was handed, and the same
-plane computed on the host from a flattened scene; the subtree cull's gate words, a word per pixel behind the bits, in the same two forms."""
+plane computed on the host from a flattened scene; the subtree cull's gate words, a word per pixel behind the bits, and the primary entry
+words behind those (csrc/rt_entry.h), in the same two forms."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +10,9 @@ from .objects import Scene
 
 _u32p = C.POINTER(C.c_uint32)
 GATE_STATS = ("pixels", "centre_steps", "centre_steps_gated", "pixels_with_dead_gates")
+ENTRY_STATS = ("pixels_triangle", "pixels_nothing", "pixels_unknown", "centre_steps_triangle", "centre_steps_nothing", "centre_steps_unknown",
+               "centre_tests_triangle", "centre_tests_nothing", "centre_tests_unknown", "triangles_classified")
+ENTRY_NOTHING = 2
 STATS = ("root_entering", "flagged_root_entering", "centre_steps_flagged", "centre_steps_root_entering", "flagged", "words")
 
 
@@ -77,3 +81,32 @@ def subtree_cull_host(scene, camera, antialias=True):
     if st != 0:
         raise ValueError("rt_debug_subtree_cull_host refused its arguments (status %d)" % st)
     return words.reshape(int(camera.c.height), int(camera.c.width)), dict(zip(GATE_STATS, (int(x) for x in stats)))
+
+
+def primary_entry_words(ctx):
+    """(used, words): whether the context's last render launch was handed a cull plane, and the entry words behind it read back from the device as a
+    (height, width) array (None if it was not): T << 1 | 1 - every primary ray of the pixel ends on triangle T -, ENTRY_NOTHING or 0; waits for
+    the device"""
+    info = (C.c_int32 * 4)()
+    ctx._check(lib().rt_debug_primary_entry(ctx._h, None, 0, info))
+    if not info[0]:
+        return False, None
+    words = np.zeros(int(info[3]), np.uint32)
+    ctx._check(lib().rt_debug_primary_entry(ctx._h, words.ctypes.data_as(_u32p), words.size, info))
+    return True, words.reshape(int(info[2]), int(info[1]))
+
+
+def primary_entry_host(scene, camera, antialias=True):
+    """(words, stats) of rt_entry_word evaluated on the host per pixel of `camera`'s image, words as a (height, width) array; `scene` as for
+    primary_cull_host.  Needs no GPU for a SceneObjects."""
+    v = rt_flat_view()
+    if isinstance(scene, Scene):
+        scene.ctx._check(lib().rt_debug_scene_read(scene.ctx._h, scene._h, C.byref(v)))
+    else:
+        scene._check(lib().rt_debug_flatten(scene._h, C.byref(v)))
+    words = np.zeros(int(camera.c.width) * int(camera.c.height), np.uint32)
+    stats = (C.c_int64 * 12)()
+    st = lib().rt_debug_primary_entry_host(C.byref(v), C.byref(camera.c), 1 if antialias else 0, words.ctypes.data_as(_u32p), stats)
+    if st != 0:
+        raise ValueError("rt_debug_primary_entry_host refused its arguments (status %d)" % st)
+    return words.reshape(int(camera.c.height), int(camera.c.width)), dict(zip(ENTRY_STATS, (int(x) for x in stats)))
