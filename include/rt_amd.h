@@ -1243,6 +1243,20 @@ rt_status rt_debug_primary_entry(rt_ctx *ctx, uint32_t *words, int32_t capacity_
  * the unflagged pixels whose jitter cone may enter the root box, by class of their word - `triangle`, `nothing`, 0: {pixels x 3, the centre ray's node
  * steps x 3, its triangle tests x 3}, walked in the kernel's order with the pixel's gate word, then {triangles the predicate looked at, 0, 0} */
 rt_status rt_debug_primary_entry_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, uint32_t *words, int64_t *stats12);
+/* The sub-entry words (rt_entry.h): a pixel of a jittered view whose entry word is 0 gets a table of 64 such words, one per sub-box of the jitter
+ * cube split in four per axis, and a primary ray whose jitter falls in a sub-box with a non-zero word starts as above.  The tables are filled in by
+ * the first launch of a view that draws at least RT_AMD_SUBENTRY_SAMPLES samples per pixel (spp x frames; default 2200), else by the view's first
+ * reuse.  RT_AMD_PRIMARY_SUBENTRY=0 (read by rt_ctx_create): no tables.  Frames are bit-identical either way.
+ * rt_debug_primary_subentry: the tables the context's last render launch was handed, read back (waits for the device), in ascending order of the
+ * pixel: pixels[i] = py * width + px, words[64 * i + idx] its sub-word of sub-box idx = jx + 4 jy + 16 jz.  info4 = {1 if that launch was handed
+ * a plane with the view's tables else 0, width, height, tables in use}; with pixels or words NULL or too small a capacity only info4 is written.
+ * rt_debug_primary_entry reports a pixel that has a table with its own word, 0. */
+rt_status rt_debug_primary_subentry(rt_ctx *ctx, uint32_t *pixels, uint32_t *words, int32_t capacity_tables, int32_t *info4);
+/* the same tables computed on the HOST (no device is touched).  cap < 0: as many tables as the image's allocation holds, else at most cap (the first
+ * pixels in order).  stats8, or NULL: {pixels that want a table, tables handed out, sub-words `triangle`, `nothing`, 0, the table pixels' centre-ray
+ * gated node steps summed over their non-zero sub-words, the same over all 64, 0} */
+rt_status rt_debug_primary_subentry_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, int32_t cap, uint32_t *pixels, uint32_t *words,
+                                         int32_t capacity_tables, int64_t *stats8);
 /* evaluates one function of the shared math / RNG headers ON THE DEVICE, element-wise, on raw
  * 32-bit patterns (host pointers).  op: 0 rt_logf, 1 rt_cosf, 2 rt_sinf, 3 rt_asinf, 4 rt_acosf,
  * 5 rt_u01, 6 rt_jitter, 7 rt_theta (5-7 take the uint32 hash output), 8 sqrtf, 9 1.0f/x,

@@ -33,5 +33,5 @@ from .denoise import DenoiseParams, denoise, denoise_device, render_denoised  # 
 from .adaptive import BUDGET_MAX, AdaptiveParams, adaptive_plan_device, render_adaptive, render_budget, render_budget_device  # noqa: F401
 from .views import VIEWS_MAX, lens_cameras, render_views, render_views_device  # noqa: F401
 from .sky import SKY_MAX_FACE, Sky, render_sky, render_sky_device, sky_from_equirect, sky_texel_directions  # noqa: F401
-from .cull import primary_cull_host, primary_cull_plane, primary_entry_host, primary_entry_words, subtree_cull_host, subtree_cull_words  # noqa: F401
+from .cull import primary_cull_host, primary_cull_plane, primary_entry_host, primary_entry_words, primary_subentry_host, primary_subentry_tables, subtree_cull_host, subtree_cull_words  # noqa: F401
 from .update import REBUILD_LDS_TRIS  # noqa: F401  (and Scene.update_mesh, Scene.update_mesh_device, Scene.debug_read)

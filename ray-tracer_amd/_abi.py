@@ -241,6 +241,8 @@ ABI = {
     "rt_debug_subtree_cull_host": (st, [C.POINTER(rt_flat_view), cam, i32, u32p, C.POINTER(C.c_int64)]),
     "rt_debug_primary_entry": (st, [vp, u32p, i32, i32p]),
     "rt_debug_primary_entry_host": (st, [C.POINTER(rt_flat_view), cam, i32, u32p, C.POINTER(C.c_int64)]),
+    "rt_debug_primary_subentry": (st, [vp, u32p, u32p, i32, i32p]),
+    "rt_debug_primary_subentry_host": (st, [C.POINTER(rt_flat_view), cam, i32, i32, u32p, u32p, i32, C.POINTER(C.c_int64)]),
     "rt_debug_eval": (st, [vp, i32, u32p, u32p, i32]),
     "rt_debug_exhaustive": (st, [vp, u64p]),
     "rt_debug_read_stats": (st, [vp, u64p]),

@@ -12,6 +12,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <climits>
 #include <cstdio>
@@ -169,6 +170,8 @@ extern "C" rt_status rt_ctx_create(int32_t device, rt_ctx **out)
     ctx->cull.enabled = env_int("RT_AMD_PRIMARY_CULL", 0, 1, 1) != 0;
     ctx->cull.gates = env_int("RT_AMD_SUBTREE_CULL", 0, 1, 1) != 0;
     ctx->cull.entry = env_int("RT_AMD_PRIMARY_ENTRY", 0, 1, 1) != 0;
+    ctx->cull.sub = env_int("RT_AMD_PRIMARY_SUBENTRY", 0, 1, 1) != 0;
+    ctx->cull.sub_threshold = env_int("RT_AMD_SUBENTRY_SAMPLES", 0, 1 << 30, RT_SUB_THRESHOLD_SAMPLES);
     if (ctx->tile_counter.grow(256) != hipSuccess ||
         hipEventCreate(&ctx->ev_start.e) != hipSuccess || hipEventCreate(&ctx->ev_stop.e) != hipSuccess) {
         delete ctx;
@@ -685,31 +688,39 @@ static void bind_cull(rt_ctx *ctx, const rt_scene *scene, const rt_camera *cam, 
     k.scene_uid = scene->uid;
     camera_floats(*cam, k.cam);
     k.width = cam->width; k.height = cam->height; k.antialias = rs->antialias ? 1 : 0;
+    /* (the sub-entry tables, rt_entry.h: only the one-mesh scene whose triangles the flags can name has them) */
+    const bool entry = cp.entry && scene->flat.num_meshes == 1 && scene->flat.off_tris >= 0 && scene->flat.off_tris < (1 << (31 - RT_CULL_TRIS_SHIFT));
+    cp.plan.want_tables = cp.sub && entry;
     const rt_cull_host::Step step = cp.plan.next(k, enabled, [&](size_t words) {
         /* (the old plane is freed first, which waits for the launches that read it) */
-        const bool ok = cp.d.grow(rt_cull_alloc_words_entry(words)) == hipSuccess;     /* the bits and, behind them, the gate words and the entry words */
+        /* the bits and, behind them, the gate words and the entry words; with `tables` the sub-entry tables behind those */
+        const bool ok = cp.d.grow(cp.plan.tables ? rt_sub_alloc_words(words) : rt_cull_alloc_words_entry(words)) == hipSuccess;
         if (!ok) (void)hipGetLastError();
         return ok;
     });
     if (step == rt_cull_host::Step::none) return;
+    const bool refine = cp.plan.refine(step, k, (int64_t)rs->rays_per_pixel * (int64_t)a.num_frames, cp.sub_threshold);
     bool ok = true;
-    if (step == rt_cull_host::Step::run) {
+    if (step == rt_cull_host::Step::reuse && cp.stream != stream) ok = hipStreamWaitEvent(stream, cp.ev, 0) == hipSuccess;
+    if (step == rt_cull_host::Step::run || refine) {
         /* the plane is rewritten: ordinary launches are already behind every launch that read it (render_frames); a pipelined frame
-         * overlaps the others in flight, whose render kernels are waited for here - once per view */
+         * overlaps the others in flight, whose render kernels are waited for here - once per view, and once more where its refinement
+         * is queued by a later launch */
         if (slot)
             for (FrameSlot &fs : ctx->pipe.slots)
                 if (fs.used && &fs != slot) ok = ok && hipEventSynchronize(fs.ev_done) == hipSuccess;
         if (ok && !cp.ev.e) ok = hipEventCreateWithFlags(&cp.ev.e, hipEventDisableTiming) == hipSuccess;
-        /* (the entry words need the triangles: where they start rides in the flags' upper bits, rt_entry.h) */
-        const bool entry = cp.entry && scene->flat.num_meshes == 1 && scene->flat.off_tris >= 0 && scene->flat.off_tris < (1 << (31 - RT_CULL_TRIS_SHIFT));
-        const int32_t view_flags = (k.antialias ? RT_CULL_ANTIALIAS : 0) | (cp.gates ? RT_CULL_WITH_GATES : 0) | (entry ? RT_CULL_WITH_ENTRY | (scene->flat.off_tris << RT_CULL_TRIS_SHIFT) : 0);
+        /* (the entry words need the triangles: where they start rides in the flags' upper bits, rt_entry.h.  A reused plane has its
+         * words: RT_CULL_WITH_SUBENTRY without RT_CULL_WITH_ENTRY queues the refinement alone) */
+        const bool pre_pass = step == rt_cull_host::Step::run;
+        const int32_t view_flags = (k.antialias ? RT_CULL_ANTIALIAS : 0) | (cp.gates ? RT_CULL_WITH_GATES : 0) | (entry && pre_pass ? RT_CULL_WITH_ENTRY : 0) |
+                                   (refine ? RT_CULL_WITH_SUBENTRY : 0) | (entry ? scene->flat.off_tris << RT_CULL_TRIS_SHIFT : 0);
         ok = ok && rt_launch_cull(k.cam, k.width, k.height, view_flags, scene->d_blob.p, scene->flat.off_nodes, scene->flat.num_nodes, scene->flat.off_meshes,
                                   scene->flat.num_meshes, cp.d.p, stream) == hipSuccess;
         ok = ok && hipEventRecord(cp.ev, stream) == hipSuccess;
         cp.stream = stream;
-        cp.plan.ran(k, ok);
-    } else if (cp.stream != stream) {
-        ok = hipStreamWaitEvent(stream, cp.ev, 0) == hipSuccess;
+        if (pre_pass) cp.plan.ran(k, ok);
+        else if (!ok) cp.plan.refine_failed();
     }
     if (!ok) { (void)hipGetLastError(); return; }
     rt_kernel_args_set_cull(a, cp.d.p);
@@ -936,6 +947,89 @@ extern "C" rt_status rt_debug_primary_entry(rt_ctx *ctx, uint32_t *words, int32_
     RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
     RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
     RT_HIP(ctx, hipMemcpy(words, cp.d.p + rt_cull_entry_base(rt_cull_words(cp.plan.key.width, cp.plan.key.height)), n * 4, hipMemcpyDeviceToHost), "reading the entry words");
+    /* (a pixel with a sub-entry table carries its slot here: its own word is 0, and rt_debug_primary_subentry has its table) */
+    for (size_t i = 0; i < n; i++)
+        if (rt_sub_slot_plus1(words[i]) != 0u) words[i] = 0u;
+    return RT_OK;
+}
+
+/* test hook: the sub-entry tables (rt_entry.h) the last render launch of the context was handed, read back (waits for the device) and keyed
+ * by pixel, in ascending order of the pixel: pixels[i] = py * width + px, words[64 * i + idx] its sub-word of sub-box idx.  info4 = {1 if
+ * that launch was handed a plane whose view is refined else 0, the image's width, its height, the tables in use}; with pixels or words NULL
+ * or too small a capacity only info4 is written */
+extern "C" rt_status rt_debug_primary_subentry(rt_ctx *ctx, uint32_t *pixels, uint32_t *words, int32_t capacity_tables, int32_t *info4)
+{
+    if (!ctx || !info4 || capacity_tables < 0) return set_err(ctx, RT_ERR_INVALID, "bad argument");
+    const CullPlane &cp = ctx->cull;
+    const bool have = cp.plan.valid && cp.plan.used_last && cp.d.p && cp.plan.tables && cp.plan.refined;
+    info4[0] = have ? 1 : 0;
+    info4[1] = have ? cp.plan.key.width : 0;
+    info4[2] = have ? cp.plan.key.height : 0;
+    info4[3] = 0;
+    if (!have) return RT_OK;
+    const size_t pw = rt_cull_words(cp.plan.key.width, cp.plan.key.height);
+    RT_HIP(ctx, hipSetDevice(ctx->device), "selecting device");
+    RT_HIP(ctx, hipDeviceSynchronize(), "waiting for the device");
+    uint32_t counter = 0;
+    RT_HIP(ctx, hipMemcpy(&counter, cp.d.p + rt_sub_header_base(pw), 4, hipMemcpyDeviceToHost), "reading the slot counter");
+    const size_t n = (size_t)counter < rt_sub_cap(pw) ? (size_t)counter : rt_sub_cap(pw);
+    info4[3] = (int32_t)n;
+    if (!pixels || !words || (size_t)capacity_tables < n || n == 0) return RT_OK;
+    std::vector<uint32_t> by_slot(n), table(n * RT_SUB_WORDS), order(n);
+    RT_HIP(ctx, hipMemcpy(by_slot.data(), cp.d.p + rt_sub_pixels_base(pw), n * 4, hipMemcpyDeviceToHost), "reading the slots' pixels");
+    RT_HIP(ctx, hipMemcpy(table.data(), cp.d.p + rt_sub_tables_base(pw), n * RT_SUB_WORDS * 4, hipMemcpyDeviceToHost), "reading the sub-entry tables");
+    for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return by_slot[x] < by_slot[y]; });
+    for (size_t i = 0; i < n; i++) {
+        pixels[i] = by_slot[order[i]];
+        for (size_t k = 0; k < RT_SUB_WORDS; k++) words[i * RT_SUB_WORDS + k] = rt_sub_word_of(table[(size_t)order[i] * RT_SUB_WORDS + k]);   /* (as stored: rt_entry.h) */
+    }
+    return RT_OK;
+}
+
+/* test / development hook, host only (no device is touched): the sub-entry tables of `cam`'s image on a flattened scene as the refinement
+ * writes them, keyed by pixel in ascending order.  cap < 0: the image's own (rt_sub_cap); else at most `cap` pixels get a table, the first
+ * in pixel order (the device hands its slots out in no particular order).  pixels / words as rt_debug_primary_subentry's, for at most
+ * capacity_tables tables (NULL: only the statistics).  stats8, or NULL: {pixels that want a table, tables handed out, sub-words `triangle`,
+ * `nothing`, not known, the table pixels' centre-ray gated node steps summed over their resolved sub-boxes, the same over all 64, 0} - what
+ * tools/primary_cull_estimate.py prints.  A view without jitter or a scene of several meshes has no tables. */
+extern "C" rt_status rt_debug_primary_subentry_host(const rt_flat_view *view, const rt_camera *cam, int32_t antialias, int32_t cap, uint32_t *pixels, uint32_t *words,
+                                                    int32_t capacity_tables, int64_t *stats8)
+{
+    if (!view || !cam || !view->blob || cam->width <= 0 || cam->height <= 0 || (int64_t)cam->width * cam->height > (1 << 28) || capacity_tables < 0) return RT_ERR_INVALID;
+    float c12[12];
+    camera_floats(*cam, c12);
+    int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const size_t limit = cap < 0 ? rt_sub_cap(rt_cull_words(cam->width, cam->height)) : (size_t)cap;
+    const bool one = view->num_meshes == 1 && antialias;
+    for (int py = 0; one && py < cam->height; py++)
+        for (int px = 0; px < cam->width; px++) {
+            float P[3];
+            rt_cull_primary(c12, px, py, P);
+            const rt_cull_cone cone = rt_cull_cone_of(P, c12, 1);
+            const bool flagged = rt_cull_no_leaf(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 1, rt_cull_local_stack());
+            const uint32_t word = rt_entry_word(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, view->off_tris, view->num_triangles, rt_cull_local_stack(),
+                                                rt_cull_local_stack());
+            if (!rt_sub_wants_table(flagged, word)) continue;
+            st[0]++;
+            if ((size_t)st[1] >= limit) continue;
+            const size_t slot = (size_t)st[1]++;
+            const uint32_t gates = rt_cull_gate_word(cone, view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, rt_cull_local_stack());
+            const float inv[3] = {1.0f / P[0], 1.0f / P[1], 1.0f / P[2]};
+            int64_t steps = rt_cull_walk_steps(view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, c12, P, inv, gates);
+            if (steps < 0) steps = 0;
+            const bool keep = pixels && words && slot < (size_t)capacity_tables;
+            if (keep) pixels[slot] = (uint32_t)((size_t)py * (size_t)cam->width + (size_t)px);
+            for (uint32_t idx = 0; idx < RT_SUB_WORDS; idx++) {
+                const uint32_t w = rt_entry_word(rt_sub_cone_of(P, c12, idx), view->blob, view->off_nodes, view->num_nodes, view->off_meshes, 0, view->off_tris, view->num_triangles,
+                                                 rt_cull_local_stack(), rt_cull_local_stack());
+                if (keep) words[slot * RT_SUB_WORDS + idx] = w;
+                st[(w & RT_ENTRY_TAG) ? 2 : (w == RT_ENTRY_NOTHING ? 3 : 4)]++;
+                if (w != 0u) st[5] += steps;
+                st[6] += steps;
+            }
+        }
+    if (stats8) std::memcpy(stats8, st, sizeof st);
     return RT_OK;
 }
 

@@ -418,22 +418,54 @@ struct Plan {
     bool used_last = false;              /* the last render launch was handed the plane */
     /* what the launch of view `k` does.  grow(words) allocates a plane of at least that many words and says whether it could; it is called
      * only when the image outgrows the allocation, and a refusal leaves the context without a plane (the launch renders without one). */
+    /* The sub-entry tables (rt_entry.h) live behind the plane in the same allocation.  want_tables is the caller's switch, set before
+     * next(); while next() calls grow(words), `tables` says which size the allocation is to have - with the tables (rt_sub_alloc_words) or
+     * without (rt_cull_alloc_words_entry).  An allocation with tables that is refused is asked for again without them, once per size:
+     * the plane then works as before and nothing is refined until the image outgrows it.  want_tables follows the scene (one mesh), `tables`
+     * the allocation: once granted the larger allocation is kept - a launch that wants no tables uses its front part - and only growth of the
+     * image allocates again, with the tables if the launch that grows it wants them.  So a one-mesh and a several-mesh scene alternating at
+     * growing sizes allocate once per size, as before, and once more where the first launch of a size wanted no tables and a later one does;
+     * each allocation frees the old plane, which waits for the launches that read it. */
+    bool want_tables = false;
+    bool tables = false;                 /* the allocation has room for the tables of cap_words */
+    bool tables_refused = false;         /* ... it was refused with them: not asked for again at this size */
+    bool refined = false;                /* the plane's view has its tables filled in (or queued to be) */
     template <class Grow> Step next(const Key &k, bool enabled, Grow grow)
     {
         used_last = false;
         if (!enabled) return Step::none;
         if (valid && key.same(k)) return Step::reuse;
         valid = false;
+        refined = false;
         const size_t words = rt_cull_words(k.width, k.height);
-        if (cap_words < words) {
+        if (cap_words < words || (want_tables && !tables && !tables_refused)) {
+            if (cap_words < words) tables_refused = false;
             cap_words = 0;
-            if (!grow(words)) return Step::none;
+            tables = want_tables && !tables_refused;
+            if (!grow(words)) {
+                if (!tables) return Step::none;
+                tables = false; tables_refused = true;
+                if (!grow(words)) return Step::none;
+            }
             cap_words = words;
         }
         return Step::run;
     }
     /* the pre-pass for `k` is queued (ok) or could not be (the launch then renders without the plane) */
-    void ran(const Key &k, bool ok) { valid = ok; if (ok) key = k; }
+    void ran(const Key &k, bool ok) { valid = ok; if (ok) key = k; else refined = false; }
+    /* Does the launch that next() answered `step` for queue the refinement?  `samples` are the launch's own samples per pixel (spp x
+     * frames).  A view's first launch refines at once if it reaches `threshold` - the refinement then pays for itself inside the launch -;
+     * otherwise the first reuse of the view's plane does: a caller who never repeats a view with launches below the threshold never pays. */
+    bool refine(Step step, const Key &k, int64_t samples, int64_t threshold)
+    {
+        /* (a view without jitter has one ray per pixel: no tables) */
+        if (step == Step::none || !want_tables || !tables || refined || !k.antialias) return false;
+        if (step == Step::run && samples < threshold) return false;
+        refined = true;
+        return true;
+    }
+    /* the refinement could not be queued: the words of the plane are as the pre-pass left them or half rewritten - compute the view again */
+    void refine_failed() { valid = false; refined = false; }
 };
 
 }  // namespace rt_cull_host

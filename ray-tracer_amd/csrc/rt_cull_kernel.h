@@ -66,6 +66,52 @@ __global__ __launch_bounds__(RT_CULL_THREADS) void rt_cull_kernel(const rt_cull_
     }
 }
 
+/* ---- the refinement (rt_entry.h, "The sub-entry words"): two kernels behind the pre-pass, or on their own over a plane that has its view's
+ * words.  rt_sub_compact_kernel, one thread per pixel, hands every unflagged pixel whose entry word is 0 a slot from the counter (zeroed by
+ * the launcher), writes the slot into the pixel's entry word and the pixel into the slot's word; a pixel that finds the tables full keeps
+ * 0.  rt_sub_refine_kernel then runs one thread per (slot, sub-box): the 64 lanes of a wave walk the 64 sub-cones of one pixel, which are
+ * neighbours, so a wave is evenly loaded whatever the image looks like.  Every word of every table in use is written.  The number of tables in
+ * use is known on the device only, so the grid is the image's bound, cap x 64 threads (16.6 M, 64,800 workgroups at 1080p, where the monkey
+ * uses 47 % of them): a workgroup past the counter reads it and ends, which is part of the 14.5 ms measured there; nothing was tuned. */
+__global__ __launch_bounds__(RT_CULL_THREADS) void rt_sub_compact_kernel(const rt_cull_args a)
+{
+    const size_t i = (size_t)blockIdx.x * RT_CULL_THREADS + threadIdx.x;
+    const size_t pixels = (size_t)a.width * (size_t)a.height, words = rt_cull_words(a.width, a.height);
+    if (i >= pixels) return;
+    uint32_t *const entry = a.plane + rt_cull_entry_base(words) + i;
+    const bool flagged = ((a.plane[i >> 5] >> (i & 31u)) & 1u) != 0u;
+    if (!rt_sub_wants_table(flagged, *entry)) return;
+    const uint32_t slot = atomicAdd(a.plane + rt_sub_header_base(words), 1u);
+    if ((size_t)slot < rt_sub_cap(words)) {
+        a.plane[rt_sub_pixels_base(words) + slot] = (uint32_t)i;
+        *entry = rt_sub_slot_word(slot);
+    } else {
+        *entry = 0u;
+    }
+}
+
+__global__ __launch_bounds__(RT_CULL_THREADS) void rt_sub_refine_kernel(const rt_cull_args a)
+{
+    __shared__ uint32_t stacks[RT_CULL_STACK * RT_CULL_THREADS];
+    __shared__ uint32_t bounds[RT_CULL_STACK * RT_CULL_THREADS];
+    const size_t t = (size_t)blockIdx.x * RT_CULL_THREADS + threadIdx.x;
+    const size_t words = rt_cull_words(a.width, a.height), cap = rt_sub_cap(words), slot = t / RT_SUB_WORDS;
+    const uint32_t idx = (uint32_t)(t % RT_SUB_WORDS);
+    const size_t handed = a.plane[rt_sub_header_base(words)];        /* (the counter runs past cap where the tables are full) */
+    if (slot >= cap || slot >= handed) return;
+    const size_t i = a.plane[rt_sub_pixels_base(words) + slot];
+    uint32_t word = 0u;
+    if (i < (size_t)a.width * (size_t)a.height) {
+        const int py = (int)(i / (size_t)a.width), px = (int)(i - (size_t)py * (size_t)a.width);
+        float P[3];
+        rt_cull_primary(a.cam, px, py, P);
+        const rt_cull_cone c = rt_sub_cone_of(P, a.cam, idx);
+        word = rt_entry_word(c, a.blob, a.off_nodes, a.num_nodes, a.off_meshes, 0, a.off_tris, a.num_tris, rt_cull_lds_stack{stacks + threadIdx.x}, rt_cull_lds_stack{bounds + threadIdx.x});
+    }
+    /* (stored with the pixel's gate word where it is not known: rt_entry.h, "What a table stores") */
+    a.plane[rt_sub_tables_base(words) + slot * RT_SUB_WORDS + idx] = rt_sub_stored(word, i < (size_t)a.width * (size_t)a.height ? a.plane[words + i] : 0u);
+}
+
 extern "C" hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t height, int32_t view_flags, const rt_f4 *blob, int32_t off_nodes, int32_t num_nodes,
                                      int32_t off_meshes, int32_t num_meshes, uint32_t *plane, hipStream_t stream)
 {
@@ -80,8 +126,20 @@ extern "C" hipError_t rt_launch_cull(const float *cam, int32_t width, int32_t he
     a.blob = (const float *)blob;
     a.off_nodes = off_nodes; a.num_nodes = num_nodes; a.off_meshes = off_meshes; a.num_meshes = num_meshes;
     a.plane = plane;
-    const size_t threads = rt_cull_words(width, height) * 32;
-    hipLaunchKernelGGL(rt_cull_kernel, dim3((unsigned)((threads + RT_CULL_THREADS - 1) / RT_CULL_THREADS)), dim3(RT_CULL_THREADS), 0, stream, a);
+    const size_t words = rt_cull_words(width, height), threads = words * 32;
+    const size_t sub_blocks = (rt_sub_cap(words) * RT_SUB_WORDS + RT_CULL_THREADS - 1) / RT_CULL_THREADS;
+    if (threads / RT_CULL_THREADS + 1 > 0x7fffffffu || sub_blocks > 0x7fffffffu) return hipErrorInvalidValue;      /* (an image beyond check_image_size's 2^28 pixels) */
+    const unsigned blocks = (unsigned)((threads + RT_CULL_THREADS - 1) / RT_CULL_THREADS);
+    /* RT_CULL_WITH_SUBENTRY alone: the plane has this view's words, only the refinement is queued (the view's first reuse, rt_cull_host::Plan) */
+    const bool refine = (view_flags & RT_CULL_WITH_SUBENTRY) && a.antialias && num_meshes == 1, refine_only = refine && !(view_flags & RT_CULL_WITH_ENTRY);
+    if (!refine_only) hipLaunchKernelGGL(rt_cull_kernel, dim3(blocks), dim3(RT_CULL_THREADS), 0, stream, a);
+    if (refine) {
+        /* (the plane then has rt_sub_alloc_words(words) words: the caller's side of the flag) */
+        hipError_t e = hipMemsetAsync(plane + rt_sub_header_base(words), 0, RT_SUB_HEADER * 4, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(rt_sub_compact_kernel, dim3(blocks), dim3(RT_CULL_THREADS), 0, stream, a);
+        hipLaunchKernelGGL(rt_sub_refine_kernel, dim3((unsigned)sub_blocks), dim3(RT_CULL_THREADS), 0, stream, a);
+    }
     return hipGetLastError();
 }
 

@@ -312,6 +312,91 @@ RT_CULL_HD uint32_t rt_entry_word(const rt_cull_cone &c, const float *blob, int3
     return others > st.cand_hi ? rt_entry_triangle((uint32_t)st.cand) : 0u;
 }
 
+/* ================= THE SUB-ENTRY WORDS: the same word per sub-box of the jitter cube, for the pixels whose own word is 0 =================
+ * A pixel whose cone straddles a triangle edge or a silhouette, or has a direction interval that touches zero, has the word 0 although most
+ * of its samples are unambiguous.  The jitter cube [-J, J]^3 is split into RT_SUB_S^3 = 64 closed sub-boxes; sub-interval j of an axis is
+ * [tau_j, tau_j+1] with tau = -J, -J/2, 0, J/2, J, five exact floats.  Rounding is monotone, so for a jitter off_k in sub-interval j
+ * v_k = fl(P_k + off_k) lies in [fl(P_k + tau_j), fl(P_k + tau_j+1)] - rt_cull.h's own argument - and the SUB-CONE built from those two
+ * floats per axis (rt_sub_cone_of) holds every sample whose jitter falls in the sub-box.  rt_entry_word runs on the sub-cone as it is: no
+ * new predicate, no new error bound, and a sub-word `triangle T`, `nothing` or 0 has the meaning and the bit-identity argument above for
+ * those samples.  A jitter on a threshold belongs to both neighbouring closed sub-boxes: either word is valid for it.
+ *
+ * THE INDEX of a sample (rt_sub_index) is computed from the very floats px_gen adds to the direction; this one definition serves the
+ * render kernel, the host hooks and the tests.
+ *
+ * THE STORAGE.  Behind the entry words, in the same allocation (rt_sub_alloc_words): a header of RT_SUB_HEADER words whose first is the slot
+ * counter, then `cap` words - the pixel of each slot - and then `cap` tables of 64 sub-words; cap = rt_sub_cap(plane words), an eighth of
+ * the pre-pass's threads.  A pixel with a table carries its slot in its entry word as (slot + 1) << 2 | 2 (rt_sub_slot_word): bit 0 is
+ * clear, so it is no `triangle`; bits 1..0 are 10 and the rest is not 0, so it is neither `nothing` (2) nor 0.  Only an unflagged pixel
+ * whose word is 0 gets a slot; one that finds the tables full keeps 0.  Slot order is whatever the device's atomics make it: the image does
+ * not depend on it.
+ *
+ * WHAT A TABLE STORES.  The render kernel has one register for a pixel's gate word, entry word or slot word (rt_pixel.h: a second one held
+ * across the traversal loops costs it two VGPRs), so a table pixel's gate word rides in its table: a sub-word `triangle T` is stored as it
+ * is, `nothing` as RT_SUB_NOTHING - all ones: T << 1 | 1 of a triangle no leaf can name, and no gate word, whose bit 0 is clear - and 0,
+ * not known, as the pixel's gate word, which is what such a sample traverses with.  One load then brings whichever the sample needs
+ * (rt_sub_stored).  rt_sub_word_of gives the sub-word back: that is what the debug hooks report. */
+#define RT_SUB_NOTHING 0xffffffffu
+RT_CULL_HD uint32_t rt_sub_stored(uint32_t sub_word, uint32_t gate_word) { return sub_word == 0u ? gate_word & ~RT_ENTRY_TAG : sub_word == RT_ENTRY_NOTHING ? RT_SUB_NOTHING : sub_word; }
+RT_CULL_HD uint32_t rt_sub_word_of(uint32_t stored) { return stored == RT_SUB_NOTHING ? RT_ENTRY_NOTHING : (stored & RT_ENTRY_TAG) ? stored : 0u; }
+static_assert((RT_SUB_NOTHING >> 1) > RT_REF_START_MASK, "no leaf names the triangle RT_SUB_NOTHING is tagged with");
+#define RT_SUB_S 4
+#define RT_SUB_WORDS 64                  /* RT_SUB_S^3 sub-words per table */
+#define RT_SUB_HEADER 4                  /* words in front of the slots' pixels: the slot counter, three spare */
+#define RT_CULL_WITH_SUBENTRY 8          /* rt_launch_cull's view_flags: queue the refinement; without RT_CULL_WITH_ENTRY the pre-pass itself is not run (the plane has this view's words already) */
+/* The samples per pixel (spp x frames) from which a view's FIRST launch queues the refinement; below it the view's first reuse does
+ * (rt_cull_host::Plan::refine; RT_AMD_SUBENTRY_SAMPLES overrides).  Set where the measured gain of one launch is twice the measured refinement
+ * time: DESIGN.md section 24, "The sub-entry words", has the two figures. */
+#define RT_SUB_THRESHOLD_SAMPLES 2200
+static_assert(RT_CULL_WITH_SUBENTRY < (1 << RT_CULL_TRIS_SHIFT), "the flag sits below the triangles' offset");
+RT_CULL_HD uint32_t rt_sub_slot_word(uint32_t slot) { return ((slot + 1u) << 2) | 2u; }
+/* slot + 1 of a word that carries one, else 0 */
+RT_CULL_HD uint32_t rt_sub_slot_plus1(uint32_t word) { return (word & 3u) == 2u ? word >> 2 : 0u; }
+static_assert((((0u + 1u) << 2 | 2u) & RT_ENTRY_TAG) == 0u && ((0u + 1u) << 2 | 2u) != RT_ENTRY_NOTHING && (RT_ENTRY_NOTHING >> 2) == 0u && (RT_ENTRY_NOTHING & 3u) == 2u,
+              "a slot word reads as neither `triangle` nor `nothing` nor 0, and `nothing` carries no slot");
+RT_CULL_HD size_t rt_sub_cap(size_t plane_words) { return plane_words * 4; }
+RT_CULL_HD size_t rt_sub_header_base(size_t plane_words) { return rt_cull_alloc_words_entry(plane_words); }
+RT_CULL_HD size_t rt_sub_pixels_base(size_t plane_words) { return rt_sub_header_base(plane_words) + RT_SUB_HEADER; }
+RT_CULL_HD size_t rt_sub_tables_base(size_t plane_words) { return rt_sub_pixels_base(plane_words) + rt_sub_cap(plane_words); }
+RT_CULL_HD size_t rt_sub_alloc_words(size_t plane_words) { return rt_sub_tables_base(plane_words) + rt_sub_cap(plane_words) * RT_SUB_WORDS; }
+
+/* tau_j, j = 0 .. RT_SUB_S */
+RT_CULL_HD float rt_sub_tau(int j)
+{
+    return j <= 0 ? -RT_CULL_JITTER : j == 1 ? -0.5f * RT_CULL_JITTER : j == 2 ? 0.0f : j == 3 ? 0.5f * RT_CULL_JITTER : RT_CULL_JITTER;
+}
+/* the sub-interval of one jitter component, and the sub-box of a sample's three */
+RT_CULL_HD uint32_t rt_sub_axis_index(float off)
+{
+    return (uint32_t)(off >= -0.5f * RT_CULL_JITTER) + (uint32_t)(off >= 0.0f) + (uint32_t)(off >= 0.5f * RT_CULL_JITTER);
+}
+RT_CULL_HD uint32_t rt_sub_index(float off_x, float off_y, float off_z)
+{
+    return rt_sub_axis_index(off_x) + 4u * rt_sub_axis_index(off_y) + 16u * rt_sub_axis_index(off_z);
+}
+/* the cone of the samples of primary direction P whose jitter falls in sub-box idx: rt_cull_cone_of with the sub-interval's ends for -J, J */
+RT_CULL_HD rt_cull_cone rt_sub_cone_of(const float P[3], const float cam_pos[3], uint32_t idx)
+{
+    rt_cull_cone c;
+    c.ok = 1;
+    float largest = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        const int j = (int)((idx >> (2 * k)) & 3u);
+        const float lo = P[k] + rt_sub_tau(j), hi = P[k] + rt_sub_tau(j + 1);
+        c.o[k] = cam_pos[k];
+        if (!rt_cull_finite(lo) || !rt_cull_finite(hi) || !rt_cull_finite(cam_pos[k]) || !(fabsf(cam_pos[k]) <= RT_CULL_HUGE)) c.ok = 0;
+        c.sgn[k] = lo >= RT_CULL_TINY ? 1 : (hi <= -RT_CULL_TINY ? -1 : 0);
+        c.alo[k] = c.sgn[k] > 0 ? lo : -hi;
+        c.ahi[k] = c.sgn[k] > 0 ? hi : -lo;
+        const float a = fmaxf(fabsf(lo), fabsf(hi));
+        largest = a > largest ? a : largest;
+    }
+    if (!(largest >= 0.25f && largest <= 4.0f)) c.ok = 0;
+    return c;
+}
+/* does a pixel get a table?  An unflagged one whose own word is 0 (or a slot of an earlier refinement), in a jittered view */
+RT_CULL_HD bool rt_sub_wants_table(bool flagged, uint32_t entry_word) { return !flagged && (entry_word == 0u || rt_sub_slot_plus1(entry_word) != 0u); }
+
 /* ---- the kernel's triangle test (tri_closer_lanes, rt_intersect.h) restated for host code, operation for operation: accepted iff
  * t > RT_EPS_F, min(u, v, w) >= 0 (a NaN fails) and t < best.  What tests/sanitize/entry_soundness.cpp and the estimate walk. */
 RT_CULL_HD bool rt_entry_tri_closer(const float *q, const float o[3], const float d[3], float best, float &t_out)

@@ -179,6 +179,8 @@ struct CullPlane {
     bool enabled = true;                 /* RT_AMD_PRIMARY_CULL=0: every launch renders without the plane */
     bool gates = true;                   /* RT_AMD_SUBTREE_CULL=0: the pre-pass writes every gate word as 0 (the kernel then gates nothing) */
     bool entry = true;                   /* RT_AMD_PRIMARY_ENTRY=0: the pre-pass writes every entry word as 0 (rt_entry.h: every primary ray starts at the root) */
+    bool sub = true;                     /* RT_AMD_PRIMARY_SUBENTRY=0: no sub-entry tables (rt_entry.h): the allocation ends with the entry words and nothing is refined */
+    int64_t sub_threshold = 0;           /* RT_AMD_SUBENTRY_SAMPLES: a view's first launch queues the refinement if it draws at least this many samples per pixel (rt_cull_host::Plan::refine) */
 };
 
 /* knobs (RT_AMD_*), none changes an image: rt_schedule.h has them, their accepted ranges and what the kernel is handed for them

@@ -22,6 +22,13 @@
 #include "rt_traverse.h"
 #include "rt_vec.h"
 
+/* s_waitcnt vmcnt(0), expcnt and lgkmcnt at their maxima, as gfx9 encodes it (vmcnt in bits 3..0 and 15..14, expcnt in 6..4, lgkmcnt in
+ * 11..8): right for gfx950 and the rest of the family, and wrong for gfx10 and later, whose fields lie elsewhere */
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "RT_WAIT_VMCNT0 is the gfx9 encoding of s_waitcnt: give this target its own"
+#endif
+#define RT_WAIT_VMCNT0 0x0f70
+#define PX_SUBTABLE 0x40000000u       /* ... and: the pixel has a sub-entry table (rt_entry.h), and the loop's gate-word register holds its slot word instead */
 #define PX_NOCULL 0x80000000u         /* Px::id in the kernels that read the cull plane (rt_loop_culls): the pixel is NOT flagged by it */
 
 /* per-lane pixel state (registers) */
@@ -193,7 +200,7 @@ __device__ __forceinline__ void px_finish_pixel(Px &p, const rt_kernel_args &a, 
         return;
     }
     const V3 c = p.colour / (float)f.spp;
-    const unsigned id = CULL ? p.id & ~PX_NOCULL : p.id;
+    const unsigned id = CULL ? p.id & ~(PX_NOCULL | PX_SUBTABLE) : p.id;
     const int tile = (int)(id >> 6), within = (int)(id & 63u);
     int tx, ty, compact_row;
     tile_place(a, f, tile, tx, ty, compact_row);
@@ -575,6 +582,11 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
                 const uint32_t entry = plane[rt_cull_entry_base(rt_cull_words(f.W, f.H)) + pixel];
                 if (entry == RT_ENTRY_NOTHING) nocull = 0u;
                 if (entry & RT_ENTRY_TAG) gates = entry;
+                /* ... and a pixel whose own word is 0 may carry the slot of its sub-entry table there.  The slot word then takes the gate
+                 * word's place too, marked by PX_SUBTABLE in p.id (bit 30, which no id reaches either): the table's words for the sub-boxes
+                 * that are not known are the pixel's gate word itself, so px_gen's one load brings whichever the sample needs.  No register
+                 * of its own: one more held across the traversal loops puts the kernel above the generic kernel's 97 VGPRs */
+                if (rt_sub_slot_plus1(entry) != 0u) { gates = entry; nocull |= PX_SUBTABLE; }
             }
             p.id |= nocull;
             *px_gates = gates;
@@ -599,8 +611,12 @@ __device__ __forceinline__ void px_fetch(Px &p, Chunk &ch, const rt_kernel_args 
 /* ================= GEN: jitter the direction, test the simple objects ====================== */
 /* TRAITS: see rt_closest_simple (rt_intersect.h).  With RT_TRAIT_ONE_MESH a ray leaves as M_SHADE and the caller tests the one mesh's root box
  * at once (rt_render_loop.inc): there is no M_MESH and no mesh counter */
-template <bool HAS_MESH, int TRAITS = 0>
-__device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds &L)
+/* SUB (the kernel that reads the cull plane): *sub becomes the word the mesh start acts on (rt_render_loop.inc) - px_gates, the pixel's gate
+ * word or tagged entry word, or, for a primary ray of a pixel with a sub-entry table (PX_SUBTABLE: px_gates is then its slot word, rt_entry.h),
+ * the table's word for the sub-box of the very jitter added to the direction here.  The load is issued as soon as the jitter is known; the
+ * mesh start uses it behind the simple objects' tests. */
+template <bool HAS_MESH, int TRAITS = 0, bool SUB = false>
+__device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds &L, const Frame *f = nullptr, uint32_t px_gates = 0u, uint32_t *sub = nullptr)
 {
     V3 &o = p.o, &d = p.d;
     p.frame_steps += (unsigned)(RT_COST_GEN * RT_MAX_BATCH_FRAMES);
@@ -610,7 +626,22 @@ __device__ __forceinline__ void px_gen(Px &p, const rt_kernel_args &a, const Lds
         off.x = rt_jitter(rt_pcg_next(&p.rng));
         off.y = rt_jitter(rt_pcg_next(&p.rng));
         off.z = rt_jitter(rt_pcg_next(&p.rng));
+        if (SUB) {
+            uint32_t word = px_gates;
+            if (((unsigned)p.bounce | (~p.id & PX_SUBTABLE)) == 0u) {
+                /* (the plane's address as px_fetch reads it: two volatile scalar loads from the argument segment) */
+                typedef const __attribute__((address_space(1))) uint32_t *cull_words;
+                typedef const volatile __attribute__((address_space(4))) uint32_t *arg_words;
+                const arg_words args = (arg_words)__builtin_amdgcn_kernarg_segment_ptr();
+                const uint32_t plane_lo = args[offsetof(rt_kernel_args, cull_lo) / 4], plane_hi = args[offsetof(rt_kernel_args, cull_hi) / 4];
+                const cull_words plane = (cull_words)(uintptr_t)(((uint64_t)plane_hi << 32) | (uint64_t)plane_lo);
+                word = plane[rt_sub_tables_base(rt_cull_words(f->W, f->H)) + (size_t)(rt_sub_slot_plus1(px_gates) - 1u) * RT_SUB_WORDS + rt_sub_index(off.x, off.y, off.z)];
+            }
+            *sub = word;
+        }
         d = normalised(d + off);
+    } else if (SUB) {
+        *sub = px_gates;
     }
     if (HAS_MESH) p.inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);   /* src/ray.cu:198-202 (three short reciprocals behind one range check: -0.3 % cube, +0.5 % monkey - not taken) */
 

@@ -62,6 +62,8 @@
     /* CULL: the pixel's gate word, loaded by px_fetch with the pixel's cull bit and held in this register between the pixel's samples (the
      * alternatives and what was measured: DESIGN.md section 24, "The subtree cull") */
     uint32_t px_gates = 0u;
+    /* CULL: the word the mesh start acts on for the ray px_gen has just made: px_gates, or a table pixel's sub-word (rt_entry.h) */
+    uint32_t start_word = 0u;
     Chunk ch;
     ch.next = 0; ch.end = 0; ch.frame = 0; ch.exhausted = false;
 #ifdef RT_STATS
@@ -112,15 +114,17 @@
         RT_LAP(TM_FETCH);
         if (p.mode == M_GEN) {
             RT_STAT(ST_GEN);
-            px_gen<HAS_MESH, TRAITS>(p, a, L);
+            if (CULL) px_gen<HAS_MESH, TRAITS, CULL>(p, a, L, &f, px_gates, &start_word);
+            else px_gen<HAS_MESH, TRAITS>(p, a, L);
             if (ONE_MESH) {
                 /* the one mesh's root box, tested here and once: the MESH section's trip below with next_mesh == 0, and none after it (the
                  * ray came out of px_gen as M_SHADE, which it stays unless it enters the box) */
                 RT_STAT(ST_MESH);
                 const v4f m0 = L.meshes[0], m1 = L.meshes[1];
                 /* (CULL: a primary ray - bounce 0 - of a pixel the view's cull plane flags does not test the root box and stays M_SHADE: it would
-                 * enter no leaf, rt_cull.h.  Nothing else about the ray changes: the same draws, the same simple-object hit, the same shade) */
-                if (!(CULL && ((unsigned)p.bounce | (p.id & PX_NOCULL)) == 0u) && !(p.d.x != p.d.x || p.d.y != p.d.y || p.d.z != p.d.z)) {
+                 * enter no leaf, rt_cull.h.  Nothing else about the ray changes: the same draws, the same simple-object hit, the same shade.
+                 * So does a primary ray whose sub-word is `nothing`, RT_SUB_NOTHING in a table: no gate word and no tagged triangle reads so) */
+                if (!(CULL && ((unsigned)p.bounce | (p.id & PX_NOCULL)) == 0u) && !(CULL && ((unsigned)p.bounce | (start_word ^ RT_SUB_NOTHING)) == 0u) && !(p.d.x != p.d.x || p.d.y != p.d.y || p.d.z != p.d.z)) {
                     const uint32_t root_ref = __float_as_uint(m1.z);
                     float rd;
                     const bool rh = box_test(m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, p.o, p.inv, rd);
@@ -130,10 +134,11 @@
                         if (CULL) {
                             /* a primary ray of a pixel whose word is tagged `triangle T` (rt_entry.h) starts on the one-triangle leaf (T)
                              * with an empty stack and no gates: the leaf section tests T against best = RT_INF_F and merges.  Else the word
-                             * is the pixel's gate word */
-                            const bool tagged = p.bounce == 0 && (px_gates & RT_ENTRY_TAG) != 0u;
-                            if (tagged) cur = rt_entry_leaf(px_gates);
-                            w_ray_bits |= p.bounce == 0 && !tagged ? px_gates & ~RT_RAY_ZERO_DIR : 0u;
+                             * is the pixel's gate word.  For a table pixel's primary ray px_gen has put the sub-box's word there: a tagged
+                             * triangle, or the pixel's gate word where the sub-box is not known (rt_entry.h) */
+                            const bool tagged = p.bounce == 0 && (start_word & RT_ENTRY_TAG) != 0u;
+                            if (tagged) cur = rt_entry_leaf(start_word);
+                            w_ray_bits |= p.bounce == 0 && !tagged ? start_word & ~RT_RAY_ZERO_DIR : 0u;
                         }
                         p.mode = M_WAIT;
                         p.frame_steps |= 0x80000000u;
@@ -142,6 +147,12 @@
                 }
             }
         }
+        /* CULL: px_gen's load of a table pixel's sub-word is waited for here, on every path: a lane that does not reach the mesh start (a flagged
+         * pixel, a NaN direction) would carry it into the traversal loops, where the compiler then puts a wait into the descend and the leaf
+         * loop.  RT_WAIT_VMCNT0 (rt_pixel.h) is the gfx9 encoding of s_waitcnt vmcnt(0) with expcnt and lgkmcnt left alone.  It waits for every
+         * vector load outstanding, not only that one: here, at the end of the generate section, px_gen's load is the only one there can be
+         * (the section's other operands come from LDS and registers, and px_fetch's loads are consumed in px_fetch) */
+        if (CULL) __builtin_amdgcn_s_waitcnt(RT_WAIT_VMCNT0);
         RT_LAP(TM_GEN);
 
         if (HAS_MESH) {

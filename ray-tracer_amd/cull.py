@@ -13,6 +13,8 @@ GATE_STATS = ("pixels", "centre_steps", "centre_steps_gated", "pixels_with_dead_
 ENTRY_STATS = ("pixels_triangle", "pixels_nothing", "pixels_unknown", "centre_steps_triangle", "centre_steps_nothing", "centre_steps_unknown",
                "centre_tests_triangle", "centre_tests_nothing", "centre_tests_unknown", "triangles_classified")
 ENTRY_NOTHING = 2
+SUB_WORDS = 64
+SUBENTRY_STATS = ("pixels_wanting_table", "tables", "sub_triangle", "sub_nothing", "sub_unknown", "centre_steps_resolved", "centre_steps_all")
 STATS = ("root_entering", "flagged_root_entering", "centre_steps_flagged", "centre_steps_root_entering", "flagged", "words")
 
 
@@ -110,3 +112,39 @@ def primary_entry_host(scene, camera, antialias=True):
     if st != 0:
         raise ValueError("rt_debug_primary_entry_host refused its arguments (status %d)" % st)
     return words.reshape(int(camera.c.height), int(camera.c.width)), dict(zip(ENTRY_STATS, (int(x) for x in stats)))
+
+
+def primary_subentry_tables(ctx):
+    """(refined, pixels, words): whether the context's last render launch was handed a plane whose view has its sub-entry tables (csrc/rt_entry.h),
+    and those tables read back from the device keyed by pixel, in ascending order: pixels[i] = py * width + px, words[i, idx] the sub-word of
+    sub-box idx = jx + 4 jy + 16 jz - T << 1 | 1, ENTRY_NOTHING or 0 (both None if it was not); waits for the device"""
+    info = (C.c_int32 * 4)()
+    ctx._check(lib().rt_debug_primary_subentry(ctx._h, None, None, 0, info))
+    if not info[0]:
+        return False, None, None
+    n = int(info[3])
+    pixels, words = np.zeros(n, np.uint32), np.zeros((n, SUB_WORDS), np.uint32)
+    ctx._check(lib().rt_debug_primary_subentry(ctx._h, pixels.ctypes.data_as(_u32p), words.ctypes.data_as(_u32p), n, info))
+    return True, pixels[:int(info[3])], words[:int(info[3])]
+
+
+def primary_subentry_host(scene, camera, antialias=True, cap=-1):
+    """(pixels, words, stats) of the sub-entry tables computed on the host as the refinement writes them, keyed by pixel in ascending order; cap:
+    at most that many tables (the first pixels in order), -1 for what the image's allocation holds; `scene` as for primary_cull_host.  Needs no
+    GPU for a SceneObjects."""
+    v = rt_flat_view()
+    if isinstance(scene, Scene):
+        scene.ctx._check(lib().rt_debug_scene_read(scene.ctx._h, scene._h, C.byref(v)))
+    else:
+        scene._check(lib().rt_debug_flatten(scene._h, C.byref(v)))
+    stats = (C.c_int64 * 8)()
+    st = lib().rt_debug_primary_subentry_host(C.byref(v), C.byref(camera.c), 1 if antialias else 0, int(cap), None, None, 0, stats)
+    if st != 0:
+        raise ValueError("rt_debug_primary_subentry_host refused its arguments (status %d)" % st)
+    n = int(stats[1])
+    pixels, words = np.zeros(n, np.uint32), np.zeros((n, SUB_WORDS), np.uint32)
+    if n:
+        st = lib().rt_debug_primary_subentry_host(C.byref(v), C.byref(camera.c), 1 if antialias else 0, int(cap), pixels.ctypes.data_as(_u32p), words.ctypes.data_as(_u32p), n, stats)
+        if st != 0:
+            raise ValueError("rt_debug_primary_subentry_host refused its arguments (status %d)" % st)
+    return pixels, words, dict(zip(SUBENTRY_STATS, (int(x) for x in stats)))

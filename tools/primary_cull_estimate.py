@@ -36,6 +36,12 @@ def estimate(scene="monkey", width=128, height=72, antialias=True):
     st["entry_resolved_share"] = (et["pixels_triangle"] + et["pixels_nothing"]) / px if px else 0.0
     st["entry_step_share_removed"] = (et["centre_steps_triangle"] + et["centre_steps_nothing"]) / steps if steps else 0.0
     st["entry_test_share_removed"] = (et["centre_tests_triangle"] - et["pixels_triangle"] + et["centre_tests_nothing"]) / tests if tests else 0.0
+    # the sub-entry tables of the not-known pixels (csrc/rt_entry.h): every one of them gets a table here, whatever the image's allocation holds
+    _p, _w, sub = rt.primary_subentry_host(rt.SceneObjects(objs), rt.Camera(width, height), antialias, cap=1 << 30)
+    st.update({"sub_" + k: v for k, v in sub.items()})
+    boxes = sub["sub_triangle"] + sub["sub_nothing"] + sub["sub_unknown"]
+    st["sub_resolved_share"] = (sub["sub_triangle"] + sub["sub_nothing"]) / boxes if boxes else 0.0
+    st["sub_step_weighted_share"] = sub["centre_steps_resolved"] / sub["centre_steps_all"] if sub["centre_steps_all"] else 0.0
     return st
 
 
@@ -70,6 +76,8 @@ def main():
         st["entry_centre_tests_triangle"], st["entry_centre_tests_nothing"], st["entry_centre_tests_unknown"]))
     print("share of those node steps the entry words remove:   %.1f %%; of the triangle tests: %.1f %%" % (
         100 * st["entry_step_share_removed"], 100 * st["entry_test_share_removed"]))
+    print("sub-entry tables of the %d not-known pixels: sub-boxes triangle %d, nothing %d, not known %d: resolved %.1f %%, weighted by the centre ray's gated node steps %.1f %%" % (
+        st["sub_tables"], st["sub_sub_triangle"], st["sub_sub_nothing"], st["sub_sub_unknown"], 100 * st["sub_resolved_share"], 100 * st["sub_step_weighted_share"]))
 
 
 if __name__ == "__main__":
